@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: images/sec of the MMaDA-Parallel 8B parallel text+image sampler on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config {0,1,3,4}] [--scaling {weak,strong}]
+    python bench.py --gpus N --steps K --warmup W [--config {0,1,3,4}] [--scaling {weak,strong}] [--dump-outputs DIR]
         N = 1, 2, 4, 8 as a PLAIN command: for N > 1 bench.py starts its own N ranks (torch.distributed.run on 127.0.0.1,
         one rank per GPU over RCCL) and prints rank 0's JSON line as the last line of stdout
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W   (same thing)
@@ -100,7 +100,10 @@ def cpu_baseline(cfg, ids, text_rows, img_rows, seq_forwards, text_heads, img_he
     small = dict(cfg, n_layers=sample_layers)
     sd = synth.synthetic_state_dict(small, seed=0, device="cpu")
     L = ids.shape[1]
-    ncpu = os.cpu_count() or 8
+    # the CPUs this process may use (os.cpu_count() is the whole host's): its affinity mask, capped by OMP_NUM_THREADS
+    ncpu = len(os.sched_getaffinity(0))
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+        ncpu = max(1, min(ncpu, int(os.environ["OMP_NUM_THREADS"])))
     probe = dict(cfg, n_layers=1)
     best_t, best_n = None, None
     for n in sorted({min(ncpu, c) for c in (8, 16, 32, 64, ncpu // 2, ncpu) if c >= 1}):
@@ -367,6 +370,7 @@ def build_workload(args, cfgnum, model_cls_mod, dev, cfg, tp, world, rank):
                  "images/sec (512x512, 64 img + 128 text steps) MMaDA-Parallel-A 8B" + \
                  ("" if cfgnum == 1 else ", editing mode, cfg_scale=3 + cfg_img=4")
         return dict(model=model, run=run, images_per_step=B, flops_per_image=fl, workload=name, metric=metric, L=L,
+                    outputs=lambda: {"final_ids": state["final"], "pixels": state["pixels"]},   # what a caller of run() receives
                     state=state, launch_probe=launch_probe, cpu=dict(ids=job["input_ids"], text_rows=(job["text_start"], job["text_end"]),
                                           img_rows=(job["image_start"], job["image_start"] + N),
                                           seq_forwards=args.text_steps + 2 * n_img, text_heads=args.text_steps, img_heads=3 * n_img))
@@ -428,10 +432,32 @@ def build_workload(args, cfgnum, model_cls_mod, dev, cfg, tp, world, rank):
                 f"image_steps=30 text_cfg=2.5 image_cfg=4.0: 128 batch-2 forwards at L={L}, decode_code)")
         ids1 = torch.zeros((1, L), dtype=torch.long)
         return dict(model=model, run=run, images_per_step=jobs, flops_per_image=fl, workload=name, L=L, state=state,
+                    outputs=lambda: {"images": state["final"]},
                     metric="images/sec (512x512 edit, 30 img + 128 text steps) MMaDA-Parallel-M 8B",
                     cpu=dict(ids=ids1, text_rows=(L - T, L), img_rows=(P + 1, P + 1 + N), seq_forwards=2 * args.text_steps,
                              text_heads=2 * args.text_steps, img_heads=2 * n_img))
     raise SystemExit(f"--config {cfgnum}: only 0, 1 (headline), 3 (M, batch 4) and 4 (A editing, batch 16) have a single-node form")
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes the last timed step's outputs as <out_dir>/<name>.npy: float32 for floating outputs, float64 for integer ones
+    (exact below 2**53).  An array that does not fit in what is left of the budget is replaced by a fixed, seeded sample
+    of its flattened elements, so two runs with the same arguments stay comparable element for element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES - 128 * len(arrays)   # 128: the .npy header of each file
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):
+        t = t.detach().cpu()
+        a = (t.float() if t.is_floating_point() else t.double()).numpy()
+        if a.nbytes > left:
+            idx = np.random.default_rng(0).choice(a.size, size=left // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def self_launch(n, script=None, argv=None):
@@ -489,7 +515,13 @@ def main():
     ap.add_argument("--parallelism", choices=["tp", "dp"], default="tp",
                     help="tp (default, BASELINE configs[2]): the model is tensor-parallel over all ranks, batch = N jobs; "
                          "dp: every rank holds the full 16 GB model and runs its own job, no data-path collective")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed step computed as DIR/<name>.npy (rank 0; "
+                         "at most 64 MB, larger outputs as a fixed seeded sample).  A step's outputs depend on how many "
+                         "steps ran before it in the process: compare runs made with the same --warmup and --steps")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     own_steps = (32, 16) if args.config == 0 else (128, 64)
     args.text_steps = own_steps[0] if args.text_steps is None else args.text_steps
     args.timesteps = own_steps[1] if args.timesteps is None else args.timesteps
@@ -557,6 +589,8 @@ def main():
         smi.__exit__()
     cnt, ms, fl = (C.c_int32 * 5)(), (C.c_double * 5)(), (C.c_double * 5)()
     abi.check(lib.mmada_profile_end(h, cnt, ms, fl), "profile_end")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl["outputs"]())
     ranks_agree = None
     if use_dist:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)

@@ -106,8 +106,9 @@ def generate(model_fn: Callable[[torch.Tensor], torch.Tensor], input_ids: torch.
             if temperature != 0:
                 noise = torch.randn((1, seq_len), dtype=torch.bfloat16, generator=generator)  # :30-33
             else:
-                if remasking == "random":  # keep the GLOBAL generator in step: the reference draws even at temperature 0 (A.2)
-                    torch.randn((1, seq_len), dtype=torch.bfloat16)
+                # keep the generator in step: the reference draws even at temperature 0 (A.2), and the global one feeds the
+                # random fill of the read-out (:360-362) and the ranks of remasking='random'
+                torch.randn((1, seq_len), dtype=torch.bfloat16, generator=generator)
                 noise = torch.zeros((1, seq_len), dtype=torch.bfloat16)  # temperature 0: 0 * randn
             if tie_order == "torch":   # parallel_generator.py:304-344 + mask_by_random_topk :23-70 in torch ops
                 cur = ids[0, pos]

@@ -3,8 +3,12 @@ import sys
 
 # tests/test_gpu_tp.py runs the ranks of a tensor-parallel group as handles of ONE process, each with its compute stream and
 # the library's exchange stream, and a rank's wait kernel spins until its peer's launches run: every stream needs a hardware
-# queue of its own (the HIP runtime multiplexes streams over 4 by default; read when the runtime initialises)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
+# queue of its own (the HIP runtime multiplexes streams over 4 by default; read when the runtime initialises).  Raised, not
+# only defaulted: an environment that already sets a lower value leaves the ranks' streams sharing queues, and their
+# hand-offs time out
+_queues = os.environ.get("GPU_MAX_HW_QUEUES", "")
+if not _queues.isdigit() or int(_queues) < 24:
+    os.environ["GPU_MAX_HW_QUEUES"] = "24"
 
 import pytest
 

@@ -8,6 +8,9 @@ here, on the CPU: the reference loop runs against `mmada_parallel_amd.LLaDAForMu
 validation, row bookkeeping, `CausalLMOutputLite`, `LLaDAConfigLite`) with only the two device entry points underneath it
 (`forward_body`, `head_rows` — the ctypes calls) replaced by recorded logits, and must reproduce the trajectory the reference
 recorded with its own model stand-in (tests/golden/sampler_traj.npz, written by oracle/gen_golden.py) call for call.
+
+Where the reference tree is not mounted, the loop is oracle/generate_oracle.py, the restatement of the same loop that
+tests/test_oracle_golden.py pins to the same recording, calling the model the way the reference does.
 """
 import contextlib
 import io
@@ -20,9 +23,9 @@ import torch
 
 from helpers import GOLDEN, SAMPLER_CASES, STUB_CB, STUB_TEXT_VOCAB, stub_logits, tiny_job
 from mmada_parallel_amd.model import CausalLMOutputLite, LLaDAConfigLite, LLaDAForMultiModalGeneration
+from oracle import generate_oracle
 
 REF_A = "/root/reference/MMaDA-Parallel-A"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_A), reason="the reference tree is only mounted in the build container")
 
 
 class RecordedForward(LLaDAForMultiModalGeneration):
@@ -46,7 +49,32 @@ class RecordedForward(LLaDAForMultiModalGeneration):
         pass
 
 
+def _oracle_generate(model, input_ids, text_start, text_end, image_start, seq_len, newline_every, uncon_text, uncon_image,
+                     tokenizer, text_vocab_size, codebook_size, **kw):
+    """generate_oracle.generate driving `model(ids, infer=True, use_cache=False).logits` (:178,263-264), then the
+    reference's read-out of the final ids (:346-362), including the random fill of still-masked image positions."""
+    assert tokenizer is None
+    final = generate_oracle.generate(lambda ids: model(ids, infer=True, use_cache=False).logits, input_ids, text_start,
+                                     text_end, image_start, seq_len, newline_every, uncon_text=uncon_text,
+                                     uncon_image=uncon_image, text_vocab_size=text_vocab_size, codebook_size=codebook_size,
+                                     **kw)
+    text = [t for t in final[0, text_start:text_end].tolist() if t != generate_oracle.MASK_TOKEN]
+    image_end = image_start + seq_len + seq_len // newline_every
+    vq = []
+    for pos in range(image_start, image_end):
+        if int(input_ids[0, pos]) == generate_oracle.NEW_LINE:
+            continue
+        token = int(final[0, pos])
+        if token != generate_oracle.MASK_TOKEN:
+            vq.append(max(0, min(token - text_vocab_size, codebook_size - 1)))
+        else:
+            vq.append(int(torch.randint(0, codebook_size, (1,)).item()))
+    return vq, text
+
+
 def _reference_generate():
+    if not os.path.isdir(REF_A):
+        return _oracle_generate
     sys.path.insert(0, REF_A)
     try:
         from generators.parallel_generator import generate_ti2ti
