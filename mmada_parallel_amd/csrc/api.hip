@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <cmath>
 #include <utility>
@@ -186,26 +187,69 @@ int mmada_embed(mmada_handle* h, const int64_t* ids, int B, int L, void* stream)
                         h->cfg.rms_eps);
 }
 
+}  // extern "C"
+
+// ---- one block's launches, shared by this file's forward (m0 = 0, every row) and the tensor-parallel forward (tp_comm.hip, one
+// call per row chunk); each caller adds its own output side (residual and row window here, the partial-sum target there) ----
+GemmArgs qkv_args(const mmada_handle* h, int layer, int m0, int rows) {
+    const int d = h->cfg.d_model;
+    GemmArgs g = gemm_bt_args(h->xn + (size_t)m0 * d, h->layers[layer].wqkv, nullptr, rows, (h->hq_l + 2 * h->hkv_l) * 128, d, 0);
+    g.m_base = m0;
+    g.q = h->q; g.k = h->k; g.vT = h->vT; g.rope_cos = h->rope_cos; g.rope_sin = h->rope_sin;
+    g.Lp = h->Lp; g.Lkv = h->Lkv; g.Hq = h->hq_l; g.Hkv = h->hkv_l;
+    if (const CacheSlot* cc = h->cc) {  // dLLM cache step: this block's keys / values live in (and are written to) the slot
+        g.k = cc->K(layer); g.vT = cc->vT(layer); g.Lkv = cc->Lkv;
+        g.pos_map = h->cc_pos; g.Lq = h->Lkv; g.q_pos_shift = h->cc_qshift;
+    }
+    return g;
+}
+
+GemmArgs gate_up_args(const mmada_handle* h, int layer, int m0, int rows) {
+    const int d = h->cfg.d_model;
+    return gemm_bt_args(h->xn + (size_t)m0 * d, h->layers[layer].wgu, h->hbuf + (size_t)m0 * h->f_l, rows, 2 * h->f_l, d, h->f_l);
+}
+
+GemmArgs attn_out_args(const mmada_handle* h, int layer, int m0, int rows) {
+    const int d = h->cfg.d_model, K = h->hq_l * 128;
+    return gemm_bt_args(h->att + (size_t)m0 * K, h->layers[layer].wo, h->y + (size_t)m0 * d, rows, d, K, d);
+}
+
+GemmArgs down_args(const mmada_handle* h, int layer, int m0, int rows) {
+    const int d = h->cfg.d_model;
+    return gemm_bt_args(h->hbuf + (size_t)m0 * h->f_l, h->layers[layer].wdown, h->y + (size_t)m0 * d, rows, d, h->f_l, d);
+}
+
+int block_attention(mmada_handle* h, int layer, hipStream_t s, int wbeg, int W) {
+    const CacheSlot* cc = h->cc;
+    const double rows = W ? (double)h->B * W : (double)h->B * h->L;
+    ProfScope p(h, layer, 1, 4.0 * h->hq_l * rows * (cc ? cc->L : h->L) * 128.0, s);
+    if (cc)  // compact (or all) queries of this call against the slot's keys / values of the whole sequence
+        return launch_attention(h->q, cc->K(layer), cc->vT(layer), h->att, h->B, h->hq_l, h->hkv_l, cc->L, h->Lp, cc->Lkv, h->Lp,
+                                h->hq_l * 128, s, 0, h->Lkv);
+    if (W)
+        return launch_attention(h->q, h->k, h->vT, h->att, h->B, h->hq_l, h->hkv_l, h->L, wbeg + W, h->Lkv, W, h->hq_l * 128, s,
+                                wbeg);
+    return launch_attention(h->q, h->k, h->vT, h->att, h->B, h->hq_l, h->hkv_l, h->L, h->Lp, h->Lkv, h->Lp, h->hq_l * 128, s);
+}
+
+// every block of a one-rank forward, after the embedding
+static int run_blocks(mmada_handle* h, void* stream) {
+    for (int i = 0; i < h->cfg.n_layers; ++i)
+        if (mmada_attn_partial(h, i, stream) || mmada_mlp_partial(h, i, stream)) return 1;
+    return 0;
+}
+
+extern "C" {
+
 int mmada_attn_partial(mmada_handle* h, int layer, void* stream) {
     if (!h || h->M == 0) return mm_fail("mmada_attn_partial: call mmada_embed first");
     if (layer < 0 || layer >= h->cfg.n_layers) return mm_fail("mmada_attn_partial: bad layer");
     hipStream_t s = (hipStream_t)stream;
-    const LayerWeights& lw = h->layers[layer];
     const int d = h->cfg.d_model;
     if (layer == 0 && h->xn_is_layer0) {
         h->xn_is_layer0 = false;  // the embedding kernel normalised its rows already
-    } else if (launch_rmsnorm(h->x, lw.attn_norm, h->xn, h->M, d, h->cfg.rms_eps, s)) return 1;
-    GemmArgs g{};
-    g.A = h->xn; g.W = lw.wqkv; g.C = nullptr;
-    g.M = h->M; g.N = (h->hq_l + 2 * h->hkv_l) * 128; g.K = d;
-    g.lda = d; g.ldw = d; g.ldc = 0;
-    g.q = h->q; g.k = h->k; g.vT = h->vT; g.rope_cos = h->rope_cos; g.rope_sin = h->rope_sin;
-    g.Lp = h->Lp; g.Lkv = h->Lkv; g.Hq = h->hq_l; g.Hkv = h->hkv_l;
-    const CacheSlot* cc = h->cc;  // dLLM cache step: this block's keys / values live in (and are written to) the slot
-    if (cc) {
-        g.k = cc->K(layer); g.vT = cc->vT(layer); g.Lkv = cc->Lkv;
-        g.pos_map = h->cc_pos; g.Lq = h->Lkv; g.q_pos_shift = h->cc_qshift;
-    }
+    } else if (launch_rmsnorm(h->x, h->layers[layer].attn_norm, h->xn, h->M, d, h->cfg.rms_eps, s)) return 1;
+    const GemmArgs g = qkv_args(h, layer, 0, h->M);
     const double rows = (double)h->B * h->L;
     {
         ProfScope p(h, layer, 0, 2.0 * rows * g.N * g.K, s);
@@ -216,30 +260,17 @@ int mmada_attn_partial(mmada_handle* h, int layer, void* stream) {
     // The window END is rounded up to a multiple of 8 rows (inside the Lp-padded stream): the compact panel then meets the
     // shape contract of the 8-phase GEMM (whole 8-row LDS-DMA pieces); the up to 7 extra rows are computed like any other.
     int wbeg = 0, wend = 0, W = 0;
-    if (!cc && layer == h->cfg.n_layers - 1 && h->win_end > h->win_beg) {
+    if (!h->cc && layer == h->cfg.n_layers - 1 && h->win_end > h->win_beg) {
         if (h->win_end > h->L) return mm_fail("forward: consumed rows [%d,%d) exceed L=%d", h->win_beg, h->win_end, h->L);
         wbeg = h->win_beg & ~31;
         wend = std::min((h->win_end + 7) & ~7, h->Lp);
         W = wend - wbeg;
         if (W >= h->Lp) { wbeg = 0; W = 0; }  // nothing to skip
     }
+    if (block_attention(h, layer, s, wbeg, W)) return 1;
     const int Mo = W ? h->B * W : h->M;
     const double orows = W ? (double)h->B * W : rows;
-    {
-        ProfScope p(h, layer, 1, 4.0 * h->hq_l * orows * (cc ? cc->L : h->L) * 128.0, s);
-        if (cc) {  // compact (or all) queries of this call against the slot's keys / values of the whole sequence
-            if (launch_attention(h->q, g.k, g.vT, h->att, h->B, h->hq_l, h->hkv_l, cc->L, h->Lp, cc->Lkv, h->Lp,
-                                 h->hq_l * 128, s, 0, h->Lkv)) return 1;
-        } else if (W) {
-            if (launch_attention(h->q, h->k, h->vT, h->att, h->B, h->hq_l, h->hkv_l, h->L, wend, h->Lkv, W,
-                                 h->hq_l * 128, s, wbeg)) return 1;
-        } else if (launch_attention(h->q, h->k, h->vT, h->att, h->B, h->hq_l, h->hkv_l, h->L, h->Lp, h->Lkv, h->Lp,
-                                    h->hq_l * 128, s)) return 1;
-    }
-    GemmArgs o{};
-    o.A = h->att; o.W = lw.wo; o.C = h->y;
-    o.M = Mo; o.N = d; o.K = h->hq_l * 128;
-    o.lda = o.K; o.ldw = o.K; o.ldc = d;
+    GemmArgs o = attn_out_args(h, layer, 0, Mo);
     o.resid = h->x; o.ldr = d; o.resid_mod = h->cfg.tp_size; o.resid_rank = h->cfg.tp_rank;
     if (W) { o.rwin = W; o.rlp = h->Lp; o.rbeg = wbeg; }
     {
@@ -255,22 +286,15 @@ int mmada_mlp_partial(mmada_handle* h, int layer, void* stream) {
     if (!h || h->M == 0) return mm_fail("mmada_mlp_partial: call mmada_embed first");
     if (layer < 0 || layer >= h->cfg.n_layers) return mm_fail("mmada_mlp_partial: bad layer");
     hipStream_t s = (hipStream_t)stream;
-    const LayerWeights& lw = h->layers[layer];
     const int d = h->cfg.d_model;
-    if (launch_rmsnorm(h->x, lw.ff_norm, h->xn, h->Mcur, d, h->cfg.rms_eps, s)) return 1;
-    GemmArgs g{};
-    g.A = h->xn; g.W = lw.wgu; g.C = h->hbuf;
-    g.M = h->Mcur; g.N = 2 * h->f_l; g.K = d;
-    g.lda = d; g.ldw = d; g.ldc = h->f_l;
+    if (launch_rmsnorm(h->x, h->layers[layer].ff_norm, h->xn, h->Mcur, d, h->cfg.rms_eps, s)) return 1;
+    const GemmArgs g = gate_up_args(h, layer, 0, h->Mcur);
     const double rows = h->cur_W ? (double)h->Mcur : (double)h->B * h->L;
     {
         ProfScope p(h, layer, 3, 2.0 * rows * g.N * g.K, s);
         if (launch_gemm(EPI_SWIGLU, g, s)) return 1;
     }
-    GemmArgs o{};
-    o.A = h->hbuf; o.W = lw.wdown; o.C = h->y;
-    o.M = h->Mcur; o.N = d; o.K = h->f_l;
-    o.lda = h->f_l; o.ldw = h->f_l; o.ldc = d;
+    GemmArgs o = down_args(h, layer, 0, h->Mcur);
     o.resid = h->x; o.ldr = d; o.resid_mod = h->cfg.tp_size; o.resid_rank = h->cfg.tp_rank;
     {
         ProfScope p(h, layer, 4, 2.0 * rows * o.N * o.K, s);
@@ -303,24 +327,62 @@ int mmada_profile_end(mmada_handle* h, int32_t* count_out, double* ms_out, doubl
     return 0;
 }
 
+}  // extern "C"
+
+// ---- the measurement / test switches of mmada_set_option: set from any thread, read by a launch once, through switches() ----
+static struct {
+    std::atomic<int> gemm_config{-2};        // -2: the environment's (MMADA_GEMM_CFG, else -1)
+    std::atomic<int> gemm_silu_lut{-1};      // -1: the environment's (MMADA_GEMM_SILU_LUT=0: off, else on)
+    std::atomic<int> gemm_short_tiles{-1};   // -1: the environment's (MMADA_GEMM_SHORT_TILES=0: off, else on)
+    std::atomic<int> gemm_tile_order{-1};    // < 0: the environment's (MMADA_GEMM_TILE_ORDER, else 0)
+    std::atomic<int> attention_form{-1};     // < 0: the environment's (MMADA_ATTN_FORM, else 1)
+    std::atomic<int> probe_variant{0};
+    std::atomic<int> tp_allow_single_rank{0};
+} g_switches;
+
+static int env_int(const char* name, int fallback) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : fallback;
+}
+static int env_flag(const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '0' ? 0 : 1;
+}
+
+Switches switches() {
+    static const Switches env = {env_int("MMADA_GEMM_CFG", -1), env_flag("MMADA_GEMM_SILU_LUT"), env_flag("MMADA_GEMM_SHORT_TILES"),
+                                 env_int("MMADA_GEMM_TILE_ORDER", 0), env_int("MMADA_ATTN_FORM", 1), 0, 0};
+    const int cfg = g_switches.gemm_config, lut = g_switches.gemm_silu_lut, shrt = g_switches.gemm_short_tiles,
+              order = g_switches.gemm_tile_order, form = g_switches.attention_form;
+    return {cfg == -2 ? env.gemm_config : cfg, lut < 0 ? env.gemm_silu_lut : lut, shrt < 0 ? env.gemm_short_tiles : shrt,
+            order < 0 ? env.gemm_tile_order : order, form < 0 ? env.attention_form : form, g_switches.probe_variant,
+            g_switches.tp_allow_single_rank};
+}
+
+extern "C" {
+
 int mmada_set_option(const char* name, int value) {
     if (!name) return mm_fail("mmada_set_option: null name");
-    if (!strcmp(name, "gemm_config")) { gemm_force_config(value); return 0; }
-    if (!strcmp(name, "gemm_silu_lut")) { gemm_set_silu_lut(value); return 0; }
-    if (!strcmp(name, "gemm_short_tiles")) { gemm8_set_short_tiles(value); return 0; }
-    if (!strcmp(name, "gemm_tile_order")) { gemm8_set_tile_order(value); return 0; }
-    if (!strcmp(name, "attention_form")) { attention_force_form(value); return 0; }
-    if (!strcmp(name, "probe_variant")) { mfma_probe_set_variant(value); return 0; }
-    if (!strcmp(name, "tp_allow_single_rank")) { tp_allow_single_rank(value); return 0; }
+    static const struct { const char* name; std::atomic<int>* field; bool flag; } table[] = {
+        {"gemm_config", &g_switches.gemm_config, false},
+        {"gemm_silu_lut", &g_switches.gemm_silu_lut, true},
+        {"gemm_short_tiles", &g_switches.gemm_short_tiles, true},
+        {"gemm_tile_order", &g_switches.gemm_tile_order, false},
+        {"attention_form", &g_switches.attention_form, false},
+        {"probe_variant", &g_switches.probe_variant, false},
+        {"tp_allow_single_rank", &g_switches.tp_allow_single_rank, true},
+    };
+    for (const auto& o : table)
+        if (!strcmp(name, o.name)) {
+            o.field->store(o.flag ? value != 0 : value);   // flag: nonzero -> 1
+            return 0;
+        }
     return mm_fail("mmada_set_option: unknown option '%s'", name);
 }
 
 int mmada_gemm_swiglu_bt(const void* A, const void* W, void* C, int M, int N, int K, void* stream) {
     if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || N % 64) return mm_fail("mmada_gemm_swiglu_bt: bad argument");
-    GemmArgs g{};
-    g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.C = (bf16_t*)C;
-    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N / 2;
-    return launch_gemm(EPI_SWIGLU, g, (hipStream_t)stream);
+    return launch_gemm(EPI_SWIGLU, gemm_bt_args((const bf16_t*)A, (const bf16_t*)W, (bf16_t*)C, M, N, K, N / 2), (hipStream_t)stream);
 }
 
 int mmada_gemm_plan(int M, int N, int K) { return gemm_plan_code(M, N, K); }
@@ -355,11 +417,7 @@ int mmada_forward_body(mmada_handle* h, const int64_t* ids, int B, int L, void* 
         return tp_forward_body(h, (hipStream_t)stream);
     }
     if (mmada_embed(h, ids, B, L, stream)) return 1;
-    for (int i = 0; i < h->cfg.n_layers; ++i) {
-        if (mmada_attn_partial(h, i, stream)) return 1;
-        if (mmada_mlp_partial(h, i, stream)) return 1;
-    }
-    return 0;
+    return run_blocks(h, stream);
 }
 
 // ---- dLLM cache (model/modeling_llada.py:593-600,929-940,1244-1245,1406-1426) -----------------------------------------
@@ -429,17 +487,9 @@ int mmada_forward_cached(mmada_handle* h, int slot, const int64_t* ids, const in
     h->cc = &c;
     h->cc_pos = pos ? h->posmap : nullptr;
     h->cc_qshift = (pos && !q_pos_from_map) ? L - Tc : -1;
-    int rc = 0;
-    if (tp) {
-        // tensor parallel: the blocks, their exchanges and the cache hooks of this rank's heads run in tp_forward_body; its last
-        // exchange leaves xn = ln_f(x) on EVERY row of every rank, which is what the slot keeps (CacheSlot::normalized)
-        rc = tp_forward_body(h, s);
-    } else {
-        for (int i = 0; i < h->cfg.n_layers && !rc; ++i) {
-            rc = mmada_attn_partial(h, i, stream);
-            if (!rc) rc = mmada_mlp_partial(h, i, stream);
-        }
-    }
+    // tensor parallel: the blocks, their exchanges and the cache hooks of this rank's heads run in tp_forward_body; its last
+    // exchange leaves xn = ln_f(x) on EVERY row of every rank, which is what the slot keeps (CacheSlot::normalized)
+    const int rc = tp ? tp_forward_body(h, s) : run_blocks(h, stream);
     h->cc = nullptr; h->cc_pos = nullptr; h->cc_qshift = -1;
     if (rc) { h->M = 0; return 1; }
     // the rows just computed replace theirs in the slot's final residual stream (the reference scatters the logits,
@@ -485,11 +535,8 @@ int mmada_cache_head_rows(mmada_handle* h, int slot, const int32_t* rows, int R,
         if (tp_gather_rows(c.xfin(h->cfg.n_layers), rows, R, c.L, c.Lp, d, c.B * c.L, xg, s)) return 1;
     } else if (launch_rmsnorm_gather(c.xfin(h->cfg.n_layers), h->ln_f, xg, rows, R, c.L, c.Lp, d, h->cfg.rms_eps, s, 0, c.B * c.L))
         return 1;
-    GemmArgs g{};
-    g.A = xg; g.W = h->lm_head + (size_t)col_begin * d; g.C = (bf16_t*)logits_out;
-    g.M = R; g.N = col_end - col_begin; g.K = d;
-    g.lda = d; g.ldw = d; g.ldc = g.N;
-    return launch_gemm(EPI_STORE, g, s);
+    const int N = col_end - col_begin;
+    return launch_gemm(EPI_STORE, gemm_bt_args(xg, h->lm_head + (size_t)col_begin * d, (bf16_t*)logits_out, R, N, d, N), s);
 }
 
 int mmada_head_rows(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, void* logits_out,
@@ -507,11 +554,8 @@ int mmada_head_rows(mmada_handle* h, const int32_t* rows, int R, int col_begin, 
         if (tp_head_gather(h, rows, R, s)) return 1;
     } else if (launch_rmsnorm_gather(h->x, h->ln_f, h->xg, rows, R, h->L, h->cur_W ? h->cur_W : h->Lp, d, h->cfg.rms_eps, s,
                                      h->cur_beg, h->B * h->L)) return 1;
-    GemmArgs g{};
-    g.A = h->xg; g.W = h->lm_head + (size_t)col_begin * d; g.C = (bf16_t*)logits_out;
-    g.M = R; g.N = col_end - col_begin; g.K = d;
-    g.lda = d; g.ldw = d; g.ldc = g.N;
-    return launch_gemm(EPI_STORE, g, s);
+    const int N = col_end - col_begin;
+    return launch_gemm(EPI_STORE, gemm_bt_args(h->xg, h->lm_head + (size_t)col_begin * d, (bf16_t*)logits_out, R, N, d, N), s);
 }
 
 int mmada_set_consumed_rows(mmada_handle* h, int row_begin, int row_end) {
@@ -627,10 +671,7 @@ int mmada_lfq_gather(mmada_handle* h, const int64_t* idx, int B, int N, int nbit
 
 int mmada_gemm_bt(const void* A, const void* W, void* C, int M, int N, int K, void* stream) {
     if (!A || !W || !C) return mm_fail("mmada_gemm_bt: null argument");
-    GemmArgs g{};
-    g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.C = (bf16_t*)C;
-    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
-    return launch_gemm(EPI_STORE, g, (hipStream_t)stream);
+    return launch_gemm(EPI_STORE, gemm_bt_args((const bf16_t*)A, (const bf16_t*)W, (bf16_t*)C, M, N, K, N), (hipStream_t)stream);
 }
 
 int mmada_rmsnorm(const void* x, const void* w, void* out, int rows, int d, float eps, void* stream) {

@@ -336,23 +336,15 @@ int attention_chunks(int pairs, int groups, int keys) {
     return best ? best : 1;
 }
 
-static std::atomic<int> g_attn_form{-1};  // -1: read MMADA_ATTN_FORM once
-void attention_force_form(int form) { g_attn_form = form; }  // measurement / test hook; -1: back to MMADA_ATTN_FORM / default
-
-// form 1 (default): waves 4-7 run LATE (P·V one interval behind); form 0: every wave in the plain order — the same arithmetic
-// per query row, bit-identical output (tests/test_gpu_kernels.py::test_attention_forms_are_bit_identical).
+// switch "attention_form" 1 (default): waves 4-7 run LATE (P·V one interval behind); 0: every wave in the plain order — the same
+// arithmetic per query row, bit-identical output (tests/test_gpu_kernels.py::test_attention_forms_are_bit_identical).
 int launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* vT, bf16_t* out, int B, int Hq, int Hkv, int L,
                      int Lq_rows, int Lkv, int out_rows_per_batch, int ld_out, hipStream_t s, int q_begin, int Lq_alloc) {
     if (L <= 0 || B <= 0) return 0;
     if (Lkv % 64 || Lkv < L) return mm_fail("attention: Lkv=%d must be a multiple of 64 and >= L=%d", Lkv, L);
     if (Hq % Hkv) return mm_fail("attention: n_heads %% n_kv_heads != 0");
     if (q_begin < 0 || (q_begin & 31) || q_begin >= Lq_rows) return mm_fail("attention: bad q_begin=%d", q_begin);
-    int form = g_attn_form.load(std::memory_order_relaxed);
-    if (form < 0) {
-        const char* e = getenv("MMADA_ATTN_FORM");
-        form = e ? atoi(e) : 1;
-        g_attn_form.store(form, std::memory_order_relaxed);
-    }
+    const int form = switches().attention_form;
     if (form != 0 && form != 1) return mm_fail("attention: form %d does not exist (0: plain order, 1: late waves)", form);
     static MmOncePerDevice attr_set;
     MM_ONCE_PER_DEVICE(attr_set, MM_CHECK_HIP(hipFuncSetAttribute((const void*)attn16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT16_LDS)));

@@ -20,8 +20,6 @@
 //
 // Epilogues reproduce the reference's rounding points exactly: every nn.Linear output is rounded to bf16 before
 // anything else touches it.
-#include <cstdlib>
-
 #include <atomic>
 #include <mutex>
 
@@ -179,7 +177,6 @@ int launch_cfg(const GemmArgs& g, hipStream_t s) {
 //     fitted to tools/gemm_sweep.py (profiles/r03_gemm8_sweep*.txt).
 // Both kernels accumulate a K-tile at a time in the same order with the same MFMA, so the choice never changes a bit of
 // the result (tests/test_gpu_kernels.py::test_gemm_configurations_are_bit_identical).
-constexpr float OLD_SCALE = 1.0f;                    // 16-wave model vs this round's measurements
 // 8-phase kernel: us per (row of 256 columns x K-tile), per round.  D0 / D1 re-fitted in round 4 (6.0 / 0.03 before): the epilogues
 // lost half of their instructions with the hardware fp32 -> bf16 conversion (tools/fit_gemm8_cost.py on
 // profiles/r04_gemm8_sweep_final.txt; with the old constants the short-K tensor-parallel shapes went to the slower 16-wave kernel)
@@ -187,25 +184,17 @@ constexpr float A8 = 0.00483f, D0 = 2.7f, D1 = 0.025f;
 constexpr float H8[GEMM8_NCFG] = {1.0f, 1.0f, 1.08f, 1.08f};
 struct Plan { bool p8; int code; };  // code: GEMM8_* configuration or the 16-wave kernel's BM
 
-std::atomic<int> g_force{-2};  // -2: read MMADA_GEMM_CFG once; -1: automatic; else gemm_force_config's code
-
-Plan plan(const GemmArgs& g) {
-    if (g_force == -2) {
-        const char* e = getenv("MMADA_GEMM_CFG");  // e.g. MMADA_GEMM_CFG=1 (GEMM8_256x256) or 1160 (16-wave, BM = 160)
-        g_force = e ? atoi(e) : -1;
-        const char* b = getenv("MMADA_GEMM_BM");   // round-2 spelling: the 16-wave kernel with this BM
-        if (!e && b) g_force = 1000 + atoi(b);
-    }
+// force: the "gemm_config" switch (Switches).  A pinned 8-phase configuration the shape cannot run gets the automatic pick.
+Plan plan(const GemmArgs& g, int force) {
     const bool can8 = gemm8_supports(g);
 #ifdef MMADA_TUNE
-    if (g_force >= 0 && g_force < GEMM8_NCFG + 20 && can8) return {true, g_force};
+    if (force >= 0 && force < GEMM8_NCFG + 20 && can8) return {true, force};
 #endif
-    if (g_force >= 0 && g_force < GEMM8_NCFG && can8) return {true, g_force};
-    if (g_force >= 1000) {
-        const int bm = g_force - 1000;
+    if (force >= 0 && force < GEMM8_NCFG && can8) return {true, force};
+    if (force >= 1000) {
+        const int bm = force - 1000;
         if (bm == 128 || bm == 160 || bm == 192 || bm == 224 || bm == 256 || bm == 320) return {false, bm};
     }
-    static const bool no8 = [] { const char* e = getenv("MMADA_GEMM_NO8"); return e && e[0] == '1'; }();
     const int M = g.M, N = g.N, nk = g.K / BK;
     Plan best{false, 256};
     float best_cost = 1e30f;
@@ -217,11 +206,11 @@ Plan plan(const GemmArgs& g) {
         for (int i = 0; i < 6; ++i) {
             const int bm = cand[i];
             const int tiles = ((M + bm - 1) / bm) * ntn;
-            const float cost = (float)((tiles + 255) / 256) * (A * bm * nk * h[i] + C0 + C1 * bm) * OLD_SCALE;
+            const float cost = (float)((tiles + 255) / 256) * (A * bm * nk * h[i] + C0 + C1 * bm);
             if (cost < best_cost) { best_cost = cost; best = {false, bm}; }
         }
     }
-    if (can8 && !no8) {
+    if (can8) {
         const int bm8[GEMM8_NCFG] = {320, 256, 160, 320}, bn8[GEMM8_NCFG] = {256, 256, 256, 128};
         for (int c = 0; c < GEMM8_NCFG; ++c) {
             const int tiles = ((M + bm8[c] - 1) / bm8[c]) * ((N + bn8[c] - 1) / bn8[c]);
@@ -234,9 +223,9 @@ Plan plan(const GemmArgs& g) {
 }
 
 template <int EPI>
-int launch_t(const GemmArgs& g, hipStream_t s) {
-    const Plan p = plan(g);
-    if (p.p8) return launch_gemm8(EPI, p.code, g, s);
+int launch_t(const GemmArgs& g, const Switches& sw, hipStream_t s) {
+    const Plan p = plan(g, sw.gemm_config);
+    if (p.p8) return launch_gemm8(EPI, p.code, g, sw, s);
     switch (p.code) {
         case 320: return launch_cfg<EPI, 320, 4, 4>(g, s);
         case 256: return launch_cfg<EPI, 256, 4, 4>(g, s);
@@ -249,46 +238,17 @@ int launch_t(const GemmArgs& g, hipStream_t s) {
 
 }  // namespace
 
-void gemm_force_config(int code) { g_force = code; }
-
 // what the planner would launch for a plain [M, K] x [N, K]^T product (host arithmetic only): 0..3 = GEMM8_* configuration,
 // 1000 + BM = the 16-wave kernel — tests/test_host_logic.py holds it against the committed sweep table
 int gemm_plan_code(int M, int N, int K) {
-    GemmArgs g{};
-    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
     if (M <= 0 || N <= 0 || K <= 0 || K % BK) return -1;
-    const Plan p = plan(g);
+    const Plan p = plan(gemm_bt_args(nullptr, nullptr, nullptr, M, N, K, N), switches().gemm_config);
     return p.p8 ? p.code : 1000 + p.code;
 }
 
-// 8 zero rows of up to ZERO_ROW_ELEMS / 8 elements per device (never freed: process lifetime): the source of the A rows of
-// the last row tile that lie beyond M
-static int zero_rows_for_device(const bf16_t** out) {
-    static std::atomic<bf16_t*> rows[16];
-    static std::mutex mu;
-    static const bool enabled = [] { const char* e = getenv("MMADA_GEMM_ZEROPAD"); return !(e && e[0] == '0'); }();
-    *out = nullptr;
-    if (!enabled) return 0;
-    int dev = 0;
-    MM_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16) return 0;
-    bf16_t* have = rows[dev].load(std::memory_order_acquire);
-    if (!have) {   // normally built by gemm_prepare_device (mmada_create); a bare mmada_gemm_bt call gets here
-        std::lock_guard<std::mutex> lock(mu);
-        have = rows[dev].load(std::memory_order_acquire);
-        if (!have) {
-            bf16_t* p = nullptr;
-            MM_CHECK_HIP(hipMalloc(&p, ZERO_ROW_ELEMS * sizeof(bf16_t)));
-            MM_CHECK_HIP(hipMemset(p, 0, ZERO_ROW_ELEMS * sizeof(bf16_t)));
-            rows[dev].store(p, std::memory_order_release);
-            have = p;
-        }
-    }
-    *out = have;
-    return 0;
-}
-
-// ---- the SiLU table of the SwiGLU epilogue (gemm_epilogue.h: SiluLut), one per device, filled by the function it replaces ----
+// ---- per-device constants of the launches, allocated once and never freed (process lifetime): 8 zero rows (the source of the A
+// rows of the last row tile that lie beyond M) and the SiLU table of the SwiGLU epilogue (gemm_epilogue.h: SiluLut), filled by
+// the function it replaces ----
 __global__ void silu_lut_kernel(uint16_t* t) {
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (unsigned)gemm_detail::SiluLut::ENTRIES) return;
@@ -300,41 +260,41 @@ __global__ void silu_lut_kernel(uint16_t* t) {
     }
     t[idx] = v;
 }
-static std::atomic<int> g_silu_lut{-1};  // -1: read MMADA_GEMM_SILU_LUT once (default on)
-static int silu_lut_for_device(const uint16_t** out, hipStream_t s) {
-    static std::atomic<uint16_t*> lut[16];
+struct DeviceConsts { const bf16_t* zero_row; const uint16_t* silu_lut; };
+
+// The record of the current device; built on first use on `s` (normally by gemm_prepare_device; a bare mmada_gemm_bt call gets
+// here).  Two host threads: one builds it, the other waits.  A hipMalloc + synchronise cannot run under hipGraph capture (e.g. a
+// graph captured on a device no handle was created on): that launch gets no record — its pad rows re-read row M-1 and SiLU is
+// evaluated, the same bits — and a later eager launch builds it.  {null, null} on a device beyond the 16 slots.
+static int device_consts(DeviceConsts* out, hipStream_t s) {
+    static DeviceConsts rec[16];
+    static std::atomic<bool> ready[16];
     static std::mutex mu;
-    *out = nullptr;
-    if (g_silu_lut.load(std::memory_order_relaxed) < 0) {
-        const char* e = getenv("MMADA_GEMM_SILU_LUT");
-        g_silu_lut.store(e && e[0] == '0' ? 0 : 1, std::memory_order_relaxed);
-    }
-    if (!g_silu_lut.load(std::memory_order_relaxed)) return 0;
+    *out = DeviceConsts{};
     int dev = 0;
     MM_CHECK_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= 16) return 0;
-    uint16_t* have = lut[dev].load(std::memory_order_acquire);
-    if (!have) {   // first SwiGLU launch on this device: allocate and fill once (two host threads: one does it, the other waits)
-        // A hipMalloc + synchronise cannot run under hipGraph capture (e.g. the option switched on after the eager warm-up
-        // step): that launch evaluates SiLU instead — the same bits — and a later eager launch builds the table.
+    if (!ready[dev].load(std::memory_order_acquire)) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
             (void)hipGetLastError();
             return 0;
         }
         std::lock_guard<std::mutex> lock(mu);
-        have = lut[dev].load(std::memory_order_acquire);
-        if (!have) {
-            uint16_t* p = nullptr;
-            MM_CHECK_HIP(hipMalloc(&p, gemm_detail::SiluLut::BYTES));
-            hipLaunchKernelGGL(silu_lut_kernel, dim3((gemm_detail::SiluLut::ENTRIES + 255) / 256), dim3(256), 0, s, p);   // ordered before the GEMM
+        if (!ready[dev].load(std::memory_order_acquire)) {
+            bf16_t* zero = nullptr;
+            uint16_t* lut = nullptr;
+            MM_CHECK_HIP(hipMalloc(&zero, ZERO_ROW_ELEMS * sizeof(bf16_t)));
+            MM_CHECK_HIP(hipMalloc(&lut, gemm_detail::SiluLut::BYTES));
+            MM_CHECK_HIP(hipMemsetAsync(zero, 0, ZERO_ROW_ELEMS * sizeof(bf16_t), s));
+            hipLaunchKernelGGL(silu_lut_kernel, dim3((gemm_detail::SiluLut::ENTRIES + 255) / 256), dim3(256), 0, s, lut);
             MM_CHECK_HIP(hipGetLastError());
-            MM_CHECK_HIP(hipStreamSynchronize(s));   // once per device: another stream's first SwiGLU launch must not overtake the fill
-            lut[dev].store(p, std::memory_order_release);
-            have = p;
+            MM_CHECK_HIP(hipStreamSynchronize(s));   // another stream's first launch must not overtake the fill
+            rec[dev] = {zero, lut};
+            ready[dev].store(true, std::memory_order_release);
         }
     }
-    *out = have;
+    *out = rec[dev];
     return 0;
 }
 // Everything a GEMM launch would otherwise allocate lazily (the zero rows, the SiLU table: a hipMalloc and a stream
@@ -342,33 +302,31 @@ static int silu_lut_for_device(const uint16_t** out, hipStream_t s) {
 // tensor-parallel rank group driven by one host thread deadlocks (until the hand-off timeout) if the first SwiGLU launch of the
 // process synchronises rank 0's stream while rank 1's kernels are not enqueued yet.
 int gemm_prepare_device() {
-    const bf16_t* z = nullptr;
-    if (zero_rows_for_device(&z)) return 1;
-    const uint16_t* lut = nullptr;
-    return silu_lut_for_device(&lut, (hipStream_t)0);
+    DeviceConsts dc;
+    return device_consts(&dc, (hipStream_t)0);
 }
 
-void gemm_set_silu_lut(int on) { g_silu_lut.store(on != 0 ? 1 : 0, std::memory_order_relaxed); }
-
 int launch_gemm(int epi, const GemmArgs& g_in, hipStream_t s) {
+    const Switches sw = switches();   // one snapshot decides the whole launch
+    DeviceConsts dc;
+    if (device_consts(&dc, s)) return 1;
     GemmArgs g = g_in;
-    g.silu_lut = nullptr;
-    if (epi == EPI_SWIGLU && silu_lut_for_device(&g.silu_lut, s)) return 1;
+    g.silu_lut = epi == EPI_SWIGLU && sw.gemm_silu_lut ? dc.silu_lut : nullptr;
     // the 16-wave kernel reads K zeros, the 8-phase kernel a block of 8 rows x lda
-    if (g.K <= ZERO_ROW_ELEMS / 8 && g.lda <= ZERO_ROW_ELEMS / 8 && zero_rows_for_device(&g.zero_row)) return 1;
+    g.zero_row = g.K <= ZERO_ROW_ELEMS / 8 && g.lda <= ZERO_ROW_ELEMS / 8 ? dc.zero_row : nullptr;
     if (g.M <= 0 || g.N <= 0) return 0;
     if (g.K % BK != 0 || g.K <= 0) return mm_fail("gemm: K=%d must be a positive multiple of %d", g.K, BK);
     if ((g.lda % 8) || (g.ldw % 8)) return mm_fail("gemm: lda/ldw must be multiples of 8 elements");
     switch (epi) {
-        case EPI_STORE: return launch_t<EPI_STORE>(g, s);
-        case EPI_RESID: return launch_t<EPI_RESID>(g, s);
+        case EPI_STORE: return launch_t<EPI_STORE>(g, sw, s);
+        case EPI_RESID: return launch_t<EPI_RESID>(g, sw, s);
         case EPI_SWIGLU:
             if (g.N % 64) return mm_fail("gemm/swiglu: N must be a multiple of 64");
-            return launch_t<EPI_SWIGLU>(g, s);
+            return launch_t<EPI_SWIGLU>(g, sw, s);
         case EPI_QKV:
             if (g.N != (g.Hq + 2 * g.Hkv) * 128) return mm_fail("gemm/qkv: N mismatch");
             if (g.Lp % 8 || g.m_base % 8) return mm_fail("gemm/qkv: Lp and m_base must be multiples of 8");
-            return launch_t<EPI_QKV>(g, s);
+            return launch_t<EPI_QKV>(g, sw, s);
     }
     return mm_fail("gemm: bad epilogue %d", epi);
 }

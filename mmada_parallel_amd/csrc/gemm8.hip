@@ -28,8 +28,6 @@
 //   WAR: a slot is re-staged >= 2 phases after the phase that read it.
 // The counted waits assume that NOTHING but LDS-DMA is in the vector-memory queue between the prologue and the last
 // wait: tests/test_isa.py disassembles the library and checks that the main loops contain no scratch or global access.
-#include <cstdlib>
-
 #include "gemm_epilogue.h"
 
 namespace {
@@ -366,18 +364,6 @@ struct Gemm8 {
     }
 };
 
-// mmada_set_option("gemm_short_tiles", 0) / MMADA_GEMM_SHORT_TILES=0: every row tile full height (the round-3 kernel; A/B timing)
-std::atomic<int> g_short_tiles{-1};
-bool short_tiles_on() {
-    if (g_short_tiles < 0) {
-        const char* e = getenv("MMADA_GEMM_SHORT_TILES");
-        g_short_tiles = e && e[0] == '0' ? 0 : 1;
-    }
-    return g_short_tiles != 0;
-}
-
-std::atomic<int> g_tile_order{-1};  // -1: read MMADA_GEMM_TILE_ORDER once; 0: per-tile default (launch_cfg8); GM * 100 + GN (GM = 99: all row tiles)
-
 template <int EPI, class G>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -431,7 +417,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
 }
 
 template <int EPI, class G>
-int launch_cfg8(const GemmArgs& g, hipStream_t s) {
+int launch_cfg8(const GemmArgs& g, const Switches& sw, hipStream_t s) {
     auto fn = gemm8_kernel<EPI, G>;
     static MmOncePerDevice attr_set;
     constexpr int LDS_BYTES = G::LDS + (EPI == EPI_SWIGLU ? SiluLut::BYTES : 0);
@@ -439,49 +425,48 @@ int launch_cfg8(const GemmArgs& g, hipStream_t s) {
     const int ntm = (g.M + G::BM - 1) / G::BM, ntn = (g.N + G::BN - 1) / G::BN;
     GemmArgs ga = g;
     // short row tiles when ntm - 1 tiles of 304 rows and one of <= 320 cover M (same tile count, 5 % fewer MFMAs in all
-    // but the last row tile): M = 2440 -> 7 x 304 + 312, M = 4880 -> 15 x 304 + 320
-    ga.row_drop = G::CAN_DROP && short_tiles_on() && ntm >= 2 && (ntm - 1) * G::SHORT_BM + G::BM >= g.M ? 1 : 0;
-    if (g_tile_order < 0) {
-        const char* e = getenv("MMADA_GEMM_TILE_ORDER");
-        g_tile_order = e ? atoi(e) : 0;
-    }
+    // but the last row tile): M = 2440 -> 7 x 304 + 312, M = 4880 -> 15 x 304 + 320.  Switch "gemm_short_tiles" 0: every row tile
+    // full height (the round-3 kernel; A/B timing)
+    ga.row_drop = G::CAN_DROP && sw.gemm_short_tiles && ntm >= 2 && (ntm - 1) * G::SHORT_BM + G::BM >= g.M ? 1 : 0;
     // Default order: per XCD-round of 32 tiles the fabric delivers gm A panels (BM rows each) + gn W panels (BN rows each), gm x gn
     // = 32, least when gm * BM ~ gn * BN: 4 x 8 for the 320 x 256 tile (FETCH_SIZE -6 % against 8 x 4, gate/up +1.3 % at M = 2440,
     // every projection +0.6 ... 1.9 % at M = 4880: profiles/r05_tile_order_fetch.txt, r05_block_ab.txt), 8 x 4 bands of 1024
-    // columns for the shorter tiles (there 4 x 8 measured -0.6 ... -2.6 %).  Any order gives the same bits.
+    // columns for the shorter tiles (there 4 x 8 measured -0.6 ... -2.6 %).  Any order gives the same bits.  Switch "gemm_tile_order"
+    // GM * 100 + GN: groups of GM row tiles (99: all) x GN column tiles instead
     constexpr int DEF_GM = (G::BM == 320 && G::BN == 256) ? 4 : 0, DEF_GN = (G::BM == 320 && G::BN == 256) ? 8 : 1024 / G::BN;
-    ga.tile_gm = g_tile_order > 0 ? g_tile_order / 100 : DEF_GM;
-    ga.tile_gn = g_tile_order > 0 && g_tile_order % 100 > 0 ? g_tile_order % 100 : DEF_GN;
+    const int order = sw.gemm_tile_order;
+    ga.tile_gm = order > 0 ? order / 100 : DEF_GM;
+    ga.tile_gn = order > 0 && order % 100 > 0 ? order % 100 : DEF_GN;
     hipLaunchKernelGGL(fn, dim3(ntm * ntn), dim3(512), LDS_BYTES, s, ga);
     MM_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 template <int EPI>
-int launch_epi8(int cfg, const GemmArgs& g, hipStream_t s) {
+int launch_epi8(int cfg, const GemmArgs& g, const Switches& sw, hipStream_t s) {
     constexpr int SW = EPI == EPI_QKV ? 2 : 1;
     switch (cfg) {
         // the balanced read schedule (OPT 2) on every tile.  Rounds 3-4 kept the first schedule on 320 x 256 because its RESID /
         // QKV builds spilled inside the loop with the balanced one; with the tail K-tiles in a one-trip loop (run()) all four
         // epilogues compile spill-free (254-255 VGPRs) and the in-model A/B reads +0.4 ... 1.0 % on gate/up and QKV, +-0 on the
         // rest (profiles/r05_block_ab_balanced.txt; tuning build: configuration 6 = the first schedule)
-        case GEMM8_320x256: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 2>>(g, s);
-        case GEMM8_256x256: return launch_cfg8<EPI, Gemm8<256, 256, 2, 4, SW, 2>>(g, s);
-        case GEMM8_160x256: return launch_cfg8<EPI, Gemm8<160, 256, 2, 4, SW, 2>>(g, s);
-        case GEMM8_320x128: return launch_cfg8<EPI, Gemm8<320, 128, 4, 2, SW, 2>>(g, s);
+        case GEMM8_320x256: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 2>>(g, sw, s);
+        case GEMM8_256x256: return launch_cfg8<EPI, Gemm8<256, 256, 2, 4, SW, 2>>(g, sw, s);
+        case GEMM8_160x256: return launch_cfg8<EPI, Gemm8<160, 256, 2, 4, SW, 2>>(g, sw, s);
+        case GEMM8_320x128: return launch_cfg8<EPI, Gemm8<320, 128, 4, 2, SW, 2>>(g, sw, s);
 #ifdef MMADA_TUNE
-        case 4: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 3>>(g, s);    // balanced + static s_setprio for the late group
-        case 5: return launch_cfg8<EPI, Gemm8<320, 128, 4, 2, SW, 0>>(g, s);
-        case 6: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 0>>(g, s);    // the first read schedule (rounds 3-4 production)
-        case 7: return launch_cfg8<EPI, Gemm8<256, 256, 2, 4, SW, 0>>(g, s);
-        case 8: return launch_cfg8<EPI, Gemm8<160, 256, 2, 4, SW, 0>>(g, s);
-        case 9: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 4>>(g, s);    // DIAG: no MFMA
-        case 10: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 8>>(g, s);   // DIAG: no LDS-DMA
-        case 11: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 16>>(g, s);  // DIAG: no ds_reads
-        case 12: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 24>>(g, s);  // DIAG: MFMAs + barriers only
-        case 13: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 20>>(g, s);  // DIAG: LDS-DMA + barriers only
-        case 14: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 84>>(g, s);  // DIAG: LDS-DMA + barriers only, no L2 misses
-        case 15: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 64>>(g, s);  // DIAG: whole kernel, no L2 misses
+        case 4: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 3>>(g, sw, s);    // balanced + static s_setprio for the late group
+        case 5: return launch_cfg8<EPI, Gemm8<320, 128, 4, 2, SW, 0>>(g, sw, s);
+        case 6: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 0>>(g, sw, s);    // the first read schedule (rounds 3-4 production)
+        case 7: return launch_cfg8<EPI, Gemm8<256, 256, 2, 4, SW, 0>>(g, sw, s);
+        case 8: return launch_cfg8<EPI, Gemm8<160, 256, 2, 4, SW, 0>>(g, sw, s);
+        case 9: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 4>>(g, sw, s);    // DIAG: no MFMA
+        case 10: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 8>>(g, sw, s);   // DIAG: no LDS-DMA
+        case 11: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 16>>(g, sw, s);  // DIAG: no ds_reads
+        case 12: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 24>>(g, sw, s);  // DIAG: MFMAs + barriers only
+        case 13: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 20>>(g, sw, s);  // DIAG: LDS-DMA + barriers only
+        case 14: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 84>>(g, sw, s);  // DIAG: LDS-DMA + barriers only, no L2 misses
+        case 15: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 64>>(g, sw, s);  // DIAG: whole kernel, no L2 misses
 #endif
     }
     return mm_fail("gemm8: unknown configuration %d", cfg);
@@ -497,16 +482,13 @@ bool gemm8_supports(const GemmArgs& g) {
            g.ldc % 8 == 0 && (g.resid == nullptr || g.ldr % 8 == 0) && ((uintptr_t)g.C & 15) == 0 && ((uintptr_t)g.resid & 15) == 0;
 }
 
-void gemm8_set_short_tiles(int on) { g_short_tiles = on != 0 ? 1 : 0; }
-void gemm8_set_tile_order(int code) { g_tile_order = code < 0 ? -1 : code; }
-
-int launch_gemm8(int epi, int cfg, const GemmArgs& g, hipStream_t s) {
+int launch_gemm8(int epi, int cfg, const GemmArgs& g, const Switches& sw, hipStream_t s) {
     if (!gemm8_supports(g)) return mm_fail("gemm8: unsupported shape M=%d N=%d K=%d", g.M, g.N, g.K);
     switch (epi) {
-        case EPI_STORE: return launch_epi8<EPI_STORE>(cfg, g, s);
-        case EPI_RESID: return launch_epi8<EPI_RESID>(cfg, g, s);
-        case EPI_SWIGLU: return launch_epi8<EPI_SWIGLU>(cfg, g, s);
-        case EPI_QKV: return launch_epi8<EPI_QKV>(cfg, g, s);
+        case EPI_STORE: return launch_epi8<EPI_STORE>(cfg, g, sw, s);
+        case EPI_RESID: return launch_epi8<EPI_RESID>(cfg, g, sw, s);
+        case EPI_SWIGLU: return launch_epi8<EPI_SWIGLU>(cfg, g, sw, s);
+        case EPI_QKV: return launch_epi8<EPI_QKV>(cfg, g, sw, s);
     }
     return mm_fail("gemm8: bad epilogue %d", epi);
 }

@@ -460,17 +460,7 @@ MM_DEVICE void gemm_publish(const GemmArgs& g, int wave) {
 // gemm8.hip: the 8-phase kernel.  cfg = one of the GEMM8_* configurations; returns nonzero on a launch error.
 enum Gemm8Cfg { GEMM8_320x256 = 0, GEMM8_256x256 = 1, GEMM8_160x256 = 2, GEMM8_320x128 = 3, GEMM8_NCFG = 4 };
 bool gemm8_supports(const GemmArgs& g);  // shape contract of the 8-phase kernel (K % 128 == 0, K >= 256, M, N % 8 == 0, ...)
-int launch_gemm8(int epi, int cfg, const GemmArgs& g, hipStream_t s);
-// Measurement hook (tools/gemm_sweep.py, tests): force one configuration for every following launch of this process.
-//   -1: automatic (default);  0..3: GEMM8_* configuration;  1000 + BM: the 16-wave kernel with that row-tile height.
-void gemm_force_config(int code);
+int launch_gemm8(int epi, int cfg, const GemmArgs& g, const Switches& sw, hipStream_t s);  // sw: short row tiles, tile order
 int gemm_plan_code(int M, int N, int K);  // the planner's pick for a plain product: 0..3 or 1000 + BM; -1: unsupported shape
-// short row tiles of the 320-row configurations (gemm8.hip) on / off; on by default
-void gemm8_set_short_tiles(int on);
-// tile order of the 8-phase kernel: 0 / -1 = default (bands of 1024 columns, all row tiles per group); GM * 100 + GN = groups of
-// GM row tiles x GN column tiles (sweeps: tools/gemm_sweep.py --order)
-void gemm8_set_tile_order(int code);
-// SiLU table of the SwiGLU epilogue (8-phase kernel) on / off; on by default
-void gemm_set_silu_lut(int on);
 // allocate + fill the per-device constants of the GEMM launchers now (zero rows, SiLU table) instead of at the first launch
 int gemm_prepare_device();

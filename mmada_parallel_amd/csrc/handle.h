@@ -74,11 +74,21 @@ struct mmada_handle {
     bool xn_is_layer0 = false;  // mmada_embed already wrote xn = RMSNorm(x) * blocks[0].attn_norm (fused, K1)
 };
 
+// api.hip: one block's launches (the one-rank forward: m0 = 0, every row; the tensor-parallel forward: one row chunk each).  The
+// GemmArgs of block `layer`'s projections on stream rows [m0, m0 + rows): xn -> q / k / vT + RoPE (a dLLM-cache step writes keys /
+// values into the slot), xn -> hbuf (SiLU·mul), att -> y and hbuf -> y (the caller adds its residual or its own target)
+GemmArgs qkv_args(const mmada_handle* h, int layer, int m0, int rows);
+GemmArgs gate_up_args(const mmada_handle* h, int layer, int m0, int rows);
+GemmArgs attn_out_args(const mmada_handle* h, int layer, int m0, int rows);
+GemmArgs down_args(const mmada_handle* h, int layer, int m0, int rows);
+// the block's attention over this rank's heads, timed as kernel class 1: a cache step's queries against the slot, the row window
+// [wbeg, wbeg + W) of each sequence (W > 0: the one-rank forward's last block), or every row
+int block_attention(mmada_handle* h, int layer, hipStream_t s, int wbeg = 0, int W = 0);
+
 // tp_comm.hip
 int tp_forward_body(mmada_handle* h, hipStream_t s);              // all blocks of a tensor-parallel forward, after mmada_embed
 int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s);  // residual stream rows of every owner -> [M, d]
 void tp_comm_free(mmada_handle* h);
-void tp_allow_single_rank(int on);   // test switch: mmada_comm_create accepts tp_size == 1
 bool tp_comm_connected(const mmada_handle* h);   // a transport (or the no-exchange diagnostic) is active on this handle
 int tp_head_gather(mmada_handle* h, const int32_t* rows, int R, hipStream_t s);  // xg[r] = xn[row r] (xn already = ln_f(x))
 // out[r] = src[b * Lp + l] for rows[r] = b * L + l: the plain row gather behind tp_head_gather, on any [B * Lp, d] buffer

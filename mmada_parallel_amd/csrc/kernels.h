@@ -49,6 +49,23 @@ struct GemmArgs {
 
 int launch_gemm(int epi, const GemmArgs& g, hipStream_t s);
 
+// A plain C[M, ldc] = A[M, K] · W[N, K]^T on K-contiguous operands (lda = ldw = K), epilogue fields left zero.
+static inline GemmArgs gemm_bt_args(const bf16_t* A, const bf16_t* W, bf16_t* C, int M, int N, int K, int ldc) {
+    GemmArgs g{};
+    g.A = A; g.W = W; g.C = C;
+    g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = ldc;
+    return g;
+}
+
+// The measurement / test switches of mmada_set_option (include/mmada_mi355x.h: what each value means), resolved at one point in
+// time: a switch never set takes the environment's default (MMADA_GEMM_CFG, MMADA_GEMM_SILU_LUT, MMADA_GEMM_SHORT_TILES,
+// MMADA_GEMM_TILE_ORDER, MMADA_ATTN_FORM: parsed once per process).  A launch takes one snapshot and decides everything from it.
+struct Switches {
+    int gemm_config, gemm_silu_lut, gemm_short_tiles, gemm_tile_order, attention_form, probe_variant, tp_allow_single_rank;
+};
+Switches switches();
+
 // elementwise.hip
 // norm_w != null: also xn = RMSNorm(x) * norm_w (the first norm of the forward, fused: SURVEY §2.3 K1)
 int launch_embed(const int64_t* ids, const bf16_t* wte, bf16_t* x, int B, int L, int Lp, int d, int vocab, hipStream_t s,
@@ -82,7 +99,6 @@ int launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* vT, bf16_t*
                      int Lq_alloc = 0);
 
 int attention_chunks(int pairs, int groups, int keys);  // workgroups per (batch, head) pair (the launch plan; host arithmetic)
-void attention_force_form(int form);  // 0: every wave in the plain order, 1: late waves (default); tests compare the two
 
 // sampler.hip
 struct TextStat { float lmax; int32_t arg; double sum; };  // one rank's record of a text row (vocabulary-parallel head)
@@ -99,6 +115,5 @@ int launch_image_commit(int64_t* ids, int B, int L, const int32_t* pos_map, int 
                         int mask_id, int text_vocab, int codebook, int mvar, hipStream_t s);
 
 // probe.hip: MFMA-only diagnostic (attainable roof at the sustained clock on random data)
-void mfma_probe_set_variant(int v);
 int launch_f2bf_probe(const float* in, bf16_t* out, long long n, hipStream_t s);
 int launch_mfma_probe(const bf16_t* data, float* sink, int iters, int launches, hipStream_t s, double* tflops_out, double* ms_out);

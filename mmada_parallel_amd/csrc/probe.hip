@@ -128,12 +128,9 @@ __global__ __launch_bounds__(4 * 64, 2) void mfma_probe16w4_kernel(const bf16_t*
 
 // data: >= 64 * 8 * 16 * 64 * 16 bytes (8 MiB) of bf16 values the caller filled (random: never zeros — see above).
 // Runs `launches` back-to-back launches of `iters` iterations on `stream` and returns the achieved dense TFLOP/s.
-static std::atomic<int> g_probe_variant{0};
-void mfma_probe_set_variant(int v) { g_probe_variant = v & 3; }
-
 int launch_mfma_probe(const bf16_t* data, float* sink, int iters, int launches, hipStream_t s, double* tflops_out, double* ms_out) {
     typedef void (*probe_fn)(const bf16_t*, int, float*);
-    const int v = g_probe_variant;
+    const int v = switches().probe_variant & 3;   // switch "probe_variant"
     const probe_fn fn = v == 0 ? (probe_fn)mfma_probe_kernel : v == 1 ? (probe_fn)mfma_probe32_kernel<8>
                       : v == 2 ? (probe_fn)mfma_probe16w4_kernel : (probe_fn)mfma_probe32_kernel<4>;
     const int waves = (v & 2) ? 4 : PROBE_WAVES;

@@ -43,9 +43,6 @@
 
 #include "handle.h"
 
-std::atomic<int> g_allow_single_rank{0};   // mmada_set_option("tp_allow_single_rank", 1): test switch, see mmada_comm_create
-void tp_allow_single_rank(int on) { g_allow_single_rank = on != 0; }
-
 namespace {
 
 constexpr int TP_MAX = 8;
@@ -505,7 +502,6 @@ static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
     Slice sl[2];
     for (int k = 0; k < nch; ++k) sl[k] = chunk_slice(M, tp, c->rank, nch, k);
     const double rows_real = (double)h->B * h->L / M;  // fraction of stream rows that are not padding (FLOP accounting)
-    const CacheSlot* cc = h->cc;
     // first RMSNorm of the forward: the embeddings are replicated, no exchange needed
     if (h->xn_is_layer0) h->xn_is_layer0 = false;  // fused into the embedding kernel
     else if (launch_rmsnorm(h->x, h->layers[0].attn_norm, h->xn, M, d, h->cfg.rms_eps, s)) return 1;
@@ -527,36 +523,20 @@ static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
     };
     for (int layer = 0; layer < nl; ++layer) {
         const LayerWeights& lw = h->layers[layer];
-        // ---- q/k/v (column-parallel: this rank's heads), RoPE in the epilogue ----
+        // ---- q/k/v (column-parallel: this rank's heads), RoPE in the epilogue; a dLLM cache step writes this rank's heads of the
+        // block's keys / values into the slot ----
         for (int k = 0; k < nch; ++k) {
             if (need_xn(k)) return 1;
-            GemmArgs g{};
-            g.A = h->xn + (size_t)sl[k].m0 * d; g.W = lw.wqkv; g.C = nullptr;
-            g.M = sl[k].m1 - sl[k].m0; g.N = (h->hq_l + 2 * h->hkv_l) * 128; g.K = d;
-            g.lda = d; g.ldw = d; g.ldc = 0; g.m_base = sl[k].m0;
-            g.q = h->q; g.k = h->k; g.vT = h->vT; g.rope_cos = h->rope_cos; g.rope_sin = h->rope_sin;
-            g.Lp = h->Lp; g.Lkv = h->Lkv; g.Hq = h->hq_l; g.Hkv = h->hkv_l;
-            if (cc) {   // dLLM cache step (mmada_forward_cached): this rank's heads of the block's keys / values live in the slot
-                g.k = cc->K(layer); g.vT = cc->vT(layer); g.Lkv = cc->Lkv;
-                g.pos_map = h->cc_pos; g.Lq = h->Lkv; g.q_pos_shift = h->cc_qshift;
-            }
+            const GemmArgs g = qkv_args(h, layer, sl[k].m0, sl[k].m1 - sl[k].m0);
             ProfScope p(h, layer, 0, 2.0 * g.M * rows_real * g.N * g.K, s);
             if (launch_gemm(EPI_QKV, g, s)) return 1;
         }
-        {   // ---- attention over this rank's heads: the one join point (every key of a sequence) ----
-            ProfScope p(h, layer, 1, 4.0 * h->hq_l * (double)h->B * h->L * (cc ? cc->L : h->L) * 128.0, s);
-            if (cc) {   // compact (or all) queries of this call against the slot's keys / values of the whole sequence
-                if (launch_attention(h->q, cc->K(layer), cc->vT(layer), h->att, h->B, h->hq_l, h->hkv_l, cc->L, h->Lp, cc->Lkv,
-                                     h->Lp, h->hq_l * 128, s, 0, h->Lkv)) return 1;
-            } else if (launch_attention(h->q, h->k, h->vT, h->att, h->B, h->hq_l, h->hkv_l, h->L, h->Lp, h->Lkv, h->Lp,
-                                        h->hq_l * 128, s)) return 1;
-        }
+        // ---- attention over this rank's heads: the one join point (every key of a sequence) ----
+        if (block_attention(h, layer, s)) return 1;
         // ---- attn_out (row-parallel) chunk by chunk; chunk k's exchange runs under chunk k+1's GEMM ----
         for (int k = 0; k < nch; ++k) {
-            GemmArgs o{};
-            o.A = h->att + (size_t)sl[k].m0 * h->hq_l * 128; o.W = lw.wo; o.C = c->part + (size_t)sl[k].m0 * d;
-            o.M = sl[k].m1 - sl[k].m0; o.N = d; o.K = h->hq_l * 128;
-            o.lda = o.K; o.ldw = o.K; o.ldc = d; o.publish = c->mode == 1 || c->mode == 4;
+            GemmArgs o = attn_out_args(h, layer, sl[k].m0, sl[k].m1 - sl[k].m0);
+            o.C = c->part + (size_t)sl[k].m0 * d; o.publish = c->mode == 1 || c->mode == 4;
             {
                 ProfScope p(h, layer, 2, 2.0 * o.M * rows_real * o.N * o.K, s);
                 if (launch_gemm(EPI_STORE, o, s)) return 1;
@@ -566,19 +546,14 @@ static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
         // ---- gate/up (column-parallel) + SiLU*mul, then down (row-parallel) ----
         for (int k = 0; k < nch; ++k) {
             if (need_xn(k)) return 1;
-            GemmArgs g{};
-            g.A = h->xn + (size_t)sl[k].m0 * d; g.W = lw.wgu; g.C = h->hbuf + (size_t)sl[k].m0 * h->f_l;
-            g.M = sl[k].m1 - sl[k].m0; g.N = 2 * h->f_l; g.K = d;
-            g.lda = d; g.ldw = d; g.ldc = h->f_l;
+            const GemmArgs g = gate_up_args(h, layer, sl[k].m0, sl[k].m1 - sl[k].m0);
             ProfScope p(h, layer, 3, 2.0 * g.M * rows_real * g.N * g.K, s);
             if (launch_gemm(EPI_SWIGLU, g, s)) return 1;
         }
         const bf16_t* next_w = layer + 1 < nl ? h->layers[layer + 1].attn_norm : h->ln_f;
         for (int k = 0; k < nch; ++k) {
-            GemmArgs o{};
-            o.A = h->hbuf + (size_t)sl[k].m0 * h->f_l; o.W = lw.wdown; o.C = c->part + (size_t)sl[k].m0 * d;
-            o.M = sl[k].m1 - sl[k].m0; o.N = d; o.K = h->f_l;
-            o.lda = h->f_l; o.ldw = h->f_l; o.ldc = d; o.publish = c->mode == 1 || c->mode == 4;
+            GemmArgs o = down_args(h, layer, sl[k].m0, sl[k].m1 - sl[k].m0);
+            o.C = c->part + (size_t)sl[k].m0 * d; o.publish = c->mode == 1 || c->mode == 4;
             {
                 ProfScope p(h, layer, 4, 2.0 * o.M * rows_real * o.N * o.K, s);
                 if (launch_gemm(EPI_STORE, o, s)) return 1;
@@ -653,7 +628,7 @@ int mmada_comm_create(mmada_handle* h, int max_rows, void* export_out) {
     // tp_size == 1 behind mmada_set_option("tp_allow_single_rank", 1): a one-rank group runs EVERY line of the exchange (RCCL
     // reduce-scatter / all-gather of one rank are copies, the pull transport has no peer to wait for) and must reproduce the
     // plain forward bit for bit — the test that executes the RCCL transport without a second GPU (tests/test_gpu_tp.py)
-    if ((h->cfg.tp_size < 2 && !(h->cfg.tp_size == 1 && g_allow_single_rank)) || h->cfg.tp_size > TP_MAX)
+    if ((h->cfg.tp_size < 2 && !(h->cfg.tp_size == 1 && switches().tp_allow_single_rank)) || h->cfg.tp_size > TP_MAX)
         return mm_fail("mmada_comm_create: tp_size must be 2..%d", TP_MAX);
     if (h->tp) tp_comm_free(h);
     TpComm* c = new TpComm();
@@ -930,10 +905,7 @@ int mmada_text_select_tp(mmada_handle* h, const int32_t* rows, int B, int T, int
     }
     if (tp_head_gather(h, rows, R, s)) return 1;
     if (v1 > v0) {
-        GemmArgs g{};
-        g.A = h->xg; g.W = h->lm_head + (size_t)v0 * d; g.C = c->head_buf;
-        g.M = R; g.N = v1 - v0; g.K = d; g.lda = d; g.ldw = d; g.ldc = w;
-        if (launch_gemm(EPI_STORE, g, s)) return 1;
+        if (launch_gemm(EPI_STORE, gemm_bt_args(h->xg, h->lm_head + (size_t)v0 * d, c->head_buf, R, v1 - v0, d, w), s)) return 1;
     }
     if (launch_text_stats_partial(c->head_buf, B, T, v1 - v0, w, v0, ids, L, text_start, h->cfg.mask_token_id, c->stats_pub, s))
         return 1;

@@ -43,7 +43,7 @@ def handle():
 
 # ---------------------------------------------------------------------------------------------------------------- GEMM
 def test_gemm_every_row_tile_height():
-    """Each BM configuration of the production kernel (forced through MMADA_GEMM_BM in a fresh process)."""
+    """Each BM configuration of the production kernel (forced through MMADA_GEMM_CFG=1000+BM in a fresh process)."""
     import subprocess
     import sys
 
@@ -59,7 +59,7 @@ def test_gemm_every_row_tile_height():
         "    assert (err <= 2.0 ** -8 * ref.abs() + 1e-3 * ref.abs().max()).all(), err.max().item()\n"
         "print('ok')\n" % ROOT)
     for bm in (128, 160, 192, 224, 256):
-        env = dict(os.environ, MMADA_GEMM_BM=str(bm))
+        env = dict(os.environ, MMADA_GEMM_CFG=str(1000 + bm))
         out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
         assert out.returncode == 0 and "ok" in out.stdout, f"BM={bm}: {out.stderr[-800:]}"
 

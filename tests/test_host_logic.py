@@ -356,6 +356,56 @@ def test_gemm_planner_picks_the_measured_best_on_the_committed_sweep():
     assert lib.mmada_gemm_plan(2440, 4096, 100) == -1   # K is not a multiple of the K-tile
 
 
+
+def test_gemm_config_switch_through_the_planner():
+    """mmada_set_option("gemm_config") as a launch sees it (mmada_gemm_plan reads the same switch snapshot; host arithmetic, no GPU):
+    a pinned configuration holds where the shape allows it, a pinned 8-phase one on a shape the 8-phase kernel cannot run (K = 192)
+    gets the automatic pick, -1 is automatic again, and an unknown option name is an error.  The library's switches are shared by
+    the whole process, so the automatic setting is restored whatever happens."""
+    from mmada_parallel_amd import abi
+
+    lib = abi.lib()
+    try:
+        abi.check(lib.mmada_set_option(b"gemm_config", -1), "set_option")
+        auto, auto_k192 = lib.mmada_gemm_plan(2440, 4096, 4096), lib.mmada_gemm_plan(2440, 4096, 192)
+        assert auto != 1 and auto_k192 >= 1000
+        abi.check(lib.mmada_set_option(b"gemm_config", 1), "set_option")
+        assert lib.mmada_gemm_plan(2440, 4096, 4096) == 1
+        assert lib.mmada_gemm_plan(2440, 4096, 192) == auto_k192
+        abi.check(lib.mmada_set_option(b"gemm_config", 1160), "set_option")
+        assert lib.mmada_gemm_plan(2440, 4096, 4096) == 1160
+        abi.check(lib.mmada_set_option(b"gemm_config", -1), "set_option")
+        assert lib.mmada_gemm_plan(2440, 4096, 4096) == auto
+        assert lib.mmada_set_option(b"no_such_option", 1) != 0
+        assert b"unknown option" in lib.mmada_last_error()
+    finally:
+        lib.mmada_set_option(b"gemm_config", -1)
+
+
+def test_gemm_config_environment_default():
+    """MMADA_GEMM_CFG is the process default of "gemm_config" (read on first use); mmada_set_option("gemm_config", -1) is the
+    automatic pick even while it is set.  A fresh process, so that the environment is read under this test's value."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from mmada_parallel_amd import abi\n"
+            "lib = abi.lib()\n"
+            "pinned = lib.mmada_gemm_plan(2440, 4096, 4096)\n"
+            "lib.mmada_set_option(b'gemm_config', -1)\n"
+            "print(pinned, lib.mmada_gemm_plan(2440, 4096, 4096))\n" % root)
+    from mmada_parallel_amd import abi
+
+    lib = abi.lib()
+    abi.check(lib.mmada_set_option(b"gemm_config", -1), "set_option")
+    auto = lib.mmada_gemm_plan(2440, 4096, 4096)
+    for cfg in (1, 1160):
+        env = dict(os.environ, MMADA_GEMM_CFG=str(cfg))
+        out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-800:]
+        assert out.stdout.split() == [str(cfg), str(auto)], out.stdout
+
 def test_attention_plan():
     """The launch plan of the attention kernel (csrc/attention.hip: attention_chunks through mmada_attention_plan, host arithmetic):
     a (batch, head) pair's 16-row query groups are cut into the fewest workgroups with the least estimated time
