@@ -110,6 +110,23 @@ int mmada_forward_body(mmada_handle* h, const int64_t* ids /*device [B,L]*/, int
 int mmada_head_rows(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end,
                     void* logits_out, void* stream);
 
+/* Scoring: the forward value of F.cross_entropy(logits, labels, reduction='none') of LLaDAForMultiModalGeneration.forward(labels=...)
+ * (model/modeling_xllmx_dimoo.py:83-91) WITHOUT materialising the logits.  After mmada_forward_body: for each of the R rows (row
+ * index b*L + l, as in mmada_head_rows) the log-probability of targets[i] under soft-max over logit columns [col_begin, col_end)
+ * of the LM head.  The head GEMM reduces every 256-column tile to one 16-byte record per row in its epilogue (max, first arg-max,
+ * sum of exponentials of the bf16-rounded logits); a second kernel joins the records of a row in a fixed order.
+ * targets: device int64 [R], column index inside the WHOLE vocabulary; < 0 = ignore (logprob_out[i] = 0).  A target >= 0 outside
+ * [col_begin, col_end) is not an error (the call only launches, it never reads back): that row's logprob_out is -inf.
+ * logprob_out: device fp32 [R] = x_target - lse.  lse_out (fp32), argmax_out (int32, column in the whole vocabulary, first
+ * maximum) and max_out (fp32): device [R] or NULL.
+ * Honours the row window of mmada_set_consumed_rows exactly as mmada_head_rows does.  Record buffer: owned by the handle,
+ * (re)allocated when a call needs more than it holds — ceil(N / 256) * ceil8(R) * 16 + ceil8(R) * 4 bytes, 1/32 of the bf16 logits
+ * the call stands for (mmada_score_buffer_bytes reports what is held); a call that fits is capturable in a hipGraph.
+ * Tensor-parallel handles: not yet (returns an error). */
+int mmada_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
+                        float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out, void* stream);
+size_t mmada_score_buffer_bytes(const mmada_handle* h);
+
 /* Declare which residual-stream rows the caller will read after the forwards that follow: only l in
  * [row_begin, row_end) of every sequence (e.g. the image + text span of generate_ti2ti; the prompt and the input image
  * are never decoded).  The LAST block then runs attention queries, attn_out and the MLP on those rows only — every

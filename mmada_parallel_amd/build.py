@@ -88,6 +88,7 @@ def verify_isa() -> None:
         asm8, asma = ex.map(isa_check.device_asm, ["gemm8.hip", "attention.hip"])
     errors = []
     errors += isa_check.check_gemm8(asm8)[1]          # counted waits, M0 contract, no spill, 16-byte epilogue stores
+    errors += isa_check.check_gemm8_rowstat(asm8)[1]  # the scoring head's epilogue: the same, one v_exp_f32 per logit, no logit stored
     errors += isa_check.check_attention(asma)[1]      # M0 contract, counted LDS waits, no spill
     if errors:
         raise RuntimeError("compiled-code checks failed (tools/isa_check.py):\n" + "\n".join(errors))

@@ -88,6 +88,7 @@ int mmada_destroy(mmada_handle* h) {
     }
     (void)hipFree(h->rope_cos);
     (void)hipFree(h->rope_sin);
+    (void)hipFree(h->score_buf);
     delete h;
     return 0;
 }
@@ -557,6 +558,40 @@ int mmada_head_rows(mmada_handle* h, const int32_t* rows, int R, int col_begin, 
     const int N = col_end - col_begin;
     return launch_gemm(EPI_STORE, gemm_bt_args(h->xg, h->lm_head + (size_t)col_begin * d, (bf16_t*)logits_out, R, N, d, N), s);
 }
+
+int mmada_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
+                        float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out, void* stream) {
+    if (!h || h->M == 0) return mm_fail("mmada_head_logprobs: no forward resident");
+    if (!rows || !targets || !logprob_out) return mm_fail("mmada_head_logprobs: null argument");
+    if (h->xn_is_final || h->cfg.tp_size != 1 || tp_comm_connected(h))
+        return mm_fail("mmada_head_logprobs: tensor-parallel handles are not supported yet (a vocabulary-parallel score exchanges "
+                       "the same records as mmada_text_select_tp)");
+    if (R <= 0) return 0;
+    if (R > h->B * h->L) return mm_fail("mmada_head_logprobs: R=%d exceeds B*L=%d", R, h->B * h->L);
+    if (col_begin < 0 || col_end > h->cfg.vocab || col_begin >= col_end) return mm_fail("mmada_head_logprobs: bad column range");
+    hipStream_t s = (hipStream_t)stream;
+    const int d = h->cfg.d_model, N = col_end - col_begin;
+    const size_t need = head_rowstat_bytes(R, N);
+    if (need > h->score_bytes) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+            (void)hipGetLastError();
+            return mm_fail("mmada_head_logprobs: the record buffer must grow (%zu bytes): run the call once outside the capture", need);
+        }
+        MM_CHECK_HIP(hipStreamSynchronize(s));   // an earlier call on this stream may still read the old buffer
+        (void)hipFree(h->score_buf);
+        h->score_buf = nullptr; h->score_bytes = 0;
+        MM_CHECK_HIP(hipMalloc(&h->score_buf, need));
+        h->score_bytes = need;
+    }
+    // the same gather as mmada_head_rows (compact stream of a windowed forward; rows outside the window are an error there)
+    if (launch_rmsnorm_gather(h->x, h->ln_f, h->xg, rows, R, h->L, h->cur_W ? h->cur_W : h->Lp, d, h->cfg.rms_eps, s, h->cur_beg,
+                              h->B * h->L)) return 1;
+    return launch_head_rowstat(h->xg, h->lm_head + (size_t)col_begin * d, R, N, d, col_begin, targets, h->score_buf, logprob_out,
+                               lse_out, argmax_out, max_out, s);
+}
+
+size_t mmada_score_buffer_bytes(const mmada_handle* h) { return h ? h->score_bytes : 0; }
 
 int mmada_set_consumed_rows(mmada_handle* h, int row_begin, int row_end) {
     if (!h) return mm_fail("mmada_set_consumed_rows: null handle");

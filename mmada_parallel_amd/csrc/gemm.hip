@@ -150,6 +150,10 @@ __global__ __launch_bounds__(NTHREADS, 4) void gemm_bt_kernel(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < T::FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     mainloop<BM, WM, WN>(g, smem, mt * BM, nt * BN, 0, g.K / BK, acc, wave, lane);
+    if constexpr (EPI == EPI_ROWSTAT) {
+        __syncthreads();   // every wave has read its last K-tile: the stage buffers are free for the row records
+        gemm_epilogue<EPI, T::TM, T::TN, WN>(g, mt * BM, nt * BN, acc, wave, lane, g.M, (int)(uintptr_t)(lptr_t)smem, BM);
+    } else
     gemm_epilogue<EPI, T::TM, T::TN, WN>(g, mt * BM, nt * BN, acc, wave, lane, g.M);
     gemm_publish(g, wave);
 }
@@ -224,7 +228,22 @@ Plan plan(const GemmArgs& g, int force) {
 
 template <int EPI>
 int launch_t(const GemmArgs& g, const Switches& sw, hipStream_t s) {
-    const Plan p = plan(g, sw.gemm_config);
+    Plan p = plan(g, sw.gemm_config);
+    if constexpr (EPI == EPI_ROWSTAT) {
+        // the row-statistics epilogue exists for 256-column tiles of four 64-column waves: a pinned configuration without one
+        // (320 x 128; the 16-wave kernel's 2 x 8 wave grids) gets the automatic pick, and that the next taller 4 x 4 grid
+        if (p.p8 && p.code == GEMM8_320x128) p = plan(g, -1);
+        if (p.p8 && p.code == GEMM8_320x128) p = {true, GEMM8_320x256};
+        if (!p.p8 && p.code == 160) p.code = 192;
+        if (!p.p8 && p.code == 224) p.code = 256;
+        if (p.p8) return launch_gemm8(EPI, p.code, g, sw, s);
+        switch (p.code) {
+            case 320: return launch_cfg<EPI, 320, 4, 4>(g, s);
+            case 256: return launch_cfg<EPI, 256, 4, 4>(g, s);
+            case 192: return launch_cfg<EPI, 192, 4, 4>(g, s);
+            default: return launch_cfg<EPI, 128, 4, 4>(g, s);
+        }
+    } else {
     if (p.p8) return launch_gemm8(EPI, p.code, g, sw, s);
     switch (p.code) {
         case 320: return launch_cfg<EPI, 320, 4, 4>(g, s);
@@ -233,6 +252,7 @@ int launch_t(const GemmArgs& g, const Switches& sw, hipStream_t s) {
         case 128: return launch_cfg<EPI, 128, 4, 4>(g, s);
         case 160: return launch_cfg<EPI, 160, 2, 8>(g, s);
         default: return launch_cfg<EPI, 224, 2, 8>(g, s);
+    }
     }
 }
 
@@ -327,6 +347,82 @@ int launch_gemm(int epi, const GemmArgs& g_in, hipStream_t s) {
             if (g.N != (g.Hq + 2 * g.Hkv) * 128) return mm_fail("gemm/qkv: N mismatch");
             if (g.Lp % 8 || g.m_base % 8) return mm_fail("gemm/qkv: Lp and m_base must be multiples of 8");
             return launch_t<EPI_QKV>(g, sw, s);
+        case EPI_ROWSTAT:
+            if (const RowStatArgs rs = rowstat_args(g); !rs.part || !rs.tx || !rs.target || rs.rows <= 0 || rs.rows > g.M || rs.ld < rs.rows)
+                return mm_fail("gemm/rowstat: record buffers missing");
+            return launch_t<EPI_ROWSTAT>(g, sw, s);
     }
     return mm_fail("gemm: bad epilogue %d", epi);
+}
+
+// ---- the scoring head: D = A · lm_head[col0 : col0 + N]^T reduced to row statistics (gemm_epilogue.h: EPI_ROWSTAT) ----------
+// Record buffer: [ceil(N / 256)][ceil8(R)] records of 16 bytes, then ceil8(R) target logits (fp32): 1/32 of the bytes of the
+// bf16 logits it stands for, plus 4 bytes per row.
+static inline int rowstat_tiles(int N) { return (N + BN - 1) / BN; }
+size_t head_rowstat_bytes(int R, int N) {
+    const size_t rp = (size_t)((R + 7) / 8 * 8);
+    return rp * rowstat_tiles(N) * sizeof(float4) + rp * sizeof(float);
+}
+
+// Joins the column-tile records of a row in a FIXED order (so that neither the tile order of the GEMM nor its configuration
+// shows in the result): 16 rows x 16 tile groups per workgroup; group j folds tiles j, j + 16, ... in ascending order (online
+// soft-max: rescale by exp(m_tile - m_row)), then thread (row, 0) folds the 16 groups in ascending order.
+constexpr int RS_ROWS = 16, RS_GROUPS = 16;
+__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void rowstat_combine_kernel(const float4* part, const float* tx, const int64_t* targets,
+                                                                               int R, int ld, int ntn, float* logprob, float* lse_out,
+                                                                               int32_t* argmax_out, float* max_out) {
+    __shared__ float sm[RS_GROUPS][RS_ROWS], ss[RS_GROUPS][RS_ROWS];
+    __shared__ int sa[RS_GROUPS][RS_ROWS];
+    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
+    const int row = blockIdx.x * RS_ROWS + rl;
+    float m = -__builtin_inff(), sum = 0.f;
+    int arg = 0x7fffffff;
+    if (row < R)
+        for (int t = j; t < ntn; t += RS_GROUPS) {
+            const float4 p = part[(size_t)t * ld + row];
+            const int a = __float_as_int(p.z);
+            if (p.x > m) {   // tiles ascend inside a group: an equal maximum further right does not replace
+                sum = sum * expf(m - p.x) + p.y;
+                m = p.x;
+                arg = a;
+            } else
+                sum += p.y * expf(p.x - m);
+        }
+    sm[j][rl] = m; ss[j][rl] = sum; sa[j][rl] = arg;
+    __syncthreads();
+    if (j != 0 || row >= R) return;
+    for (int q = 1; q < RS_GROUPS; ++q) {
+        const float mq = sm[q][rl], sq = ss[q][rl];
+        const int aq = sa[q][rl];
+        if (mq > m) {
+            sum = sum * expf(m - mq) + sq;
+            m = mq;
+            arg = aq;
+        } else if (mq > -__builtin_inff()) {
+            sum += sq * expf(mq - m);
+            if (mq == m && aq < arg) arg = aq;   // groups interleave the tiles: the leftmost column wins
+        }
+    }
+    const float lse = m + logf(sum);
+    const long long t = targets[row];
+    logprob[row] = t < 0 ? 0.f : tx[row] - lse;
+    if (lse_out) lse_out[row] = lse;
+    if (argmax_out) argmax_out[row] = arg;
+    if (max_out) max_out[row] = m;
+}
+
+int launch_head_rowstat(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, const int64_t* targets, void* part,
+                        float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s) {
+    if (R <= 0 || N <= 0) return 0;
+    const int rp = (R + 7) / 8 * 8, ntn = rowstat_tiles(N);
+    GemmArgs g = gemm_bt_args(A, W, nullptr, rp, N, K, 8);
+    const RowStatArgs rs{(float4*)part, (float*)((float4*)part + (size_t)rp * ntn), targets, R, rp, col0};
+    set_rowstat_args(g, rs);
+    // a target outside the column range leaves -inf behind (no lane holds it)
+    MM_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)rs.tx, 0xff800000u, rp, s));
+    if (launch_gemm(EPI_ROWSTAT, g, s)) return 1;
+    hipLaunchKernelGGL(rowstat_combine_kernel, dim3((R + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, rs.part, rs.tx,
+                       targets, R, rp, ntn, logprob, lse, argmax, vmax);
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
 }

@@ -445,6 +445,14 @@ int launch_cfg8(const GemmArgs& g, const Switches& sw, hipStream_t s) {
 template <int EPI>
 int launch_epi8(int cfg, const GemmArgs& g, const Switches& sw, hipStream_t s) {
     constexpr int SW = EPI == EPI_QKV ? 2 : 1;
+    if constexpr (EPI == EPI_ROWSTAT) {   // 256-column tiles only (gemm_epilogue.h: one record per row and 256 columns)
+        switch (cfg) {
+            case GEMM8_320x256: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 2>>(g, sw, s);
+            case GEMM8_256x256: return launch_cfg8<EPI, Gemm8<256, 256, 2, 4, SW, 2>>(g, sw, s);
+            case GEMM8_160x256: return launch_cfg8<EPI, Gemm8<160, 256, 2, 4, SW, 2>>(g, sw, s);
+        }
+        return mm_fail("gemm8: configuration %d has no row-statistics epilogue", cfg);
+    } else
     switch (cfg) {
         // the balanced read schedule (OPT 2) on every tile.  Rounds 3-4 kept the first schedule on 320 x 256 because its RESID /
         // QKV builds spilled inside the loop with the balanced one; with the tail K-tiles in a one-trip loop (run()) all four
@@ -489,6 +497,7 @@ int launch_gemm8(int epi, int cfg, const GemmArgs& g, const Switches& sw, hipStr
         case EPI_RESID: return launch_epi8<EPI_RESID>(cfg, g, sw, s);
         case EPI_SWIGLU: return launch_epi8<EPI_SWIGLU>(cfg, g, sw, s);
         case EPI_QKV: return launch_epi8<EPI_QKV>(cfg, g, sw, s);
+        case EPI_ROWSTAT: return launch_epi8<EPI_ROWSTAT>(cfg, g, sw, s);
     }
     return mm_fail("gemm8: bad epilogue %d", epi);
 }

@@ -72,11 +72,171 @@ MM_DEVICE void tile_coords_g(int t, int ntm, int ntn, int GM, int GN, int& mt, i
 template <int GN = 4>
 MM_DEVICE void tile_coords(int t, int ntm, int ntn, int& mt, int& nt) { tile_coords_g(t, ntm, ntn, 0, GN, mt, nt); }
 
+// ---- EPI_ROWSTAT: the scoring head (round 7).  Nothing of D is stored: a workgroup reduces its BM x 256 logits to one record per
+// row, {max, sum exp(x - max), first column of the max}, and hands the one logit at the row's target column out.  x is the
+// accumulator ROUNDED TO BF16 first — the logits nn.Linear would have written (the rounding point every other epilogue keeps).
+// Three steps, two workgroup barriers, through 15 KiB of the LDS the main loop has finished with (RowStatLds):
+//   1. every wave: max / first arg-max over its 64 columns of each of its rows — in registers over the lane's values, then
+//      across the lanes that share the row (__shfl_xor: lane ^ 16, ^ 32 in the transposed layout, ^ 1 ... ^ 8 in the other);
+//   2. with the TILE's max of the row (the 4 waves' maxima from LDS): sum of exp2((x - max) * log2 e), one v_exp_f32 per logit;
+//   3. thread r of the workgroup joins the 4 waves' records of tile row r and writes the record (one 16-byte store, 256 B per 16
+//      lanes).
+// The sum is evaluated in ONE fixed tree whatever kernel, tile height or operand order ran: groups of 4 consecutive columns
+// (e0 + e1) + (e2 + e3); the 4 fragments of a wave's 64 columns in order; the 4 column groups of a fragment (g0 + g1) + (g2 + g3);
+// the 4 waves (w0 + w1) + (w2 + w3).  fp32 addition commutes, so both layouts produce the same bits; max, arg-max and the target
+// logit are functions of the bf16 logits alone.
+struct RowStatLds {
+    static constexpr int ROWS = 320, WAVES = 4;   // tallest row tile, wave columns of a 256-column tile of 64-column waves
+    static constexpr int MAX = 0, ARG = ROWS * WAVES * 4, SUM = 2 * ROWS * WAVES * 4, BYTES = 3 * ROWS * WAVES * 4;
+};
+typedef __attribute__((address_space(3))) float* lds_f32_ptr;
+typedef __attribute__((address_space(3))) int* lds_i32_ptr;
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wint-to-pointer-cast"
+MM_DEVICE float lds_ldf(int byte_off) { return *(lds_f32_ptr)(uint32_t)byte_off; }
+MM_DEVICE void lds_stf(int byte_off, float v) { *(lds_f32_ptr)(uint32_t)byte_off = v; }
+MM_DEVICE int lds_ldi(int byte_off) { return *(lds_i32_ptr)(uint32_t)byte_off; }
+MM_DEVICE void lds_sti(int byte_off, int v) { *(lds_i32_ptr)(uint32_t)byte_off = v; }
+#pragma clang diagnostic pop
+
+MM_DEVICE void rowstat_take(float& m, int& a, float om, int oa) {   // torch's arg-max tie rule: the first index wins
+    if (om > m || (om == m && oa < a)) { m = om; a = oa; }
+}
+MM_DEVICE float rowstat_exp(float x, float m) {
+#pragma clang fp contract(off)
+    return __builtin_amdgcn_exp2f((x - m) * 1.44269504088896340736f);
+}
+// column (inside the launch) of row m's target, or -1: none in this launch
+MM_DEVICE int rowstat_target(const GemmArgs& g, const RowStatArgs& rs, int m) {
+    const long long t = rs.target[m] - (long long)rs.col0;
+    return t >= 0 && t < (long long)g.N ? (int)t : -1;
+}
+
+// TR: transposed accumulator layout (gemm_epilogue_t) or not (gemm_epilogue); lds: byte address of RowStatLds::BYTES free bytes
+template <bool TR, int TM, int TN, int WN>
+MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim, int lds,
+                                 int bm /* rows of the workgroup's tile, <= RowStatLds::ROWS */) {
+#pragma clang fp contract(off)
+    constexpr int FM = TM / 16, FN = TN / 16;
+    static_assert(TN == 64 && WN == RowStatLds::WAVES, "row statistics: 256-column tiles of four 64-column waves");
+    const int wm = wave / WN, wn = wave % WN;
+    const int l15 = lane & 15, lq = lane >> 4;
+    const int wcol0 = n0 + wn * TN;
+    const RowStatArgs rs = rowstat_args(g);
+    const int rows = min(m_lim, rs.rows);
+    const float NEG = -__builtin_inff();
+    // slots: the rows a lane takes part in.  TR: FM (row mi*16 + l15, 16 values: 4 fragments x 4 consecutive columns lq*4 + r);
+    // else FM * 4 (row mi*16 + lq*4 + r, 4 values: column l15 of 4 fragments)
+    constexpr int NS = TR ? FM : FM * 4;
+    const bool writer = TR ? lq == 0 : l15 == 0;
+    auto slot_row = [&](int sl) { return TR ? wm * TM + sl * 16 + l15 : wm * TM + (sl >> 2) * 16 + lq * 4 + (sl & 3); };
+    auto val = [&](int sl, int ni, int r) {   // bf16-rounded logit; columns beyond N never win and add nothing
+        const int n = wcol0 + ni * 16 + (TR ? lq * 4 + r : l15);
+        float a;
+        if constexpr (TR) a = acc[sl][ni][r];
+        else a = acc[sl >> 2][ni][sl & 3];
+        return n < g.N ? bfround(a) : NEG;
+    };
+    // ---- 1: wave maxima; the target logit ----
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) {
+        const int rt = slot_row(sl), m = m0 + rt;
+        const int tc = m < rows ? rowstat_target(g, rs, m) : -1;
+        const int c0 = wcol0 + (TR ? lq * 4 : l15);
+        float bm = NEG;
+        int ba = c0;
+#pragma unroll
+        for (int ni = 0; ni < FN; ++ni)
+#pragma unroll
+            for (int r = 0; r < (TR ? 4 : 1); ++r) {
+                const float x = val(sl, ni, r);
+                if (x > bm) { bm = x; ba = c0 + ni * 16 + r; }
+            }
+        const int d = tc - c0;   // this lane holds the target column if d = ni*16 + r
+        if (tc >= 0 && d >= 0 && d < TN && (d & 15) < (TR ? 4 : 1)) {
+            float x = NEG;
+#pragma unroll
+            for (int ni = 0; ni < FN; ++ni)
+#pragma unroll
+                for (int r = 0; r < (TR ? 4 : 1); ++r)
+                    if (d == ni * 16 + r) x = val(sl, ni, r);
+            rs.tx[m] = x;
+        }
+        if constexpr (TR) {
+            rowstat_take(bm, ba, __shfl_xor(bm, 16, 64), __shfl_xor(ba, 16, 64));
+            rowstat_take(bm, ba, __shfl_xor(bm, 32, 64), __shfl_xor(ba, 32, 64));
+        } else {
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) rowstat_take(bm, ba, __shfl_xor(bm, o, 64), __shfl_xor(ba, o, 64));
+        }
+        if (writer) {
+            lds_stf(lds + RowStatLds::MAX + (wn * RowStatLds::ROWS + rt) * 4, bm);
+            lds_sti(lds + RowStatLds::ARG + (wn * RowStatLds::ROWS + rt) * 4, ba);
+        }
+    }
+    __syncthreads();
+    // ---- 2: sums of exponentials against the tile's row max ----
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) {
+        const int rt = slot_row(sl);
+        float mt = lds_ldf(lds + RowStatLds::MAX + rt * 4);
+#pragma unroll
+        for (int w = 1; w < WN; ++w) mt = fmaxf(mt, lds_ldf(lds + RowStatLds::MAX + (w * RowStatLds::ROWS + rt) * 4));
+        float s = 0.f;
+#pragma unroll
+        for (int ni = 0; ni < FN; ++ni) {
+            float gsum;
+            if constexpr (TR) {
+                gsum = (rowstat_exp(val(sl, ni, 0), mt) + rowstat_exp(val(sl, ni, 1), mt)) +
+                       (rowstat_exp(val(sl, ni, 2), mt) + rowstat_exp(val(sl, ni, 3), mt));
+            } else {
+                gsum = rowstat_exp(val(sl, ni, 0), mt);
+                gsum += __shfl_xor(gsum, 1, 64);
+                gsum += __shfl_xor(gsum, 2, 64);
+            }
+            s = ni == 0 ? gsum : s + gsum;
+        }
+        if constexpr (TR) {
+            s += __shfl_xor(s, 16, 64);
+            s += __shfl_xor(s, 32, 64);
+        } else {
+            s += __shfl_xor(s, 4, 64);
+            s += __shfl_xor(s, 8, 64);
+        }
+        if (writer) lds_stf(lds + RowStatLds::SUM + (wn * RowStatLds::ROWS + rt) * 4, s);
+    }
+    __syncthreads();
+    // ---- 3: one record per tile row ----
+    const int rt = wave * 64 + lane, m = m0 + rt;
+    if (rt < bm && m < rows) {
+        float mw[WN], sw[WN];
+        int aw[WN];
+#pragma unroll
+        for (int w = 0; w < WN; ++w) {
+            mw[w] = lds_ldf(lds + RowStatLds::MAX + (w * RowStatLds::ROWS + rt) * 4);
+            aw[w] = lds_ldi(lds + RowStatLds::ARG + (w * RowStatLds::ROWS + rt) * 4);
+            sw[w] = lds_ldf(lds + RowStatLds::SUM + (w * RowStatLds::ROWS + rt) * 4);
+        }
+        float mt = mw[0];
+        int at = aw[0];
+#pragma unroll
+        for (int w = 1; w < WN; ++w)
+            if (mw[w] > mt) { mt = mw[w]; at = aw[w]; }   // wave columns ascend: a later equal maximum does not replace
+        const float st = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+        rs.part[(size_t)(n0 / (TN * WN)) * rs.ld + m] = float4{mt, st, __int_as_float(at + rs.col0), 0.f};
+    }
+}
+
 // m_lim: first row this tile does NOT write (g.M, or the end of a short row tile of gemm8.hip).
 // Wave grid WM x WN over the block tile, a wave owns TM x TN outputs = FM x FN fragments of 16 x 16:
 //     acc[mi][ni][r] = D[m][n],  m = m0 + wm*TM + mi*16 + (lane>>4)*4 + r,  n = n0 + wn*TN + ni*16 + (lane&15)
 template <int EPI, int TM, int TN, int WN>
-MM_DEVICE void gemm_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim) {
+MM_DEVICE void gemm_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim,
+                             int lds = 0, int bm = 0 /* EPI_ROWSTAT: free LDS (byte address), rows of the tile */) {
+    if constexpr (EPI == EPI_ROWSTAT) {
+        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<false, TM, TN, WN>(g, m0, n0, acc, wave, lane, m_lim, lds, bm);
+        return;
+    }
     constexpr int FM = TM / 16, FN = TN / 16;
     static_assert(TN % 32 == 0, "fused epilogues pair adjacent 16-column fragments");
     const int wm = wave / WN, wn = wave % WN;
@@ -237,6 +397,10 @@ MM_DEVICE int run8_col(int lq) { return (lq & 1) * 16 + (lq >> 1) * 8; }
 template <int EPI, int TM, int TN, int WN>
 MM_DEVICE void gemm_epilogue_t(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim,
                                 int lut_lds = -1 /* LDS byte address of the SiLU table, or -1 */) {
+    if constexpr (EPI == EPI_ROWSTAT) {   // the 8-phase kernel owns the LDS from address 0; its main loop is behind a barrier
+        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<true, TM, TN, WN>(g, m0, n0, acc, wave, lane, m_lim, 0, TM * (8 / WN));
+        return;
+    }
     constexpr int FM = TM / 16, FN = TN / 16;
     static_assert(TN % 32 == 0, "fused epilogues pair adjacent 16-column fragments");
     const int wm = wave / WN, wn = wave % WN;

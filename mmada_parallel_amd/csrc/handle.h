@@ -71,6 +71,9 @@ struct mmada_handle {
     // ln_f(x) for every row (the last reduce-scatter of a tensor-parallel forward applies ln_f on the owned rows)
     TpComm* tp = nullptr;
     bool xn_is_final = false;
+    // record buffer of mmada_head_logprobs (kernels.h: head_rowstat_bytes), grown at first use, freed with the handle
+    void* score_buf = nullptr;
+    size_t score_bytes = 0;
     bool xn_is_layer0 = false;  // mmada_embed already wrote xn = RMSNorm(x) * blocks[0].attn_norm (fused, K1)
 };
 
@@ -150,7 +153,7 @@ static Carve carve_for(const mmada_handle* h, int B, int L) {
     c.q = take((size_t)B * h->hq_l * c.Lkv * 128 * 2);
     c.k = take((size_t)B * h->hkv_l * c.Lkv * 128 * 2);
     c.vT = take((size_t)B * h->hkv_l * 128 * c.Lkv * 2);
-    c.xg = take((size_t)B * L * d * 2);
+    c.xg = take(((size_t)B * L + 8) * d * 2);   // + 8: the scoring head multiplies ceil8(R) rows (pad rows: any content)
     c.rows = take((size_t)B * L * 4);
     c.posmap = take((size_t)c.M * 4);
     c.total = off;

@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include "common.h"
 
-enum GemmEpilogue { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_QKV = 3 };
+enum GemmEpilogue { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_QKV = 3, EPI_ROWSTAT = 4 };
 
 struct GemmArgs {
     const bf16_t* A;   // [M, lda]   activations, K-contiguous
@@ -49,6 +49,27 @@ struct GemmArgs {
 
 int launch_gemm(int epi, const GemmArgs& g, hipStream_t s);
 
+// EPI_ROWSTAT (the scoring head, launch_head_rowstat).  Nothing of C is stored.  Per row m < rows and 256-column tile nt ONE
+// record part[nt * ld + m] = {max, sum exp(x - max), first column of the max in the whole vocabulary (int bits), 0} over the
+// bf16-rounded logits x of that tile, and the logit at column target[m] - col0 (if that is a column of this launch) to tx[m].
+// M may be `rows` rounded up to 8 (pad rows of A hold anything; their results are dropped).
+// Its arguments travel in GemmArgs fields the epilogue has no other use for (C, resid, pos_map; rwin, rlp, rbeg), so that the
+// argument block every GEMM kernel takes keeps its layout and no other kernel's compiled code changes.
+struct RowStatArgs {
+    float4* part;            // [ceil(N / 256)][ld] records
+    float* tx;               // [ld] target logits, preset to -inf by the launcher
+    const int64_t* target;   // [rows] column in the whole vocabulary, or negative: none
+    int rows, ld, col0;
+};
+static inline __host__ __device__ RowStatArgs rowstat_args(const GemmArgs& g) {
+    return RowStatArgs{(float4*)g.C, (float*)g.resid, (const int64_t*)g.pos_map, g.rwin, g.rlp, g.rbeg};
+}
+static inline void set_rowstat_args(GemmArgs& g, const RowStatArgs& r) {
+    g.C = (bf16_t*)r.part; g.resid = (const bf16_t*)r.tx; g.pos_map = (const int32_t*)r.target;
+    g.ldc = 8; g.ldr = 8;   // (the 8-phase kernel's shape contract looks at them)
+    g.rwin = r.rows; g.rlp = r.ld; g.rbeg = r.col0;
+}
+
 // A plain C[M, ldc] = A[M, K] · W[N, K]^T on K-contiguous operands (lda = ldw = K), epilogue fields left zero.
 static inline GemmArgs gemm_bt_args(const bf16_t* A, const bf16_t* W, bf16_t* C, int M, int N, int K, int ldc) {
     GemmArgs g{};
@@ -65,6 +86,13 @@ struct Switches {
     int gemm_config, gemm_silu_lut, gemm_short_tiles, gemm_tile_order, attention_form, probe_variant, tp_allow_single_rank;
 };
 Switches switches();
+
+// gemm.hip: the scoring head.  A [ceil8(R), K] (rows >= R: anything), W = lm_head rows [col0, col0 + N).  `part` holds
+// head_rowstat_bytes(R, N) bytes.  Outputs [R] (lse / argmax / max may be null): logprob = x_target - lse (0 for a negative
+// target, -inf for a target outside [col0, col0 + N)), argmax = column index in the WHOLE vocabulary (first maximum).
+size_t head_rowstat_bytes(int R, int N);
+int launch_head_rowstat(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, const int64_t* targets, void* part,
+                        float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s);
 
 // elementwise.hip
 // norm_w != null: also xn = RMSNorm(x) * norm_w (the first norm of the forward, fused: SURVEY §2.3 K1)

@@ -76,8 +76,84 @@ def _validate(cfg: LLaDAConfigLite) -> None:
         raise NotImplementedError("head_dim must be 128")
 
 
+# special ids of the reference class (model/modeling_xllmx_dimoo.py:28-34)
+IMAGE_START_TOKEN, IMAGE_END_TOKEN = 126349, 126350
+ANSWER_START_TOKEN, ANSWER_END_TOKEN = 126354, 126355
+BREAKLINE_TOKEN = 126084
+IGNORE_INDEX = -100
+
+
+def pad_id_lists(input_ids, labels=None):
+    """The reference's ragged-batch handling (model/modeling_xllmx_dimoo.py:56-59,80-81): id lists are padded with token 0,
+    label lists with -100, to the longest.  Tensors pass through (every length = L).  Returns (ids [B, L] int64 CPU tensor or
+    the given tensor, labels likewise or None, lengths list)."""
+    if torch.is_tensor(input_ids):
+        ids = input_ids.to(torch.long)
+        lengths = [ids.shape[1]] * ids.shape[0]
+    else:
+        lengths = [len(e) for e in input_ids]
+        L = max(lengths)
+        ids = torch.tensor([list(e) + [0] * (L - len(e)) for e in input_ids], dtype=torch.long)
+    if labels is None:
+        return ids, None, lengths
+    if torch.is_tensor(labels):
+        lab = labels.to(torch.long)
+    else:
+        L = ids.shape[1]
+        lab = torch.tensor([list(e) + [IGNORE_INDEX] * (L - len(e)) for e in labels], dtype=torch.long)
+    if lab.shape != ids.shape:
+        raise ValueError(f"labels {tuple(lab.shape)} do not match input_ids {tuple(ids.shape)}")
+    return ids, lab, lengths
+
+
+def loss_regions(unscaled_loss: torch.Tensor, input_ids: torch.Tensor, labels: torch.Tensor, lengths, t=None):
+    """interleave / text / image loss of the reference from per-token losses (model/modeling_xllmx_dimoo.py:93-173), as tensor
+    operations on whatever device the arguments live on.
+
+    unscaled_loss [B, L] (0 where labels == -100; the reference's dtype is the logits': bf16), input_ids / labels [B, L] int64,
+    lengths: the sequences' lengths before padding.  Regions, per sequence with an answer-start token (others contribute to
+    the interleave loss only): the answer span runs from the first answer-start token to the first answer-end token behind it
+    (else to the sequence's length).  With an image-start token inside the span and an image-end token anywhere behind it:
+    image loss = every position strictly between the two that is not a break-line token (labelled or not), text loss = the
+    labelled positions behind the image end inside the span; an image start without an end contributes nothing.  Without an
+    image: text loss = the labelled positions of the span behind the answer-start token.  Each loss is the mean over its
+    positions in (sequence, position) order — the order of the reference's lists — or 0.0 (fp32) when there are none;
+    t: text_loss / t.mean().clamp(min=0.01) when any text position exists.
+    Returns (interleave_loss, text_loss, image_loss), 0-dim tensors."""
+    dev = unscaled_loss.device
+    ids, lab = input_ids.to(dev), labels.to(dev)
+    B, L = ids.shape
+    pos = torch.arange(L, device=dev)[None, :]
+    lens = torch.as_tensor(lengths, device=dev, dtype=torch.long)
+
+    def first(cond):   # (any, index of the first True or L)
+        return cond.any(1), torch.where(cond, pos, L).amin(1)
+
+    valid = lab != IGNORE_INDEX
+    has_as, a_start = first(ids == ANSWER_START_TOKEN)
+    has_ae, a_end = first((ids == ANSWER_END_TOKEN) & (pos >= a_start[:, None]))
+    a_end = torch.where(has_ae, a_end, lens)
+    in_answer = (pos >= a_start[:, None]) & (pos < a_end[:, None])
+    has_img, i_start = first((ids == IMAGE_START_TOKEN) & in_answer)
+    has_ie, i_end = first((ids == IMAGE_END_TOKEN) & (pos >= i_start[:, None]))
+    img_ok = has_as & has_img & has_ie
+    image_mask = img_ok[:, None] & (pos > i_start[:, None]) & (pos < i_end[:, None]) & (ids != BREAKLINE_TOKEN)
+    behind = torch.where(has_img[:, None], has_ie[:, None] & (pos > i_end[:, None]), pos > a_start[:, None])
+    text_mask = has_as[:, None] & valid & behind & (pos < a_end[:, None])
+
+    def mean_of(mask):
+        sel = unscaled_loss[mask]
+        return sel.mean() if sel.numel() else torch.tensor(0.0, device=dev)
+
+    interleave_loss = mean_of(valid)
+    text_loss, image_loss = mean_of(text_mask), mean_of(image_mask)
+    if t is not None and bool(text_mask.any()):
+        text_loss = text_loss / torch.as_tensor(t, device=dev).mean().clamp(min=0.01)
+    return interleave_loss, text_loss, image_loss
+
+
 class LLaDAForMultiModalGeneration:
-    """MI355X-native drop-in for the reference class of the same name (inference path only)."""
+    """MI355X-native drop-in for the reference class of the same name (inference and scoring; no backward pass)."""
 
     MASK_TOKEN = 126336
 
@@ -311,6 +387,68 @@ class LLaDAForMultiModalGeneration:
                                             out[cut:].data_ptr(), st), "mmada_head_rows")
         return out
 
+    _TP_SCORE = ("scoring under tensor parallelism is not implemented yet: a vocabulary-parallel score is the same records "
+                 "exchanged as in mmada_text_select_tp")
+
+    def token_logprobs(self, rows: torch.Tensor, targets: torch.Tensor, col_begin: int = 0, col_end: Optional[int] = None,
+                       return_stats: bool = False):
+        """log softmax(logits[rows[r], col_begin:col_end])[targets[r]] as fp32 [R], after forward_body(), without materialising
+        the logits (mmada_head_logprobs: the head GEMM reduces its tiles to row statistics in the epilogue).
+
+        rows = b*L + l (batch-major); targets = column in the WHOLE vocabulary, < 0: ignored (0.0), outside the column range:
+        -inf.  return_stats: also (lse fp32, argmax int32 — column in the whole vocabulary, first maximum —, max fp32)."""
+        if self.tp_size != 1:
+            raise NotImplementedError(self._TP_SCORE)
+        col_end = self.vocab if col_end is None else col_end
+        rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
+        targets = targets.to(device=self.device, dtype=torch.long).contiguous()
+        R = rows.numel()
+        if targets.numel() != R:
+            raise ValueError("token_logprobs: one target per row")
+        lp = torch.empty(R, dtype=torch.float32, device=self.device)
+        stats = (torch.empty(R, dtype=torch.float32, device=self.device), torch.empty(R, dtype=torch.int32, device=self.device),
+                 torch.empty(R, dtype=torch.float32, device=self.device)) if return_stats else None
+        st = abi.stream_ptr()
+
+        def call(handle, lo, hi, row_t):
+            if hi <= lo:
+                return
+            ptr = lambda t_: t_[lo:hi].data_ptr()   # noqa: E731
+            abi.check(self._lib.mmada_head_logprobs(handle, row_t.data_ptr(), hi - lo, col_begin, col_end, ptr(targets), ptr(lp),
+                                                    ptr(stats[0]) if stats else None, ptr(stats[1]) if stats else None,
+                                                    ptr(stats[2]) if stats else None, st), "mmada_head_logprobs")
+
+        if getattr(self, "_split", None) is None:
+            call(self._handle, 0, R, rows)
+        else:   # micro-batched forward: the second activation context indexes its own batch from 0 (as head_rows does)
+            B0, L = self._split, self._shape[1]
+            cut = int((rows < B0 * L).sum())
+            if cut and cut < R and not bool((rows[:cut] < B0 * L).all()):
+                raise ValueError("token_logprobs on a micro-batched forward needs batch-major rows")
+            call(self._handle, 0, cut, rows[:cut].contiguous())
+            call(self._handle1, cut, R, (rows[cut:] - B0 * L).contiguous())
+        return (lp, *stats) if return_stats else lp
+
+    def score(self, input_ids: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """Per-token negative log-likelihood, fp32 [B, L]: -log softmax(logits[b, l])[labels[b, l]], 0 where labels == -100 —
+        F.cross_entropy(logits.view(-1, V), labels.view(-1), ignore_index=-100, reduction='none') of the reference
+        (model/modeling_xllmx_dimoo.py:86-91) in fp32.  One forward_body plus one token_logprobs over the labelled rows."""
+        if self.tp_size != 1:
+            raise NotImplementedError(self._TP_SCORE)
+        ids = input_ids.to(device=self.device, dtype=torch.long)
+        lab = labels.to(device=self.device, dtype=torch.long)
+        if lab.shape != ids.shape:
+            raise ValueError(f"labels {tuple(lab.shape)} do not match input_ids {tuple(ids.shape)}")
+        if bool((lab >= self.vocab).any()):
+            raise ValueError("labels outside the vocabulary")
+        self.forward_body(ids)
+        out = torch.zeros(ids.shape, dtype=torch.float32, device=self.device)
+        flat = lab.reshape(-1)
+        rows = (flat != IGNORE_INDEX).nonzero().flatten()
+        if rows.numel():
+            out.view(-1)[rows] = -self.token_logprobs(rows.to(torch.int32), flat[rows])
+        return out
+
     def hidden_state(self) -> torch.Tensor:
         """Residual stream after the last block, [B, L, d] (parity tap)."""
         B, L = self._shape
@@ -342,15 +480,60 @@ class LLaDAForMultiModalGeneration:
             t = t.reshape(B, hkv, 128, lkv.value // 32, 8, 4)[..., [0, 2, 4, 6, 1, 3, 5, 7], :].reshape(B, hkv, 128, lkv.value)
         return t
 
-    def forward(self, input_ids=None, labels=None, infer=False, use_cache=False, to_compute_mask=None, cat="", **_):
+    def _forward_loss(self, input_ids, labels, return_dict, compute_separate_losses, t):
+        """forward(infer=False): the reference's loss contract (model/modeling_xllmx_dimoo.py:56-194), see forward()."""
+        if self.tp_size != 1:
+            raise NotImplementedError(self._TP_SCORE)
+        if labels is None:
+            # the reference returns the logits here (:74-78), which forward(infer=True) already does; this combination stays the
+            # loud refusal it has always been (tests/test_reference_contract.py pins it)
+            raise NotImplementedError("forward(infer=False) needs labels (the loss); forward(infer=True) returns the logits")
+        ids, lab, lengths = pad_id_lists(input_ids, labels)
+
+        def all_logits():
+            self.forward_body(ids)
+            B, L = self._shape
+            rows = torch.arange(B * L, dtype=torch.int32, device=self.device)
+            return self.head_rows(rows, 0, self.vocab).view(B, L, self.vocab)
+
+        lab = lab.to(self.device)
+        unscaled = self.score(ids, lab).to(torch.bfloat16)   # the reference's per-token loss has the logits' dtype
+        logits = all_logits() if return_dict else None
+        if not compute_separate_losses:
+            valid = lab != IGNORE_INDEX
+            loss = unscaled[valid].mean() if bool(valid.any()) else torch.tensor(0.0, device=self.device)
+            return {"logits": logits, "loss": loss, "labels": lab} if return_dict else loss
+        loss, text_loss, image_loss = loss_regions(unscaled, ids, lab, lengths, t=t)
+        if return_dict:
+            return {"logits": logits, "loss": loss, "interleave_loss": loss, "text_loss": text_loss, "image_loss": image_loss,
+                    "labels": lab}
+        return loss, {"text_loss": text_loss, "image_loss": image_loss, "interleave_loss": loss}
+
+    def forward(self, input_ids=None, labels=None, infer=False, use_cache=False, to_compute_mask=None, cat="",
+                return_dict=False, compute_separate_losses=True, t=None, **_):
         """LLaDAForMultiModalGeneration.forward(infer=True) (model/modeling_xllmx_dimoo.py:41-72) -> logits [B, L, vocab].
 
         use_cache / to_compute_mask / cat are LLaDAModelLM.forward's dLLM-cache arguments (model/modeling_llada.py:
         1468-1493,1244-1245,929-940,1406-1413): with use_cache=True the call goes through the cache slot of `cat`
         (forward_cached); to_compute_mask [B, L] bool then selects the tokens that are recomputed — every other position's
-        keys, values and logits are reused — and the returned logits are the whole logit cache, as in the reference."""
-        if not infer or labels is not None:
-            raise NotImplementedError("only forward(infer=True) is on the MI355X hot path (training loss is out of scope)")
+        keys, values and logits are reused — and the returned logits are the whole logit cache, as in the reference.
+
+        infer=False (model/modeling_xllmx_dimoo.py:74-194; forward value only, there is no backward pass): input_ids / labels are
+        lists of id lists (padded with 0 / -100 to the longest, as the reference does) or [B, L] tensors.  The reference pads a
+        ragged batch and then attends to the pad tokens — its attention drops the attention bias the wrapper builds
+        (model/modeling_llada.py:671-679) — so a padded batch is simply an equal-length batch whose pad rows are ignored through
+        labels = -100; that is reproduced, not repaired.  labels=None (the reference returns the logits, :74-78) stays refused:
+        forward(infer=True) is the logits call.  The per-token loss is score() rounded once to bf16 (the logits' dtype in the reference) and the result is the
+        reference's: the scalar interleave loss (compute_separate_losses=False), (loss, {'text_loss', 'image_loss',
+        'interleave_loss'}), or with return_dict a dict that also holds 'labels' and 'logits' — only that last form materialises
+        the [B, L, vocab] logits (through head_rows); every other form runs the fused scoring head.  t: scales text_loss
+        (loss_regions).  text_coeff / image_coeff are accepted and unused, as in the reference."""
+        if not infer:
+            if use_cache or to_compute_mask is not None:
+                raise NotImplementedError("forward(infer=False) does not go through the dLLM cache")
+            return self._forward_loss(input_ids, labels, return_dict, compute_separate_losses, t)
+        if labels is not None:
+            raise NotImplementedError("forward(infer=True) returns logits; pass infer=False to score labels")
         if to_compute_mask is not None and not use_cache:
             raise ValueError("to_compute_mask needs use_cache=True (the reference only gathers the tokens then, "
                              "model/modeling_llada.py:1244-1245)")

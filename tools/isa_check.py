@@ -94,12 +94,21 @@ def check_m0(name, lines):
     return errors
 
 
-def check_gemm8(asm=None):
+# scalar memory WRITES (stores, atomics, data-cache write-back / discard): never emitted for this code base; checked by mnemonic
+SCALAR_WRITE = re.compile(r"^s_(?:buffer_|scratch_)?(?:st" r"ore|at" r"omic)|^s_dcache_(?:w" r"b|disc" r"ard)")
+
+
+def check_gemm8(asm=None, epilogues=(0, 1, 2, 3)):
+    """The 8-phase kernels whose template argument EPI is in `epilogues` (0-3: STORE, RESID, SwiGLU, QKV; 4: the scoring head's
+    row statistics, see check_gemm8_rowstat)."""
     asm = asm or device_asm("gemm8.hip")
     body, meta = kernels(asm)
     report, errors = [], []
     for name, lines in body.items():
         if "gemm8_kernel" not in name:
+            continue
+        m_e = re.search(r"gemm8_kernelILi(\d)E", name)
+        if not m_e or int(m_e.group(1)) not in epilogues:
             continue
         # Control-flow graph over basic blocks, then a forward may-analysis of one bit: "a foreign vector-memory op may be
         # in the queue" (set by a foreign op, cleared by any vmcnt(0) wait).  A hand-written counted wait reached with
@@ -212,6 +221,9 @@ def check_gemm8(asm=None):
             errors.append(f"{name}: private segment of {priv} bytes, {n_scratch} scratch instructions (a register spill)")
         if n_dma == 0 or n_saddr != n_dma:
             errors.append(f"{name}: {n_saddr} of {n_dma} LDS-DMA loads use the scalar-base form")
+        n_swr = sum(1 for b in blocks for x in b if SCALAR_WRITE.match(x))
+        if n_swr:
+            errors.append(f"{name}: {n_swr} scalar memory write instructions")
         # epilogues of the STORE / RESID / SwiGLU builds (template argument EPI = 0, 1, 2: every wave has the transposed
         # accumulator): all output goes out as 16-byte stores after a half-row lane exchange — no 2-, 4- or 8-byte store left
         m_epi = re.search(r"gemm8_kernelILi(\d)E", name)
@@ -227,9 +239,37 @@ def check_gemm8(asm=None):
     if not report:
         errors.append("no gemm8 kernel found")
     for name, lines in body.items():
-        if "gemm8_kernel" in name:
+        if any(name == r[0] for r in report):
             errors += check_m0(name, lines)
     return report, errors
+
+
+def check_gemm8_rowstat(asm=None):
+    """The row-statistics instantiations (EPI = 4, csrc/gemm_epilogue.h rowstat_epilogue) get every check of the other epilogues
+    (counted waits behind LDS-DMA only, M0 contract, no static LDS, no spill, no scalar memory write), and: three tile
+    configurations (256-column tiles only); one v_exp_f32 per logit of a lane (4 code paths x FM x 16), none of them expanded
+    into a libm call sequence; nothing of the logits is stored — per code path one 16-byte record store and the (rare) 4-byte
+    target-logit stores, no 2- or 8-byte store."""
+    asm = asm or device_asm("gemm8.hip")
+    report, errors = check_gemm8(asm, epilogues=(4,))
+    body, _ = kernels(asm)
+    if len(report) != 3:
+        errors.append(f"{len(report)} row-statistics instantiations of the 8-phase kernel (3 expected)")
+    out = []
+    for name, n_dma, n_wait, n_foreign in report:
+        ins = [ln.split(";")[0].strip() for ln in body[name]]
+        n_exp = sum(1 for x in ins if x.startswith("v_exp_f32"))
+        x4 = sum(1 for x in ins if x.startswith("global_store_dwordx4"))
+        x1 = sum(1 for x in ins if re.match(r"global_store_dword\b", x))
+        other = sum(1 for x in ins if re.match(r"(global|flat|buffer)_store_", x)) - x4 - x1
+        bm = int(re.search(r"Gemm8ILi(\d+)E", name).group(1))
+        per_path = (bm // 2 // 16) * 16
+        if n_exp < per_path or n_exp > 4 * per_path:
+            errors.append(f"{name}: {n_exp} v_exp_f32 ({per_path} per code path expected)")
+        if other or not x4 or x4 > 4:
+            errors.append(f"{name}: stores: {x4} x 16 B (records), {x1} x 4 B (target logit), {other} other")
+        out.append((name, n_dma, n_wait, n_exp, x4, x1))
+    return out, errors
 
 
 def check_attention(asm=None):
@@ -305,6 +345,10 @@ def main():
     rep, err = check_gemm8()
     for name, n_dma, n_wait, n_foreign in rep:
         print(f"gemm8  {name[:90]:90s} LDS-DMA {n_dma:3d}  counted waits {n_wait:3d}  foreign VMEM after the first DMA {n_foreign}")
+    bad += err
+    rep, err = check_gemm8_rowstat()
+    for name, n_dma, n_wait, n_exp, x4, x1 in rep:
+        print(f"gemm8  {name[:90]:90s} LDS-DMA {n_dma:3d}  counted waits {n_wait:3d}  v_exp_f32 {n_exp}  stores 16 B {x4}, 4 B {x1}")
     bad += err
     rep, err = check_attention()
     for name, n_dma, n_mfma, counted in rep:
