@@ -122,7 +122,15 @@ int mmada_head_rows(mmada_handle* h, const int32_t* rows, int R, int col_begin, 
  * Honours the row window of mmada_set_consumed_rows exactly as mmada_head_rows does.  Record buffer: owned by the handle,
  * (re)allocated when a call needs more than it holds — ceil(N / 256) * ceil8(R) * 16 + ceil8(R) * 4 bytes, 1/32 of the bf16 logits
  * the call stands for (mmada_score_buffer_bytes reports what is held); a call that fits is capturable in a hipGraph.
- * Tensor-parallel handles: not yet (returns an error). */
+ * Tensor parallel: on a handle with a connected exchange (mmada_comm_connect_*: pull, copy or RCCL; also a one-rank group) and a
+ * resident tensor-parallel forward, EVERY rank makes the call with the same arguments.  The launch's 256-column tiles are split
+ * over the ranks in contiguous blocks — ntn = ceil((col_end - col_begin) / 256), q = ceil(ntn / tp_size), rank r owns tiles
+ * [r*q, min(ntn, (r+1)*q)), possibly none — each rank writes the records of its tiles (the same records the one-rank launch
+ * writes) into a published buffer of the comm, the ranks hand off as in mmada_text_select_tp, and every rank joins every row in
+ * the one-rank order: all ranks receive the same four outputs, bit-identical to a one-rank handle on the same normalised rows.
+ * Rows pass through the published buffers in rounds of 1280; the buffers are sized by mmada_comm_create, so the call never
+ * allocates and never synchronises the host (always capturable; a captured call adds a hand-off at each end), and R > max_rows
+ * of mmada_comm_create is an error that names the limit.  tp_size > 1 without a connected exchange: an error. */
 int mmada_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
                         float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out, void* stream);
 size_t mmada_score_buffer_bytes(const mmada_handle* h);

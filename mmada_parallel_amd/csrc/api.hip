@@ -563,9 +563,12 @@ int mmada_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_beg
                         float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out, void* stream) {
     if (!h || h->M == 0) return mm_fail("mmada_head_logprobs: no forward resident");
     if (!rows || !targets || !logprob_out) return mm_fail("mmada_head_logprobs: null argument");
-    if (h->xn_is_final || h->cfg.tp_size != 1 || tp_comm_connected(h))
-        return mm_fail("mmada_head_logprobs: tensor-parallel handles are not supported yet (a vocabulary-parallel score exchanges "
-                       "the same records as mmada_text_select_tp)");
+    // a connected handle (also a one-rank group): the vocabulary-parallel head, same records, same fold (tp_comm.hip)
+    if (tp_comm_connected(h))
+        return tp_head_logprobs(h, rows, R, col_begin, col_end, targets, logprob_out, lse_out, argmax_out, max_out, (hipStream_t)stream);
+    if (h->xn_is_final || h->cfg.tp_size != 1)
+        return mm_fail("mmada_head_logprobs: a tensor-parallel handle scores through the library's exchange only (mmada_comm_create + "
+                       "mmada_comm_connect_*): a vocabulary-parallel score exchanges the same records as mmada_text_select_tp");
     if (R <= 0) return 0;
     if (R > h->B * h->L) return mm_fail("mmada_head_logprobs: R=%d exceeds B*L=%d", R, h->B * h->L);
     if (col_begin < 0 || col_end > h->cfg.vocab || col_begin >= col_end) return mm_fail("mmada_head_logprobs: bad column range");

@@ -24,6 +24,7 @@
 #include <mutex>
 
 #include "gemm_epilogue.h"
+#include "rowstat_fold.h"
 
 namespace {
 
@@ -364,51 +365,16 @@ size_t head_rowstat_bytes(int R, int N) {
     return rp * rowstat_tiles(N) * sizeof(float4) + rp * sizeof(float);
 }
 
-// Joins the column-tile records of a row in a FIXED order (so that neither the tile order of the GEMM nor its configuration
-// shows in the result): 16 rows x 16 tile groups per workgroup; group j folds tiles j, j + 16, ... in ascending order (online
-// soft-max: rescale by exp(m_tile - m_row)), then thread (row, 0) folds the 16 groups in ascending order.
-constexpr int RS_ROWS = 16, RS_GROUPS = 16;
+// Joins the column-tile records of a row in the fixed order of rowstat_fold.h (shared with the tensor-parallel join of
+// tp_comm.hip): neither the tile order of the GEMM nor its configuration shows in the result.
 __global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void rowstat_combine_kernel(const float4* part, const float* tx, const int64_t* targets,
                                                                                int R, int ld, int ntn, float* logprob, float* lse_out,
                                                                                int32_t* argmax_out, float* max_out) {
-    __shared__ float sm[RS_GROUPS][RS_ROWS], ss[RS_GROUPS][RS_ROWS];
-    __shared__ int sa[RS_GROUPS][RS_ROWS];
-    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
-    const int row = blockIdx.x * RS_ROWS + rl;
-    float m = -__builtin_inff(), sum = 0.f;
-    int arg = 0x7fffffff;
-    if (row < R)
-        for (int t = j; t < ntn; t += RS_GROUPS) {
-            const float4 p = part[(size_t)t * ld + row];
-            const int a = __float_as_int(p.z);
-            if (p.x > m) {   // tiles ascend inside a group: an equal maximum further right does not replace
-                sum = sum * expf(m - p.x) + p.y;
-                m = p.x;
-                arg = a;
-            } else
-                sum += p.y * expf(p.x - m);
-        }
-    sm[j][rl] = m; ss[j][rl] = sum; sa[j][rl] = arg;
-    __syncthreads();
-    if (j != 0 || row >= R) return;
-    for (int q = 1; q < RS_GROUPS; ++q) {
-        const float mq = sm[q][rl], sq = ss[q][rl];
-        const int aq = sa[q][rl];
-        if (mq > m) {
-            sum = sum * expf(m - mq) + sq;
-            m = mq;
-            arg = aq;
-        } else if (mq > -__builtin_inff()) {
-            sum += sq * expf(mq - m);
-            if (mq == m && aq < arg) arg = aq;   // groups interleave the tiles: the leftmost column wins
-        }
-    }
-    const float lse = m + logf(sum);
-    const long long t = targets[row];
-    logprob[row] = t < 0 ? 0.f : tx[row] - lse;
-    if (lse_out) lse_out[row] = lse;
-    if (argmax_out) argmax_out[row] = arg;
-    if (max_out) max_out[row] = m;
+    const int row = blockIdx.x * RS_ROWS + threadIdx.x % RS_ROWS;
+    float m, sum;
+    int arg;
+    if (!rowstat_fold([&](int t, int r) { return part[(size_t)t * ld + r]; }, row, R, ntn, m, sum, arg)) return;
+    rowstat_finish(row, m, sum, arg, targets[row], tx[row], logprob, lse_out, argmax_out, max_out);
 }
 
 int launch_head_rowstat(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, const int64_t* targets, void* part,

@@ -94,6 +94,9 @@ int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s);  // resi
 void tp_comm_free(mmada_handle* h);
 bool tp_comm_connected(const mmada_handle* h);   // a transport (or the no-exchange diagnostic) is active on this handle
 int tp_head_gather(mmada_handle* h, const int32_t* rows, int R, hipStream_t s);  // xg[r] = xn[row r] (xn already = ln_f(x))
+// mmada_head_logprobs on a connected handle: the 256-column tiles split over the ranks, records exchanged, every rank joins
+int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
+                     float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s);
 // out[r] = src[b * Lp + l] for rows[r] = b * L + l: the plain row gather behind tp_head_gather, on any [B * Lp, d] buffer
 int tp_gather_rows(const bf16_t* src, const int32_t* rows, int R, int L, int Lp, int d, int nflat, bf16_t* out, hipStream_t s);
 

@@ -42,6 +42,7 @@
 #include <cstring>
 
 #include "handle.h"
+#include "rowstat_fold.h"
 
 namespace {
 
@@ -49,6 +50,8 @@ constexpr int TP_MAX = 8;
 constexpr int MAXCH = 8;  // 16-B chunks per lane: d <= 4096
 
 constexpr int STAT_ROWS = 16384;  // text rows (B*T) a vocabulary-parallel select can take
+constexpr int SCORE_ROUND = 1280;  // rows per round of the vocabulary-parallel scoring head: whole 320 / 256 / 160 / 128-row GEMM tiles
+constexpr int SCORE_BN = 256;      // columns per record of EPI_ROWSTAT (kernels.h)
 
 struct TpPeers {
     const bf16_t* part[TP_MAX];
@@ -80,6 +83,15 @@ struct TpComm {
     uint32_t* ctr = nullptr;   // [16] published sequence counter (fine-grained memory when the runtime grants it)
     TextStat* stats_pub = nullptr;  // [STAT_ROWS] published: this rank's per-row record of the vocabulary-parallel text head
     TextStat* stats_all = nullptr;  // [size][STAT_ROWS] RCCL transport: all-gathered records
+    // vocabulary-parallel scoring head (tp_head_logprobs).  Two published record buffers, used alternately, in stats_pub's
+    // allocation behind the STAT_ROWS text records (one hipIpc handle covers both).  One buffer = score_round target logits
+    // (fp32), then [score_tiles][ld] 16-byte tile records of this rank's tiles (ld = the round's rows, rounded up to 8)
+    char* score_pub[2] = {nullptr, nullptr};
+    char* score_all = nullptr;      // [size][score_buf_bytes] private: the peers' buffers as gathered (RCCL) / staged (copy)
+    size_t score_buf_bytes = 0;
+    int score_round = 0;            // rows per round: min(SCORE_ROUND, ceil8(max_rows))
+    int score_tiles = 0;            // 256-column tiles a rank can own: ceil(ceil(vocab / 256) / size)
+    int score_flip = 0;             // the buffer the next round writes
     bf16_t* head_buf = nullptr;     // [head_rows, ceil(V/size)] this rank's logit slice (allocated at first use)
     size_t head_bytes = 0;
     uint32_t* seq = nullptr;   // [1]  private: number of hand-offs this rank has published
@@ -322,6 +334,65 @@ __global__ void tp_text_combine_kernel(TpPeers p, int size, int rank, const Text
         if (st[j].lmax > -INFINITY) tot += st[j].sum * exp((double)st[j].lmax - (double)mx);
     conf_out[row] = 1.0 / tot;  // exp(l[x0] - max) / sum with x0 the arg-max
     x0_out[row] = arg;
+}
+
+// ---- vocabulary-parallel scoring head ---------------------------------------------------------------------------------------
+// tx[0, n) = -inf in a PUBLISHED buffer (a target outside a rank's columns leaves it behind): ends like every publishing kernel
+__global__ __launch_bounds__(256) void tp_score_reset_kernel(float* tx, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) tx[i] = -__builtin_inff();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+struct ScoreJoinArgs {
+    const char* src[TP_MAX];  // rank j's record buffer of this round where THIS rank reads it: its own memory, a peer's mapped
+                              // buffer (pull) or the gathered / staged copy (RCCL, copy)
+    int sys;                  // pull: src[j != rank] is remote, read with system-scope loads
+    int size, rank;
+    int q;                    // tiles per rank: tile t is record (t - owner * q) of rank owner = t / q
+    uint32_t rec_off;         // byte offset of the records behind the target logits
+    int ld, ntn, R, col_begin, col_end;
+    const int64_t* targets;
+    float *logprob, *lse;
+    int32_t* argmax;
+    float* vmax;
+};
+
+// The join of rowstat_combine_kernel (gemm.hip) with tile t's record taken from the rank that owns t: the same fold
+// (rowstat_fold.h), so every rank — and a one-rank handle — ends with the same bits.  Every rank joins every row.
+__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_score_join_kernel(ScoreJoinArgs a) {
+    if (a.sys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // see tp_reduce_norm_kernel
+    const int row = blockIdx.x * RS_ROWS + threadIdx.x % RS_ROWS;
+    auto fetch = [&](int t, int r) -> float4 {
+        const int owner = t / a.q;
+        const uint32_t off = a.rec_off + ((uint32_t)(t - owner * a.q) * (uint32_t)a.ld + (uint32_t)r) * 16u;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        // the lanes of a wave hold neighbouring tiles, which may belong to two owners: one pass per rank (unrolled: src[o] is a
+        // kernel argument in SGPRs) keeps the base pointer wave-uniform, as load_sys16's descriptor needs it
+#pragma unroll
+        for (int o = 0; o < TP_MAX; ++o) {
+            if (o != owner) continue;
+            if (a.sys && o != a.rank) v = load_sys16(a.src[o], off);
+            else v = *(const u32x4*)(a.src[o] + off);
+        }
+        return float4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
+    };
+    float m, sum;
+    int arg;
+    if (!rowstat_fold(fetch, row, a.R, a.ntn, m, sum, arg)) return;
+    const long long t = a.targets[row];
+    float tx = -__builtin_inff();
+    if (t >= a.col_begin && t < a.col_end) {  // the target logit lives with the rank that owns the target's tile
+        const int owner = (int)((t - a.col_begin) / SCORE_BN) / a.q;
+#pragma unroll
+        for (int o = 0; o < TP_MAX; ++o) {
+            if (o != owner) continue;
+            const float* p = (const float*)a.src[o] + row;
+            tx = (a.sys && o != a.rank) ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : *p;
+        }
+    }
+    rowstat_finish(row, m, sum, arg, t, tx, a.logprob, a.lse, a.argmax, a.vmax);
 }
 
 // One wave on (at least) every XCD writes that XCD's L2 back: for partials that were NOT produced by a publishing kernel
@@ -615,6 +686,7 @@ void tp_comm_free(mmada_handle* h) {
     (void)hipFree(c->stage);
     (void)hipFree(c->part); (void)hipFree(c->hn_pub); (void)hipFree(c->ctr);
     (void)hipFree(c->rs_tmp); (void)hipFree(c->stats_pub); (void)hipFree(c->stats_all); (void)hipFree(c->head_buf);
+    (void)hipFree(c->score_all);
     delete c;
     h->tp = nullptr;
 }
@@ -669,8 +741,16 @@ int mmada_comm_create(mmada_handle* h, int max_rows, void* export_out) {
     c->stage = nullptr;  // the copy transport's landing zone: allocated by the first mmada_comm_set_mode(4)
     MM_CHECK_HIP(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
     MM_CHECK_HIP(hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
-    MM_CHECK_HIP(alloc_pub((void**)&c->stats_pub, (size_t)STAT_ROWS * sizeof(TextStat), true, nullptr));
-    MM_CHECK_HIP(hipMemset(c->stats_pub, 0, (size_t)STAT_ROWS * sizeof(TextStat)));
+    // the scoring head's record buffers are sized here, once: a call never allocates (and so never synchronises the host)
+    c->score_round = min(SCORE_ROUND, (max_rows + 7) / 8 * 8);
+    c->score_tiles = ((h->cfg.vocab + SCORE_BN - 1) / SCORE_BN + c->size - 1) / c->size;
+    c->score_buf_bytes = align_up((size_t)c->score_round * 4 + (size_t)c->score_tiles * c->score_round * 16, 256);
+    const size_t text_bytes = (size_t)STAT_ROWS * sizeof(TextStat), stat_bytes = text_bytes + 2 * c->score_buf_bytes;
+    if (stat_bytes >= (1ull << 32)) return mm_fail("mmada_comm_create: %zu bytes of published records exceed 4 GiB", stat_bytes);
+    MM_CHECK_HIP(alloc_pub((void**)&c->stats_pub, stat_bytes, true, nullptr));
+    MM_CHECK_HIP(hipMemset(c->stats_pub, 0, stat_bytes));
+    for (int b = 0; b < 2; ++b) c->score_pub[b] = (char*)c->stats_pub + text_bytes + (size_t)b * c->score_buf_bytes;
+    MM_CHECK_HIP(hipMalloc(&c->score_all, (size_t)c->size * c->score_buf_bytes));
     MM_CHECK_HIP(hipMalloc(&c->stats_all, (size_t)c->size * STAT_ROWS * sizeof(TextStat)));
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // the exchange must not queue behind a whole round of GEMM workgroups
@@ -931,6 +1011,91 @@ int mmada_comm_destroy(mmada_handle* h) {
 }
 
 }  // extern "C"
+
+// Vocabulary-parallel scoring head (mmada_head_logprobs on a connected handle).  The launch's 256-column tiles are split over
+// the ranks in contiguous blocks (tp.py: score_tile_slice); each rank runs the one-rank EPI_ROWSTAT launch on its own tiles —
+// the same columns, col0-based arg-max indices and partial last tile, hence the same records — into a published buffer, the
+// ranks hand off, and every rank joins every row with the fold of the one-rank head.  Rows go in rounds of c->score_round.
+//
+// Buffer reuse (write after read).  A rank writes round i's records while a slower peer may still be joining an earlier
+// round, in this call or in the previous one (two calls with no forward between them are legal).  The two published buffers
+// alternate from round to round, ACROSS calls (c->score_flip; every rank makes the same calls, so the ranks agree on it).
+// Round i + 2 is the next writer of round i's buffer.  This rank enqueues those writes behind its wait of hand-off i + 1;
+// that wait returns only after every peer has signalled hand-off i + 1; a peer enqueues that signal behind its own join of
+// round i (same stream), and a kernel starts only after its predecessor in the stream has retired.  So every peer's reads of
+// round i are over before the first write of round i + 2 — whatever hand-off "i + 1" is: the next round's, the next call's,
+// or one of a forward in between.  A graph replay breaks the alternation (the buffer choice is frozen into the graph, and
+// eager calls and replays interleave freely), so a captured call brackets itself with a hand-off of its own at both ends:
+// behind the first every earlier join has retired, and nothing later writes before the last.  The RCCL transport needs neither
+// argument: an all-gather completes on a rank only when its send buffer may be reused.
+int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
+                     float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s) {
+    TpComm* c = h->tp;
+    if (!c || c->mode == 0 || c->mode == 3) return mm_fail("mmada_head_logprobs: no tensor-parallel transport connected");
+    if (!h->xn_is_final || h->M == 0) return mm_fail("mmada_head_logprobs: no tensor-parallel forward resident");
+    if (R <= 0) return 0;
+    if (R > c->max_rows)
+        return mm_fail("mmada_head_logprobs: %d rows exceed the %d rows this handle's comm was created for (mmada_comm_create max_rows)",
+                       R, c->max_rows);
+    if (R > h->B * h->L) return mm_fail("mmada_head_logprobs: R=%d exceeds B*L=%d", R, h->B * h->L);
+    if (col_begin < 0 || col_end > h->cfg.vocab || col_begin >= col_end) return mm_fail("mmada_head_logprobs: bad column range");
+    const int d = h->cfg.d_model, tp = c->size;
+    const int ntn = (col_end - col_begin + SCORE_BN - 1) / SCORE_BN, q = (ntn + tp - 1) / tp;
+    if (q > c->score_tiles) return mm_fail("mmada_head_logprobs: %d tiles per rank exceed the record buffers (%d)", q, c->score_tiles);
+    auto tiles_of = [&](int j) { return min(ntn, (j + 1) * q) - min(ntn, j * q); };
+    const int t0 = min(ntn, c->rank * q), nt_own = tiles_of(c->rank);
+    const int c0 = col_begin + t0 * SCORE_BN, n_own = nt_own > 0 ? min(col_end, c0 + nt_own * SCORE_BN) - c0 : 0;
+    const bool mapped = c->mode == 1 || c->mode == 4;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    const bool bracket = mapped && cs != hipStreamCaptureStatusNone;
+    const uint32_t rec_off = (uint32_t)c->score_round * 4u;
+    const size_t text_bytes = (size_t)STAT_ROWS * sizeof(TextStat);
+    if (tp_head_gather(h, rows, R, s)) return 1;
+    if (bracket && signal_wait(c, s)) return 1;
+    for (int r0 = 0; r0 < R; r0 += c->score_round) {
+        const int rr = min(c->score_round, R - r0), rp = (rr + 7) / 8 * 8;
+        char* buf = c->score_pub[c->score_flip];
+        float* tx = (float*)buf;
+        hipLaunchKernelGGL(tp_score_reset_kernel, dim3((rp + 255) / 256), dim3(256), 0, s, tx, rp);
+        MM_CHECK_HIP(hipGetLastError());
+        if (n_own > 0) {
+            GemmArgs g = gemm_bt_args(h->xg + (size_t)r0 * d, h->lm_head + (size_t)c0 * d, nullptr, rp, n_own, d, 8);
+            set_rowstat_args(g, RowStatArgs{(float4*)(buf + rec_off), tx, targets + r0, rr, rp, c0});
+            g.publish = mapped;
+            if (launch_gemm(EPI_ROWSTAT, g, s)) return 1;
+        }
+        ScoreJoinArgs a{};
+        a.sys = c->mode == 1; a.size = tp; a.rank = c->rank; a.q = q; a.rec_off = rec_off; a.ld = rp; a.ntn = ntn; a.R = rr;
+        a.col_begin = col_begin; a.col_end = col_end; a.targets = targets + r0;
+        a.logprob = logprob + r0; a.lse = lse ? lse + r0 : nullptr; a.argmax = argmax ? argmax + r0 : nullptr;
+        a.vmax = vmax ? vmax + r0 : nullptr;
+        if (mapped) {
+            if (signal_wait(c, s)) return 1;  // every rank's records of this round are complete
+            for (int j = 0; j < tp; ++j) {
+                const char* peer = (const char*)c->peers.stats[j] + text_bytes + (size_t)c->score_flip * c->score_buf_bytes;
+                if (j == c->rank) a.src[j] = buf;
+                else if (c->mode == 1) a.src[j] = peer;
+                else {  // copy engines: the peer's target logits and records of ITS tiles -> local staging
+                    char* dst = c->score_all + (size_t)j * c->score_buf_bytes;
+                    if (tiles_of(j) > 0)
+                        MM_CHECK_HIP(hipMemcpyAsync(dst, peer, (size_t)rec_off + (size_t)tiles_of(j) * rp * 16, hipMemcpyDefault, s));
+                    a.src[j] = dst;
+                }
+            }
+        } else {
+            const size_t cnt = (size_t)rec_off + (size_t)q * rp * 16;  // equal counts: a rank with fewer tiles sends stale bytes nobody reads
+            ncclResult_t r = c->nccl.AllGather(buf, c->score_all, cnt, ncclUint8, c->comm, s);
+            if (r != ncclSuccess) return nccl_fail(c, "ncclAllGather", r);
+            for (int j = 0; j < tp; ++j) a.src[j] = j == c->rank ? buf : c->score_all + (size_t)j * cnt;
+        }
+        hipLaunchKernelGGL(tp_score_join_kernel, dim3((rr + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, a);
+        MM_CHECK_HIP(hipGetLastError());
+        c->score_flip ^= 1;
+    }
+    if (bracket && signal_wait(c, s)) return 1;
+    return 0;
+}
 
 int tp_gather_rows(const bf16_t* src, const int32_t* rows, int R, int L, int Lp, int d, int nflat, bf16_t* out, hipStream_t s) {
     hipLaunchKernelGGL(gather_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, s, src, rows, R, L, Lp, d, nflat, out);

@@ -387,8 +387,12 @@ class LLaDAForMultiModalGeneration:
                                             out[cut:].data_ptr(), st), "mmada_head_rows")
         return out
 
-    _TP_SCORE = ("scoring under tensor parallelism is not implemented yet: a vocabulary-parallel score is the same records "
-                 "exchanged as in mmada_text_select_tp")
+    _TP_SCORE = ("scoring under tensor parallelism needs the library's exchange (init_tp_comm): a vocabulary-parallel score is the "
+                 "same records exchanged as in mmada_text_select_tp, which the host all-reduce fallback does not carry")
+
+    def _refuse_tp_score(self):
+        if self.tp_size != 1 and not getattr(self, "_comm_in_library", False):
+            raise NotImplementedError(self._TP_SCORE)
 
     def token_logprobs(self, rows: torch.Tensor, targets: torch.Tensor, col_begin: int = 0, col_end: Optional[int] = None,
                        return_stats: bool = False):
@@ -396,9 +400,12 @@ class LLaDAForMultiModalGeneration:
         the logits (mmada_head_logprobs: the head GEMM reduces its tiles to row statistics in the epilogue).
 
         rows = b*L + l (batch-major); targets = column in the WHOLE vocabulary, < 0: ignored (0.0), outside the column range:
-        -inf.  return_stats: also (lse fp32, argmax int32 — column in the whole vocabulary, first maximum —, max fp32)."""
-        if self.tp_size != 1:
-            raise NotImplementedError(self._TP_SCORE)
+        -inf.  return_stats: also (lse fp32, argmax int32 — column in the whole vocabulary, first maximum —, max fp32).
+
+        Under tensor parallelism with the library's exchange connected (init_tp_comm) every rank must make the call: each
+        multiplies its block of the launch's 256-column tiles (tp.score_tile_slice), the records are exchanged and every rank
+        returns the same bits — those of a one-rank handle on the same normalised rows.  The call never synchronises the host."""
+        self._refuse_tp_score()
         col_end = self.vocab if col_end is None else col_end
         rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
         targets = targets.to(device=self.device, dtype=torch.long).contiguous()
@@ -432,19 +439,22 @@ class LLaDAForMultiModalGeneration:
     def score(self, input_ids: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         """Per-token negative log-likelihood, fp32 [B, L]: -log softmax(logits[b, l])[labels[b, l]], 0 where labels == -100 —
         F.cross_entropy(logits.view(-1, V), labels.view(-1), ignore_index=-100, reduction='none') of the reference
-        (model/modeling_xllmx_dimoo.py:86-91) in fp32.  One forward_body plus one token_logprobs over the labelled rows."""
-        if self.tp_size != 1:
-            raise NotImplementedError(self._TP_SCORE)
+        (model/modeling_xllmx_dimoo.py:86-91) in fp32.  One forward_body plus one token_logprobs over the labelled rows.
+
+        The labelled-row list (the one host synchronisation) is built BEFORE the forward: between the first launch of the
+        forward and the last of the join nothing waits for the device, which a tensor-parallel rank group needs (a rank's
+        hand-off spins until its peers' launches arrive)."""
+        self._refuse_tp_score()
         ids = input_ids.to(device=self.device, dtype=torch.long)
         lab = labels.to(device=self.device, dtype=torch.long)
         if lab.shape != ids.shape:
             raise ValueError(f"labels {tuple(lab.shape)} do not match input_ids {tuple(ids.shape)}")
         if bool((lab >= self.vocab).any()):
             raise ValueError("labels outside the vocabulary")
-        self.forward_body(ids)
         out = torch.zeros(ids.shape, dtype=torch.float32, device=self.device)
         flat = lab.reshape(-1)
         rows = (flat != IGNORE_INDEX).nonzero().flatten()
+        self.forward_body(ids)
         if rows.numel():
             out.view(-1)[rows] = -self.token_logprobs(rows.to(torch.int32), flat[rows])
         return out
@@ -482,8 +492,7 @@ class LLaDAForMultiModalGeneration:
 
     def _forward_loss(self, input_ids, labels, return_dict, compute_separate_losses, t):
         """forward(infer=False): the reference's loss contract (model/modeling_xllmx_dimoo.py:56-194), see forward()."""
-        if self.tp_size != 1:
-            raise NotImplementedError(self._TP_SCORE)
+        self._refuse_tp_score()
         if labels is None:
             # the reference returns the logits here (:74-78), which forward(infer=True) already does; this combination stays the
             # loud refusal it has always been (tests/test_reference_contract.py pins it)

@@ -86,3 +86,13 @@ def vocab_slice(V: int, rank: int, size: int) -> Tuple[int, int]:
     w = ((V + size - 1) // size + 7) // 8 * 8
     v0 = min(V, rank * w)
     return v0, min(V, v0 + w)
+
+
+def score_tile_slice(n_cols: int, rank: int, size: int) -> Tuple[int, int]:
+    """256-column tiles [t0, t1) of a scoring launch over `n_cols` columns that rank `rank` multiplies in the vocabulary-parallel
+    scoring head (mmada_head_logprobs on a connected handle, tp_head_logprobs in csrc/tp_comm.hip): contiguous blocks of
+    q = ceil(tiles / size) tiles, so a rank produces exactly the records the one-rank launch produces for its tiles.  The range
+    of a trailing rank may be empty.  Tile t covers columns [col_begin + 256 t, min(col_end, col_begin + 256 (t + 1)))."""
+    ntn = (n_cols + 255) // 256
+    q = (ntn + size - 1) // size
+    return min(ntn, rank * q), min(ntn, (rank + 1) * q)

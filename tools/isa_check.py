@@ -340,6 +340,36 @@ def check_tp_pull(asm=None):
     return report, errors
 
 
+def check_tp_score_join(asm=None):
+    """The join of the vocabulary-parallel scoring head (tp_score_join_kernel): a peer's records arrive as single 16-byte
+    system-scope loads through descriptors held in SGPRs (no waterfall loop), nothing spills, and the fold is the shared one
+    (rowstat_fold.h: its three 16 x 16 LDS arrays)."""
+    asm = asm or device_asm("tp_comm.hip")
+    body, meta = kernels(asm)
+    report, errors = [], []
+    for name, lines in body.items():
+        if "tp_score_join_kernel" not in name:
+            continue
+        x4 = sum(1 for ln in lines if re.search(r"buffer_load_dwordx4 .*sc0 sc1", ln))
+        wide = sum(1 for ln in lines if re.search(r"(global|buffer|flat)_load_(dwordx2|dwordx3) .*sc0 sc1", ln))
+        lds = int(meta.get(name, {}).get("group_segment_fixed_size", "0"))
+        priv = int(meta.get(name, {}).get("private_segment_fixed_size", "0"))
+        report.append((name, x4, lds))
+        if x4 == 0:
+            errors.append(f"{name}: no 16-byte system-scope load found")
+        if wide:
+            errors.append(f"{name}: {wide} system-scope loads of 8 / 12 bytes (a record is one 16-byte load)")
+        if any("v_readfirstlane" in ln for ln in lines):
+            errors.append(f"{name}: waterfall loop around a buffer load (descriptor not provably wave-uniform)")
+        if priv or any(re.match(r"\s*scratch_", ln) for ln in lines):
+            errors.append(f"{name}: private segment of {priv} bytes / scratch accesses")
+        if lds != 3 * 16 * 16 * 4:
+            errors.append(f"{name}: {lds} bytes of LDS, the shared fold uses {3 * 16 * 16 * 4}")
+    if not report:
+        errors.append("tp_score_join_kernel not found")
+    return report, errors
+
+
 def main():
     bad = []
     rep, err = check_gemm8()
@@ -357,6 +387,10 @@ def main():
     rep, err = check_tp_pull()
     for name, x4, x2 in rep:
         print(f"tp     {name[:90]:90s} sc0 sc1 loads: dwordx4 {x4}  dwordx2 {x2}")
+    bad += err
+    rep, err = check_tp_score_join()
+    for name, x4, lds in rep:
+        print(f"tp     {name[:90]:90s} sc0 sc1 loads: dwordx4 {x4}  LDS {lds} B")
     bad += err
     for e in bad:
         print("ERROR:", e)

@@ -9,11 +9,26 @@ events, interleaved in one process on one GPU:
     python tools/score_bench.py [--rounds 12] [--out profiles/score_bench.txt]
 
 Each round times (a), (b), (c) once, in an order that rotates from round to round; medians and the min-max spread over the
-rounds are reported, plus the per-round ratio (c)/(a).  Weights are synthetic (synth.synthetic_state_dict, one block)."""
+rounds are reported, plus the per-round ratio (c)/(a).  Weights are synthetic (synth.synthetic_state_dict, one block).
+
+    python tools/score_bench.py --tp 2 [--out profiles/score_tp_bench.txt]
+
+--tp k: a FUNCTIONAL rig, not a scaling measurement.  The k ranks of a tensor-parallel group are handles of this process on ONE
+device (mmada_comm_connect_local, pull transport): they share its compute units and no link is involved.  Timed, interleaved:
+
+  (c)  fused, one rank     mmada_head_logprobs on a plain TP = 1 model
+  (t)  fused, k ranks      the vocabulary-parallel call on every rank of the group, all enqueued before the window closes: the
+                           SUMMED device time of the k ranks (k tile-range GEMMs + k hand-offs per round + k joins of every row)
+  (h)  one TP rank, torch  head_rows + torch log_softmax + gather on rank 0 of the group (what a TP rank could do before)
+
+(t) / (c) is what the split and the k joins cost on top of the one-rank call; on k devices each rank's share runs in parallel."""
 import argparse
 import os
 import statistics
 import sys
+
+if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 24:
+    os.environ["GPU_MAX_HW_QUEUES"] = "24"   # --tp: every rank's compute and exchange stream needs a hardware queue of its own
 
 import torch
 
@@ -23,12 +38,122 @@ sys.path.insert(0, ROOT)
 from mmada_parallel_amd import LLaDAForMultiModalGeneration, synth  # noqa: E402
 
 
+def tp_rig(cfg, sd, k, max_rows, dev):
+    """The k ranks of a tensor-parallel group as handles of this process, one stream each, pull transport."""
+    import ctypes as C
+
+    from mmada_parallel_amd import abi
+
+    ranks = [LLaDAForMultiModalGeneration.from_state_dict(synth.full_config(cfg), sd, device=dev, tp_rank=r, tp_size=k, max_batch=2)
+             for r in range(k)]
+    lib = ranks[0]._lib
+    for m in ranks:
+        abi.check(lib.mmada_comm_create(m._handle, max_rows, None), "comm_create")
+        m._comm_rows = max_rows
+    arr = (C.c_void_p * k)(*[m._handle.value for m in ranks])
+    for m in ranks:
+        abi.check(lib.mmada_comm_connect_local(m._handle, arr), "connect_local")
+        m._comm_in_library, m.tp_collective = True, "pull"
+    return ranks, [torch.cuda.Stream(device=dev) for _ in range(k)]
+
+
+def on_every_rank(ranks, streams, fn):
+    """fn(rank) enqueued on every rank's stream, joined to the current stream; no host synchronisation."""
+    cur = torch.cuda.current_stream()
+    out = []
+    for m, s in zip(ranks, streams):
+        s.wait_stream(cur)
+        with torch.cuda.stream(s):
+            out.append(fn(m))
+    for s in streams:
+        cur.wait_stream(s)
+    return out
+
+
+def main_tp(args):
+    dev, k = "cuda:0", args.tp
+    cfg = dict(synth.CFG_8B, n_layers=1)
+    sd = synth.synthetic_state_dict(cfg, seed=3, device=dev)
+    L = 2438
+    plain = LLaDAForMultiModalGeneration.from_state_dict(synth.full_config(cfg), sd, device=dev, max_batch=2)
+    ranks, streams = tp_rig(cfg, sd, k, 2 * ((L + 7) // 8 * 8), dev)
+    del sd
+    V = plain.vocab
+    lines = [f"score_bench --tp {k}: FUNCTIONAL RIG: {k} ranks as handles of one process on ONE {torch.cuda.get_device_name(0)} (pull transport, "
+             f"no link involved); d = {cfg['d_model']}, V = {V}, {args.rounds} rounds x {args.reps} calls, device events, ms per call"]
+    for B in (1, 2):
+        R = B * L
+        g = torch.Generator().manual_seed(5 + B)
+        ids = torch.randint(0, 126000, (B, L), generator=g).to(dev)
+        targets = torch.randint(0, V, (R,), generator=g).to(dev)
+        rows = torch.arange(R, dtype=torch.int32, device=dev)
+        plain.forward_body(ids)
+        on_every_rank(ranks, streams, lambda m: m.forward_body(ids))
+        torch.cuda.synchronize()
+        logits = torch.empty((R, V), dtype=torch.bfloat16, device=dev)
+
+        def run_c():
+            return plain.token_logprobs(rows, targets)
+
+        def run_t():
+            return on_every_rank(ranks, streams, lambda m: m.token_logprobs(rows, targets))
+
+        def run_h():
+            ranks[0].head_rows(rows, 0, V, out=logits)
+            return torch.log_softmax(logits.float(), -1).gather(1, targets[:, None])[:, 0]
+
+        fns = {"c": run_c, "t": run_t, "h": run_h}
+        got, ref = run_t(), run_h()
+        torch.cuda.synchronize()
+        assert all(torch.equal(x, got[0]) for x in got), "the ranks disagree"
+        for m in ranks:
+            assert m.comm_status()["error"] == 0, m.comm_status()
+        worst = float((ref - got[0]).abs().max())
+        for f in fns.values():
+            f()
+        torch.cuda.synchronize()
+        times = {n: [] for n in fns}
+        order = ["c", "t", "h"]
+        for r in range(args.rounds):
+            for n in order[r % 3:] + order[:r % 3]:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.reps):
+                    fns[n]()
+                e1.record()
+                e1.synchronize()
+                times[n].append(e0.elapsed_time(e1) / args.reps)
+        for m in ranks:
+            assert m.comm_status()["error"] == 0, m.comm_status()
+        med = {n: statistics.median(v) for n, v in times.items()}
+        ratio = [t / c for c, t in zip(times["c"], times["t"])]
+        lines.append(f"R = {R} (B = {B}, L = {L}); ranks bit-identical; max |fused TP - torch on the same rank's logits| log-probability {worst:.2e}")
+        names = {"c": "(c) fused, one rank (TP = 1 model)", "t": f"(t) fused, {k} ranks, summed device time", "h": "(h) one TP rank: head_rows + torch"}
+        for n in order:
+            lines.append(f"  {names[n]:42s} median {med[n]:8.3f}  min {min(times[n]):8.3f}  max {max(times[n]):8.3f}")
+        lines.append(f"  (t) / (c): median of rounds {statistics.median(ratio):.4f}  min {min(ratio):.4f}  max {max(ratio):.4f};   "
+                     f"(t) / {k} / (h): {med['t'] / k / med['h']:.4f} (a rank's share against what it could do before)")
+        del logits
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=12)
     ap.add_argument("--reps", type=int, default=4, help="calls per timed window")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "score_bench.txt"))
+    ap.add_argument("--tp", type=int, default=0, help="k > 1: the functional tensor-parallel rig (k ranks on one device)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "score_tp_bench.txt" if args.tp else "score_bench.txt")
+    if args.tp:
+        if args.tp not in (2, 4, 8):
+            ap.error("--tp must be 2, 4 or 8")
+        return main_tp(args)
     dev = "cuda:0"
     cfg = dict(synth.CFG_8B, n_layers=1)
     sd = synth.synthetic_state_dict(cfg, seed=3, device=dev)
