@@ -69,7 +69,7 @@ def check_tp_exchange(model):
     """A hand-off of the tensor-parallel pull transport that timed out (a lost or stalled peer) sets a sticky device flag
     and the ranks run on unsynchronised; nothing else would report it.  Called where the sampler synchronises anyway
     (the read-out of the final ids): raises instead of returning an image computed from stale partial sums."""
-    if getattr(model, "_comm_in_library", False) and hasattr(model, "comm_status"):
+    if model._comm_in_library:
         st = model.comm_status()
         if st["mode"] == "no-exchange diagnostic":
             raise abi.MmadaError("tensor-parallel exchange: the no-exchange diagnostic (mmada_comm_set_mode 3) is still on; "
@@ -200,8 +200,7 @@ def _ti2ti_steps(
     # ---- every buffer a step touches exists before the loop (fixed addresses: a step can be captured and replayed) ----
     # That includes the library's activation workspace: an image step's unconditional pair is a 2B forward, and a workspace
     # that grows THEN would leave an already captured text-step graph pointing into the freed allocation.
-    if hasattr(model, "_ensure_ws"):
-        model._ensure_ws(2 * B if need_uncond else B, L)
+    model._ensure_ws(2 * B if need_uncond else B, L)
     CBs = codebook_size
     k_cur = torch.zeros(B, dtype=torch.int32, device=device)
     mlen_cur = torch.zeros(1, dtype=torch.int32, device=device)
@@ -284,7 +283,7 @@ def _ti2ti_steps(
     graph = (bool(graph) and temperature == 0 and text_temperature == 0 and remasking == 'low_confidence'
              and model.graph_capturable())  # a replayed step would replay its random draws
     graphs, seen = {}, set()
-    ws_epoch = getattr(model, "_ws_epoch", 0)
+    ws_epoch = model._ws_epoch
     side = torch.cuda.Stream(device=device) if graph else None
     if graph:  # the legacy default stream cannot be captured: the loop runs on a side stream, ordered after the caller's
         side.wait_stream(torch.cuda.current_stream(device))
@@ -303,13 +302,13 @@ def _ti2ti_steps(
                     # ahead of the step's launches
                     noise_buf.copy_(rng.randn((B, N), torch.bfloat16, device, generator))
                 key = (is_img, need_text)
-                if graph and graphs and getattr(model, "_ws_epoch", 0) != ws_epoch:
+                if graph and graphs and model._ws_epoch != ws_epoch:
                     # the workspace moved after all (a foreign forward in between): captured pointers are stale
                     for g_old in graphs.values():
                         lib.mmada_graph_destroy(g_old)
                     graphs.clear()
                     seen.clear()
-                ws_epoch = getattr(model, "_ws_epoch", 0)
+                ws_epoch = model._ws_epoch
                 if graph and key in graphs:
                     abi.check(lib.mmada_graph_launch(graphs[key], abi.stream_ptr()), "mmada_graph_launch")
                     model.graph_replays += 1

@@ -14,12 +14,14 @@ from __future__ import annotations
 import ctypes as C
 import json
 import os
+from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Dict, Optional
 
 import torch
 
 from . import abi
+from .tp_link import TpLink, TpLinkMixin
 
 _SUPPORTED = dict(block_type="llama", activation_type="silu", layer_norm_type="rms")
 # what the reference's ModelConfig assumes for a key that is absent from config.json (model/configuration_llada.py:147-317):
@@ -152,8 +154,51 @@ def loss_regions(unscaled_loss: torch.Tensor, input_ids: torch.Tensor, labels: t
     return interleave_loss, text_loss, image_loss
 
 
-class LLaDAForMultiModalGeneration:
-    """MI355X-native drop-in for the reference class of the same name (inference and scoring; no backward pass)."""
+@dataclass
+class _Lane:
+    """An activation context of the library with its workspace: lane 0 is the model's handle, lane 1 a clone over the same weights."""
+    handle: C.c_void_p
+    ws: Optional[torch.Tensor] = None
+    ws_bytes: int = 0   # bytes registered with the library (the tensor is padded for alignment)
+
+
+@dataclass
+class _Resident:
+    """What forward_body left in the lanes: None after a cached forward."""
+    shape: Optional[tuple] = None      # (B, L)
+    split: Optional[int] = None        # B0: lane 0 holds sequences [0, B0), lane 1 the rest; None = everything in lane 0
+    consumed: Optional[tuple] = None   # the row window forward_body(consumed=...) declared
+
+
+def equal_cut(n_rows: int, B: int, B0: int) -> int:
+    """head_rows' way to find where lane 1's rows begin: the same number of rows per batch element — host arithmetic only."""
+    if n_rows % B:
+        raise ValueError("head_rows on a micro-batched forward needs an equal row count per batch element")
+    return B0 * (n_rows // B)
+
+
+def counted_cut(rows: torch.Tensor, base: int) -> int:
+    """token_logprobs' way: count the rows below `base` = B0 * L (any count per batch element; synchronises the host)."""
+    cut = int((rows < base).sum())
+    if cut and cut < rows.numel() and not bool((rows[:cut] < base).all()):
+        raise ValueError("token_logprobs on a micro-batched forward needs batch-major rows")
+    return cut
+
+
+def lane_calls(handles, n: int, cut: Optional[int], rows: Optional[torch.Tensor] = None, base: int = 0):
+    """The per-lane calls of a read over `n` batch-major items: [(handle, lo, hi, rows of that lane)], [lo, hi) being the lane's
+    share of the items and of the output.  cut None: lane 0 holds everything and `rows` passes through untouched.  Otherwise items
+    [cut, n) live in lane 1, whose rows are re-based by `base` = B0 * L: the second micro-batch indexes its own batch from 0."""
+    if cut is None:
+        return [(handles[0], 0, n, rows)]
+    if rows is None:
+        return [(handles[0], 0, cut, None), (handles[1], cut, n, None)]
+    return [(handles[0], 0, cut, rows[:cut]), (handles[1], cut, n, (rows[cut:] - base).contiguous())]
+
+
+class LLaDAForMultiModalGeneration(TpLinkMixin):
+    """MI355X-native drop-in for the reference class of the same name (inference and scoring; no backward pass).  The
+    tensor-parallel link (init_tp_comm, comm_status, the probes, ...) is tp_link.TpLinkMixin."""
 
     MASK_TOKEN = 126336
 
@@ -171,14 +216,12 @@ class LLaDAForMultiModalGeneration:
         self.tp_rank, self.tp_size = tp_rank, tp_size
         self._lib = abi.lib()
         self._handle = C.c_void_p()
-        self._ws = None
-        self._ws1 = None
-        self._ws_bytes = [0, 0]  # bytes registered with the library per activation context
+        self._lanes = [_Lane(self._handle)]  # lane 1 joins on first use (_lane)
+        self._resident = _Resident()
         self._ws_epoch = 0       # bumped whenever a workspace is (re)allocated: captured step graphs hold its addresses
         self.graph_replays, self.graph_nodes = 0, {}  # hipGraph step replays issued / nodes per captured step kind
-        self._comm_in_library, self._comm_rows, self.tp_collective = False, 0, None
-        self._handle1 = None
-        self._split = None
+        self._link = TpLink()
+        self._cache, self.use_cache = {}, False   # dLLM cache slots by `cat` / the blocks' use_cache flag (caching())
         self.n_kv_heads = effective_n_kv_heads(config)
         self.vocab = config.get("embedding_size") or config.vocab_size
         self.mlp_hidden = config.get("mlp_hidden_size") or config.ref("mlp_ratio") * config.d_model
@@ -259,29 +302,36 @@ class LLaDAForMultiModalGeneration:
         return cls(config, _Lazy(), **kw)
 
     # ---- workspace ------------------------------------------------------------------------------------------------
-    def _ensure_ws(self, B: int, L: int, lane: int = 0) -> None:
-        h = self._lane_handle(lane)
-        need = self._lib.mmada_workspace_bytes(h, B, L)
-        if need > self._ws_bytes[lane]:  # compare with what the LIBRARY was given, not with the padded tensor
-            grow = max(need, self._lib.mmada_workspace_bytes(h, max(B, self.max_batch), L))
-            ws = torch.empty(grow + 256, dtype=torch.uint8, device=self.device)
-            base = (ws.data_ptr() + 255) // 256 * 256
-            abi.check(self._lib.mmada_set_workspace(h, base, grow), "mmada_set_workspace")
-            self._ws_bytes[lane] = grow
-            self._ws_epoch += 1
-            if lane == 0:
-                self._ws = ws
-            else:
-                self._ws1 = ws
+    def _lane(self, lane: int) -> _Lane:
+        if lane == len(self._lanes):   # the second activation context over the same weights
+            h = C.c_void_p()
+            abi.check(self._lib.mmada_clone_shared(self._handle, C.byref(h)), "mmada_clone_shared")
+            self._lanes.append(_Lane(h))
+        return self._lanes[lane]
 
     def _lane_handle(self, lane: int):
-        if lane == 0:
-            return self._handle
-        if getattr(self, "_handle1", None) is None:
-            self._handle1 = C.c_void_p()
-            self._ws1 = None
-            abi.check(self._lib.mmada_clone_shared(self._handle, C.byref(self._handle1)), "mmada_clone_shared")
-        return self._handle1
+        return self._lane(lane).handle
+
+    def _ensure_ws(self, B: int, L: int, lane: int = 0) -> None:
+        ln = self._lane(lane)
+        need = self._lib.mmada_workspace_bytes(ln.handle, B, L)
+        if need > ln.ws_bytes:  # compare with what the LIBRARY was given, not with the padded tensor
+            grow = max(need, self._lib.mmada_workspace_bytes(ln.handle, max(B, self.max_batch), L))
+            ws = torch.empty(grow + 256, dtype=torch.uint8, device=self.device)
+            base = (ws.data_ptr() + 255) // 256 * 256
+            abi.check(self._lib.mmada_set_workspace(ln.handle, base, grow), "mmada_set_workspace")
+            ln.ws, ln.ws_bytes = ws, grow
+            self._ws_epoch += 1
+
+    # the resident forward, as the tests and tools spell it.  Assigning _shape declares a plain forward of that shape resident
+    # in lane 0 (what a caller that drives mmada_embed itself has to say before it reads the stream).
+    _ws_bytes = property(lambda self: [ln.ws_bytes for ln in self._lanes])
+    _shape = property(lambda self: self._resident.shape, lambda self, shape: setattr(self, "_resident", _Resident(shape)))
+    _split = property(lambda self: self._resident.split, lambda self, split: setattr(self._resident, "split", split))
+
+    def _lane_calls(self, n: int, cut: Optional[int], rows: Optional[torch.Tensor] = None):
+        res = self._resident
+        return lane_calls([ln.handle for ln in self._lanes], n, cut, rows, 0 if cut is None else res.split * res.shape[1])
 
     # ---- forward ---------------------------------------------------------------------------------------------------
     def forward_body(self, input_ids: torch.Tensor, consumed: Optional[tuple] = None) -> None:
@@ -300,11 +350,10 @@ class LLaDAForMultiModalGeneration:
         st = abi.stream_ptr()
         in_lib = self.tp_size > 1 and self._comm_in_library
         microbatch = B >= 2 and not in_lib and (self.tp_size > 1 or os.environ.get("MMADA_MICROBATCH") == "1")
-        self._split = None
         lo, hi = (int(consumed[0]), int(consumed[1])) if consumed is not None else (0, 0)
         if consumed is not None and not 0 <= lo < hi <= L:
             raise ValueError(f"consumed rows {consumed} outside [0, {L})")
-        self._consumed = (lo, hi) if consumed is not None else None
+        self._resident = _Resident((B, L), (B + 1) // 2 if microbatch else None, (lo, hi) if consumed is not None else None)
         for lane in ((0, 1) if microbatch else (0,)):
             abi.check(self._lib.mmada_set_consumed_rows(self._lane_handle(lane), lo, hi), "mmada_set_consumed_rows")
         if not microbatch:
@@ -326,7 +375,7 @@ class LLaDAForMultiModalGeneration:
             import torch.distributed as dist
 
             reduce = dist.is_available() and dist.is_initialized()
-            B0 = (B + 1) // 2
+            B0 = self._resident.split
             parts = [ids[:B0].contiguous(), ids[B0:].contiguous()]
             handles = [self._lane_handle(0), self._lane_handle(1)]
             for j in (0, 1):
@@ -345,17 +394,14 @@ class LLaDAForMultiModalGeneration:
             for j in (0, 1):
                 if pending[j] is not None:
                     pending[j].wait()
-            self._split = B0
-        self._shape = (B, L)
 
     def _stream_view(self, lane: int = 0) -> torch.Tensor:
         """Torch view of the library's current residual-stream buffer (inside our workspace tensor)."""
-        h = self._lane_handle(lane)
-        ws = self._ws if lane == 0 else self._ws1
-        p = self._lib.mmada_stream_ptr(h)
-        n = self._lib.mmada_stream_bytes(h)
-        off = p - ws.data_ptr()
-        return ws[off:off + n].view(torch.bfloat16)
+        ln = self._lane(lane)
+        p = self._lib.mmada_stream_ptr(ln.handle)
+        n = self._lib.mmada_stream_bytes(ln.handle)
+        off = p - ln.ws.data_ptr()
+        return ln.ws[off:off + n].view(torch.bfloat16)
 
     def head_rows(self, rows: torch.Tensor, col_begin: int, col_end: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """logits[r] = lm_head[col_begin:col_end] · ln_f(x[rows[r]]), rows = b*L + l (int32, device).
@@ -363,35 +409,26 @@ class LLaDAForMultiModalGeneration:
         `rows` must be batch-major with the same number of rows per batch element (what generate_ti2ti builds).
         `out` (bf16 [R, col_end - col_begin], contiguous): write there instead of allocating (fixed address: capturable)."""
         rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
-        if os.environ.get("MMADA_CHECK_ROWS") == "1" and getattr(self, "_consumed", None) is not None and rows.numel():
-            l = rows % self._shape[1]  # debug aid (forces a device sync): rows must lie inside the declared window
-            assert int(l.min()) >= self._consumed[0] and int(l.max()) < self._consumed[1], "head_rows outside forward_body(consumed=...)"
+        res = self._resident
+        if os.environ.get("MMADA_CHECK_ROWS") == "1" and res.consumed is not None and rows.numel():
+            l = rows % res.shape[1]  # debug aid (forces a device sync): rows must lie inside the declared window
+            assert int(l.min()) >= res.consumed[0] and int(l.max()) < res.consumed[1], "head_rows outside forward_body(consumed=...)"
         if out is None:
             out = torch.empty((rows.numel(), col_end - col_begin), dtype=torch.bfloat16, device=self.device)
         elif out.shape != (rows.numel(), col_end - col_begin) or out.dtype != torch.bfloat16 or not out.is_contiguous():
             raise ValueError("head_rows(out=...): need a contiguous bf16 [rows, col_end - col_begin] tensor")
         st = abi.stream_ptr()
-        if getattr(self, "_split", None) is None:
-            abi.check(self._lib.mmada_head_rows(self._handle, rows.data_ptr(), rows.numel(), col_begin, col_end,
-                                                out.data_ptr(), st), "mmada_head_rows")
-            return out
-        B, L = self._shape
-        if rows.numel() % B:
-            raise ValueError("head_rows on a micro-batched forward needs an equal row count per batch element")
-        per_b, B0 = rows.numel() // B, self._split
-        cut = B0 * per_b
-        r1 = (rows[cut:] - B0 * L).contiguous()  # second micro-batch indexes its own batch from 0
-        abi.check(self._lib.mmada_head_rows(self._handle, rows.data_ptr(), cut, col_begin, col_end, out.data_ptr(), st),
-                  "mmada_head_rows")
-        abi.check(self._lib.mmada_head_rows(self._handle1, r1.data_ptr(), rows.numel() - cut, col_begin, col_end,
-                                            out[cut:].data_ptr(), st), "mmada_head_rows")
+        cut = None if res.split is None else equal_cut(rows.numel(), res.shape[0], res.split)
+        for handle, lo, hi, r in self._lane_calls(rows.numel(), cut, rows):
+            abi.check(self._lib.mmada_head_rows(handle, r.data_ptr(), hi - lo, col_begin, col_end,
+                                                out.data_ptr() if lo == 0 else out[lo:].data_ptr(), st), "mmada_head_rows")
         return out
 
     _TP_SCORE = ("scoring under tensor parallelism needs the library's exchange (init_tp_comm): a vocabulary-parallel score is the "
                  "same records exchanged as in mmada_text_select_tp, which the host all-reduce fallback does not carry")
 
     def _refuse_tp_score(self):
-        if self.tp_size != 1 and not getattr(self, "_comm_in_library", False):
+        if self.tp_size != 1 and not self._comm_in_library:
             raise NotImplementedError(self._TP_SCORE)
 
     def token_logprobs(self, rows: torch.Tensor, targets: torch.Tensor, col_begin: int = 0, col_end: Optional[int] = None,
@@ -415,25 +452,13 @@ class LLaDAForMultiModalGeneration:
         lp = torch.empty(R, dtype=torch.float32, device=self.device)
         stats = (torch.empty(R, dtype=torch.float32, device=self.device), torch.empty(R, dtype=torch.int32, device=self.device),
                  torch.empty(R, dtype=torch.float32, device=self.device)) if return_stats else None
-        st = abi.stream_ptr()
-
-        def call(handle, lo, hi, row_t):
-            if hi <= lo:
-                return
-            ptr = lambda t_: t_[lo:hi].data_ptr()   # noqa: E731
-            abi.check(self._lib.mmada_head_logprobs(handle, row_t.data_ptr(), hi - lo, col_begin, col_end, ptr(targets), ptr(lp),
-                                                    ptr(stats[0]) if stats else None, ptr(stats[1]) if stats else None,
-                                                    ptr(stats[2]) if stats else None, st), "mmada_head_logprobs")
-
-        if getattr(self, "_split", None) is None:
-            call(self._handle, 0, R, rows)
-        else:   # micro-batched forward: the second activation context indexes its own batch from 0 (as head_rows does)
-            B0, L = self._split, self._shape[1]
-            cut = int((rows < B0 * L).sum())
-            if cut and cut < R and not bool((rows[:cut] < B0 * L).all()):
-                raise ValueError("token_logprobs on a micro-batched forward needs batch-major rows")
-            call(self._handle, 0, cut, rows[:cut].contiguous())
-            call(self._handle1, cut, R, (rows[cut:] - B0 * L).contiguous())
+        res = self._resident   # micro-batched forward: any row count per batch element, so the cut is counted
+        cut = None if res.split is None else counted_cut(rows, res.split * res.shape[1])
+        for handle, lo, hi, row_t in self._lane_calls(R, cut, rows):
+            if hi > lo:
+                ptrs = [t_[lo:hi].data_ptr() for t_ in (targets, lp) + (stats or ())] + [None] * (0 if stats else 3)
+                abi.check(self._lib.mmada_head_logprobs(handle, row_t.data_ptr(), hi - lo, col_begin, col_end, *ptrs,
+                                                        abi.stream_ptr()), "mmada_head_logprobs")
         return (lp, *stats) if return_stats else lp
 
     def score(self, input_ids: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
@@ -463,12 +488,8 @@ class LLaDAForMultiModalGeneration:
         """Residual stream after the last block, [B, L, d] (parity tap)."""
         B, L = self._shape
         out = torch.empty((B, L, self.config.d_model), dtype=torch.bfloat16, device=self.device)
-        st = abi.stream_ptr()
-        if getattr(self, "_split", None) is None:
-            abi.check(self._lib.mmada_read_stream(self._handle, out.data_ptr(), st), "mmada_read_stream")
-        else:
-            abi.check(self._lib.mmada_read_stream(self._handle, out.data_ptr(), st), "mmada_read_stream")
-            abi.check(self._lib.mmada_read_stream(self._handle1, out[self._split:].data_ptr(), st), "mmada_read_stream")
+        for handle, b0, _, _ in self._lane_calls(B, self._resident.split):   # the items are the batch's sequences
+            abi.check(self._lib.mmada_read_stream(handle, out[b0:].data_ptr(), abi.stream_ptr()), "mmada_read_stream")
         return out
 
     def debug_buffer(self, which: int) -> torch.Tensor:
@@ -484,11 +505,19 @@ class LLaDAForMultiModalGeneration:
         n = 2
         for v in shape:
             n *= v
-        off = p.value - self._ws.data_ptr()
-        t = self._ws[off:off + n].view(torch.bfloat16).view(*shape)
+        ws = self._lanes[0].ws
+        off = p.value - ws.data_ptr()
+        t = ws[off:off + n].view(torch.bfloat16).view(*shape)
         if which == 3:  # undo the [0,4,1,5,2,6,3,7] chunk order of every 32-key block (csrc/common.h vt_key_pos)
             t = t.reshape(B, hkv, 128, lkv.value // 32, 8, 4)[..., [0, 2, 4, 6, 1, 3, 5, 7], :].reshape(B, hkv, 128, lkv.value)
         return t
+
+    def _forward_logits(self, input_ids) -> torch.Tensor:
+        """forward_body + the head over every row and the whole vocabulary: [B, L, vocab] logits."""
+        self.forward_body(input_ids)
+        B, L = self._shape
+        rows = torch.arange(B * L, dtype=torch.int32, device=self.device)
+        return self.head_rows(rows, 0, self.vocab).view(B, L, self.vocab)
 
     def _forward_loss(self, input_ids, labels, return_dict, compute_separate_losses, t):
         """forward(infer=False): the reference's loss contract (model/modeling_xllmx_dimoo.py:56-194), see forward()."""
@@ -498,16 +527,9 @@ class LLaDAForMultiModalGeneration:
             # loud refusal it has always been (tests/test_reference_contract.py pins it)
             raise NotImplementedError("forward(infer=False) needs labels (the loss); forward(infer=True) returns the logits")
         ids, lab, lengths = pad_id_lists(input_ids, labels)
-
-        def all_logits():
-            self.forward_body(ids)
-            B, L = self._shape
-            rows = torch.arange(B * L, dtype=torch.int32, device=self.device)
-            return self.head_rows(rows, 0, self.vocab).view(B, L, self.vocab)
-
         lab = lab.to(self.device)
         unscaled = self.score(ids, lab).to(torch.bfloat16)   # the reference's per-token loss has the logits' dtype
-        logits = all_logits() if return_dict else None
+        logits = self._forward_logits(ids) if return_dict else None
         if not compute_separate_losses:
             valid = lab != IGNORE_INDEX
             loss = unscaled[valid].mean() if bool(valid.any()) else torch.tensor(0.0, device=self.device)
@@ -556,289 +578,9 @@ class LLaDAForMultiModalGeneration:
             raise NotImplementedError("the dLLM cache under tensor parallelism needs the library's exchange (init_tp_comm); "
                                       "the host all-reduce fallback recomputes every row")
         # host all-reduce fallback + use_cache without a mask: every row is recomputed and nothing is kept (same logits)
-        self.forward_body(input_ids)
-        B, L = self._shape
-        rows = torch.arange(B * L, dtype=torch.int32, device=self.device)
-        logits = self.head_rows(rows, 0, self.vocab).view(B, L, self.vocab)
-        return CausalLMOutputLite(logits=logits)
+        return CausalLMOutputLite(logits=self._forward_logits(input_ids))
 
     __call__ = forward
-
-    # ---- tensor-parallel transport (csrc/tp_comm.hip) ---------------------------------------------------------------
-    class _DevView:
-        """Zero-copy torch view of library-owned device memory (__cuda_array_interface__)."""
-
-        def __init__(self, ptr, n_u16):
-            self.__cuda_array_interface__ = {"shape": (n_u16,), "typestr": "<u2", "data": (ptr, False), "version": 2}
-
-    def _part_view(self, rows: int) -> torch.Tensor:
-        ptr = self._lib.mmada_comm_part_ptr(self._handle)
-        n = rows * self.config.d_model
-        return torch.as_tensor(self._DevView(ptr, n), device=self.device).view(torch.bfloat16).view(rows, self.config.d_model)
-
-    def comm_status(self):
-        mode, err, fine = C.c_int(), C.c_int(), C.c_int()
-        abi.check(self._lib.mmada_comm_status(self._handle, C.byref(mode), C.byref(err), C.byref(fine), abi.stream_ptr()),
-                  "mmada_comm_status")
-        return {"mode": {0: "none", 1: "pull", 2: "rccl", 3: "no-exchange diagnostic", 4: "copy"}[mode.value], "error": err.value, "finegrained_counters": bool(fine.value & 1),
-                "finegrained_buffers": bool(fine.value & 2)}
-
-    def comm_selftest(self, iters: int = 3, L: int = 96) -> bool:
-        """`iters` exchanges over a small carve with known partials (different data every round, so a stale cache line
-        cannot pass): every row of the all-gathered, normalised result must equal the locally computed expectation bit for
-        bit.  Every rank must call it; returns this rank's verdict."""
-        d, tp, r = self.config.d_model, self.tp_size, self.tp_rank
-        B = 2
-        ids = (torch.arange(B * L, device=self.device).view(B, L) * 7 + 3) % 1000
-        Lp = (L + 7) // 8 * 8
-        M = B * Lp
-        self._ensure_ws(B, L)
-        w = torch.ones(d, dtype=torch.bfloat16, device=self.device)
-        part = self._part_view(M)
-        st = abi.stream_ptr()
-        ok = True
-        col = torch.arange(d, device=self.device, dtype=torch.float32)[None, :]
-        row = torch.arange(M, device=self.device, dtype=torch.float32)[:, None]
-        for it in range(iters):
-            abi.check(self._lib.mmada_embed(self._handle, ids.data_ptr(), B, L, st), "mmada_embed")
-            self._shape, self._split = (B, L), None
-            x0 = self._stream_view().view(M, d).clone()
-
-            def pat(rank):  # small integers: exact in bf16, different per rank / row / column / round
-                return (((row * 3 + col * 5 + rank * 11 + it * 17) % 13) - 6.0) * (rank + 1)
-
-            part.copy_(pat(r).to(torch.bfloat16))
-            abi.check(self._lib.mmada_comm_exchange(self._handle, w.data_ptr(), st), "mmada_comm_exchange")
-            total = sum(pat(j).to(torch.bfloat16).float() for j in range(tp))
-            x_new = (x0.float() + total.to(torch.bfloat16).float()).to(torch.bfloat16)
-            want = torch.empty_like(x_new)
-            abi.check(self._lib.mmada_rmsnorm(x_new.data_ptr(), w.data_ptr(), want.data_ptr(), M, d,
-                                              float(self.config.ref("rms_norm_eps")), st), "mmada_rmsnorm")
-            got = self.debug_buffer(0).view(-1, d)[:M]
-            ok = ok and bool(torch.equal(got, want))
-        return ok and self.comm_status()["error"] == 0
-
-    def init_tp_comm(self, max_batch: int, max_len: int, group=None, transport: str = "auto") -> str:
-        """Connect the library's tensor-parallel exchange over the ranks of `group` (a torch.distributed group: control
-        plane only — handles / unique id are exchanged as objects; the data path never goes through torch).
-        transport: "pull" (mapped peer buffers, hipIpc), "copy" (the same mapped buffers, bytes moved by the copy engines),
-        "rccl", or "auto" = pull if it connects AND passes the self-test on every rank, else RCCL, else the host-issued
-        all-reduce of the segment API.  Returns what is in use.  MMADA_TP_EXCHANGE_CUS=n (a multiple of 8) additionally gives
-        the exchange stream n CUs of its own and masks the compute stream to the rest (mmada_comm_set_partition)."""
-        import torch.distributed as dist
-
-        lib = self._lib
-        rows = max_batch * ((max_len + 7) // 8 * 8)
-        nb = lib.mmada_comm_export_bytes()
-        buf = C.create_string_buffer(nb)
-        exported = lib.mmada_comm_create(self._handle, rows, buf) == 0
-        if not exported:
-            abi.check(lib.mmada_comm_create(self._handle, rows, None), "mmada_comm_create")
-        self._comm_rows = rows
-
-        def all_agree(flag: bool) -> bool:
-            got = [None] * self.tp_size
-            dist.all_gather_object(got, bool(flag), group=group)
-            return all(got)
-
-        chosen = None
-        if transport in ("auto", "pull", "copy"):
-            blobs = [None] * self.tp_size
-            dist.all_gather_object(blobs, buf.raw if exported else None, group=group)
-            ok = exported and all(b is not None for b in blobs)
-            if ok:
-                ok = lib.mmada_comm_connect_ipc(self._handle, b"".join(blobs)) == 0
-            ok = all_agree(ok)
-            if ok and transport == "copy":
-                ok = all_agree(lib.mmada_comm_set_mode(self._handle, 4) == 0)
-            if ok:
-                self._comm_in_library = True
-                lib.mmada_comm_set_timeout(self._handle, 3.0)   # a transport that cannot work is abandoned quickly
-                ok = all_agree(self.comm_selftest())
-                lib.mmada_comm_set_timeout(self._handle, 0.0)   # back to MMADA_TP_TIMEOUT_S; clears a sticky error
-            if ok:
-                chosen = "copy" if transport == "copy" else "pull"
-            elif transport in ("pull", "copy"):
-                raise abi.MmadaError("tensor-parallel pull transport failed to connect or failed its self-test: "
-                                     + (lib.mmada_last_error() or b"").decode())
-        if chosen is None and transport in ("auto", "rccl"):
-            backend_ok = dist.get_backend(group) == "nccl"  # one rank per device: RCCL refuses two ranks on one GPU
-            if all_agree(backend_ok):
-                path = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so").encode()
-                uid = C.create_string_buffer(128)
-                if self.tp_rank == 0:
-                    abi.check(lib.mmada_comm_unique_id(uid, path), "mmada_comm_unique_id")
-                box = [uid.raw]
-                dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
-                ok = lib.mmada_comm_connect_rccl(self._handle, box[0], path) == 0
-                if all_agree(ok):
-                    self._comm_in_library = True
-                    if all_agree(self.comm_selftest()):
-                        chosen = "rccl"
-            if chosen is None and transport == "rccl":
-                raise abi.MmadaError("tensor-parallel RCCL transport failed: " + (lib.mmada_last_error() or b"").decode())
-        if chosen is None:
-            self._comm_in_library = False
-            lib.mmada_comm_destroy(self._handle)
-            chosen = "host all-reduce (torch.distributed)"
-        self._rccl_also = False
-        if chosen in ("pull", "copy") and os.environ.get("MMADA_TP_PROBE_RCCL", "0") == "1":
-            # OPT-IN (bench.py sets it): one rank per device over RCCL as well, so that collective_probe() can time BOTH
-            # transports.  A production start does not pay a second communicator (init time, memory, one more thing that
-            # can fail or hang at start-up).
-            if all_agree(dist.get_backend(group) == "nccl"):
-                path = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so").encode()
-                uid = C.create_string_buffer(128)
-                uid_ok = self.tp_rank != 0 or lib.mmada_comm_unique_id(uid, path) == 0
-                box = [uid.raw if uid_ok else None]
-                dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
-                if box[0] is not None:
-                    try:
-                        ok = lib.mmada_comm_connect_rccl(self._handle, box[0], path) == 0   # leaves mode = RCCL
-                    finally:
-                        lib.mmada_comm_set_mode(self._handle, 4 if chosen == "copy" else 1)   # the forward keeps its transport
-                    self._rccl_also = all_agree(ok)
-        self.tp_collective = chosen
-        cus = int(os.environ.get("MMADA_TP_EXCHANGE_CUS", "0") or 0)
-        if cus and self._comm_in_library:
-            abi.check(lib.mmada_comm_set_partition(self._handle, cus), "mmada_comm_set_partition")
-        return chosen
-
-    def set_exchange_partition(self, exchange_cus: int) -> None:
-        """Give the exchange stream `exchange_cus` CUs of its own (0: none) — mmada_comm_set_partition."""
-        abi.check(self._lib.mmada_comm_set_partition(self._handle, int(exchange_cus)), "mmada_comm_set_partition")
-
-    def collective_probe(self, L: int, B: int = 1, iters: int = 10):
-        """Outside any timed region: one exchange (reduce-scatter + RMSNorm + all-gather of B*L rows x d bf16) timed alone,
-        so a scaling run also records what the fabric delivered for the message size the forward uses."""
-        if not self._comm_in_library:
-            return None
-        import time
-
-        ids = torch.zeros((B, L), dtype=torch.long, device=self.device)
-        self._ensure_ws(B, L)
-        st = abi.stream_ptr()
-        abi.check(self._lib.mmada_embed(self._handle, ids.data_ptr(), B, L, st), "mmada_embed")
-        w = torch.ones(self.config.d_model, dtype=torch.bfloat16, device=self.device)
-        for _ in range(3):
-            abi.check(self._lib.mmada_comm_exchange(self._handle, w.data_ptr(), st), "mmada_comm_exchange")
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(iters):
-            abi.check(self._lib.mmada_comm_exchange(self._handle, w.data_ptr(), st), "mmada_comm_exchange")
-        torch.cuda.synchronize()
-        ms = (time.perf_counter() - t0) / iters * 1e3
-        nbytes = B * ((L + 7) // 8 * 8) * self.config.d_model * 2
-        tp = self.tp_size
-        out = {"transport": self.tp_collective, "rows": B * L, "bytes": nbytes, "ms": ms,
-               "busbw_GBps": 2.0 * (tp - 1) / tp * nbytes / (ms * 1e-3) / 1e9, "exchanges_per_forward": 2 * self.config.n_layers,
-               "status": self.comm_status()}
-        # the other data path over the same mapped buffers, for comparison: OPT-IN (MMADA_TP_PROBE_COPY=1) — it exercises a
-        # transport the run did not select; a first multi-GPU session should ask for it explicitly
-        if self.tp_collective in ("pull", "copy") and os.environ.get("MMADA_TP_PROBE_COPY", "0") == "1":
-            other, mode_other, mode_back = ("copy", 4, 1) if self.tp_collective == "pull" else ("pull", 1, 4)
-            # a comparison only: a data path that fails HERE (first contact with real multi-GPU hardware) must not take the
-            # benchmark line of the transport in use with it — record the error and go on
-            err_in_use = out["status"]["error"]   # what the transport IN USE left behind: recorded above, never erased below
-            ok = 1
-            try:
-                abi.check(self._lib.mmada_comm_set_mode(self._handle, mode_other), "mmada_comm_set_mode")
-                for _ in range(3):
-                    abi.check(self._lib.mmada_comm_exchange(self._handle, w.data_ptr(), st), "mmada_comm_exchange")
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(iters):
-                    abi.check(self._lib.mmada_comm_exchange(self._handle, w.data_ptr(), st), "mmada_comm_exchange")
-                torch.cuda.synchronize()
-                ms3 = (time.perf_counter() - t0) / iters * 1e3
-                out[other] = {"ms": ms3, "busbw_GBps": 2.0 * (tp - 1) / tp * nbytes / (ms3 * 1e-3) / 1e9,
-                              "error_flag": self.comm_status()["error"]}
-                ok = int(out[other]["error_flag"] == 0)
-            except Exception as e:   # noqa: BLE001
-                out[other] = {"error": str(e)[:300]}
-                ok = 0
-            finally:
-                abi.check(self._lib.mmada_comm_set_mode(self._handle, mode_back), "mmada_comm_set_mode")
-                if err_in_use == 0:   # only a flag the COMPARISON raised is cleared; an earlier one stays for bench.py to report
-                    self._lib.mmada_comm_set_timeout(self._handle, 0.0)
-            # a rank that failed stopped issuing exchanges while its peers went on: agree on the outcome before anything else
-            # uses the group (the comparison's figure is only meaningful when every rank completed it)
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized():
-                flag = torch.tensor([ok], dtype=torch.int32, device=self.device)
-                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-                out[other]["all_ranks_ok"] = bool(int(flag.item()))
-        if getattr(self, "_rccl_also", False) and self.tp_collective in ("pull", "copy"):   # the same exchange over RCCL, for comparison
-            abi.check(self._lib.mmada_comm_set_mode(self._handle, 2), "mmada_comm_set_mode")
-            try:
-                for _ in range(3):
-                    abi.check(self._lib.mmada_comm_exchange(self._handle, w.data_ptr(), st), "mmada_comm_exchange")
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(iters):
-                    abi.check(self._lib.mmada_comm_exchange(self._handle, w.data_ptr(), st), "mmada_comm_exchange")
-                torch.cuda.synchronize()
-                ms2 = (time.perf_counter() - t0) / iters * 1e3
-                out["rccl"] = {"ms": ms2, "busbw_GBps": 2.0 * (tp - 1) / tp * nbytes / (ms2 * 1e-3) / 1e9}
-            finally:
-                abi.check(self._lib.mmada_comm_set_mode(self._handle, 4 if self.tp_collective == "copy" else 1), "mmada_comm_set_mode")
-        return out
-
-    def rccl_nranks(self) -> int:
-        """Ranks of the RCCL communicator the LIBRARY created (ncclCommCount), 0 when it holds none."""
-        return int(self._lib.mmada_comm_rccl_nranks(self._handle)) if self._comm_in_library or getattr(self, "_rccl_also", False) else 0
-
-    def exchange_exposure_probe(self, input_ids: torch.Tensor, reps: int = 3):
-        """Outside any timed region: wall time of one tensor-parallel forward with its exchanges and of the same forward
-        with the library's "no exchange" diagnostic (mmada_comm_set_mode 3: identical GEMM / attention / owner-side kernels,
-        no peer traffic, no hand-off; the values are wrong, only the time is used).  The difference is what the exchanges
-        cost the forward AFTER the two-chunk overlap: the exposed exchange time.  Every rank must call it."""
-        if not self._comm_in_library or self.tp_size == 1:
-            return None
-        import time
-
-        import torch.distributed as dist
-
-        real_mode = {"pull": 1, "rccl": 2, "copy": 4}[self.tp_collective]
-
-        def timed(mode):
-            abi.check(self._lib.mmada_comm_set_mode(self._handle, mode), "mmada_comm_set_mode")
-            ts = []
-            try:
-                for i in range(reps + 1):
-                    if dist.is_initialized():
-                        dist.barrier()
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    self.forward_body(input_ids)
-                    torch.cuda.synchronize()
-                    if i:   # the first call of a mode is a warm-up
-                        ts.append((time.perf_counter() - t0) * 1e3)
-            finally:
-                abi.check(self._lib.mmada_comm_set_mode(self._handle, real_mode), "mmada_comm_set_mode")
-            return sorted(ts)[len(ts) // 2]
-
-        with_x = timed(real_mode)
-        without = timed(3)
-        with_x2 = timed(real_mode)
-        ms = min(with_x, with_x2)
-        return {"forward_ms_with_exchange": ms, "forward_ms_no_exchange_diagnostic": without,
-                "exposed_exchange_ms_per_forward": ms - without, "exchanges_per_forward": 2 * self.config.n_layers,
-                "batch": int(input_ids.shape[0]), "what": "median wall time of a synchronised forward_body, real transport vs "
-                "mmada_comm_set_mode(3) (owner-side kernels on the rank's own partials only, no peer traffic)"}
-
-    def vocab_parallel_head(self) -> bool:
-        """True when the text step can run on vocabulary slices of the LM head (library transport connected)."""
-        return self._comm_in_library and os.environ.get("MMADA_TP_REPLICATED_HEAD") != "1"
-
-    def graph_capturable(self) -> bool:
-        """True when forward_body / head_rows issue only stream launches (no host-side collective): the sampler may then
-        capture a whole denoise step into one hipGraph (mmada_graph_*)."""
-        # RCCL's reduce-scatter / all-gather would be captured on a forked stream; whether every call it makes is
-        # capturable has never been exercised with more than one rank, so only the pull transport (plain kernels and
-        # device-memory counters) qualifies under tensor parallelism
-        return self.tp_size == 1 or (getattr(self, "_comm_in_library", False) and getattr(self, "tp_collective", None) in ("pull", "copy")
-                                     and self._lib.mmada_comm_partition(self._handle) == 0)   # a CU mask does not survive capture
 
     # ---- dLLM cache (model/modeling_llada.py:593-600,929-940,1244-1245,1406-1426) ----------------------------------------
     def caching(self, enable: bool = True):
@@ -850,14 +592,12 @@ class LLaDAForMultiModalGeneration:
 
     def empty_cache(self):
         """LLaDAModel.empty_cache (model/modeling_llada.py:1423-1426): drops every slot's keys / values / final rows."""
-        for ent in getattr(self, "_cache", {}).values():
+        for ent in self._cache.values():
             abi.check(self._lib.mmada_cache_bind(self._handle, ent.idx, None, 0, 0, 0, abi.stream_ptr()), "mmada_cache_bind")
         self._cache = {}
 
     def _cache_slot(self, cat, B: int, L: int, rebind_ok: bool):
-        from types import SimpleNamespace
-
-        cache = self.__dict__.setdefault("_cache", {})
+        cache = self._cache
         ent = cache.get(cat)
         if ent is not None and ent.shape == (B, L):
             return ent
@@ -905,13 +645,13 @@ class LLaDAForMultiModalGeneration:
             pos = m.nonzero()[:, 1].view(B, Tc).to(torch.int32).contiguous()
             ids_c = ids[m].view(B, Tc).contiguous()
             abi.check(self._lib.mmada_forward_cached(self._handle, ent.idx, ids_c.data_ptr(), pos.data_ptr(), B, L, Tc,
-                                                     int(bool(getattr(self, "use_cache", False))), st), "mmada_forward_cached")
-        self._shape, self._split, self._consumed = None, None, None  # no plain forward is resident any more
+                                                     int(self.use_cache), st), "mmada_forward_cached")
+        self._resident = _Resident()  # no plain forward is resident any more
 
     def cache_head_rows(self, cat, rows: torch.Tensor, col_begin: int, col_end: int,
                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Rows (b*L + l) x columns [col_begin, col_end) of logit_cache[cat] (model/modeling_llada.py:1406-1413)."""
-        ent = getattr(self, "_cache", {}).get(cat)
+        ent = self._cache.get(cat)
         if ent is None:
             raise KeyError(f"no cache {cat!r}")
         rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
@@ -931,11 +671,9 @@ class LLaDAForMultiModalGeneration:
 
     def __del__(self):
         try:
-            if getattr(self, "_handle1", None) is not None and self._handle1.value:
-                self._lib.mmada_destroy(self._handle1)
-                self._handle1 = None
-            if getattr(self, "_handle", None) and self._handle.value:
-                self._lib.mmada_destroy(self._handle)
-                self._handle = C.c_void_p()
+            for ln in reversed(self._lanes):
+                if ln.handle.value:
+                    self._lib.mmada_destroy(ln.handle)
+                    ln.handle.value = None
         except Exception:
             pass

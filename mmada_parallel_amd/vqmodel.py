@@ -58,7 +58,7 @@ class VQModel:
         self.device = torch.device(device if device is not None else "cuda:0")
         self.dtype = torch.float32
         self._lib = abi.lib()
-        self._ws = None
+        self._ws = self._dec = self._enc = self._last = None   # _last: encode()'s (latents, indices, version), see quantize()
         c = VqModelCfg()
         c.n_levels = len(cfg["block_out_channels"])
         if not 1 <= c.n_levels <= 8:
@@ -167,7 +167,7 @@ class VQModel:
     def quantize(self, latents: torch.Tensor):
         """VectorQuantizer.forward: (z_q, loss, (perplexity, min_encodings, min_encoding_indices)); the reference reads only
         [2][2] (utils/image_utils.py:168).  Indices are flat [B*h*w] like diffusers' (sane_index_shape=False)."""
-        last = getattr(self, "_last", None)
+        last = self._last
         B, D, hz, wz = latents.shape
         if last is not None and last[0] is latents and latents._version == last[2]:
             idx = last[1].reshape(-1)
@@ -203,7 +203,7 @@ class VQModel:
 
     def __del__(self):
         try:
-            for h in (getattr(self, "_dec", None), getattr(self, "_enc", None)):
+            for h in (self._dec, self._enc):
                 if h:
                     self._lib.mmada_vq_destroy(h)
             self._dec = self._enc = None

@@ -1,6 +1,7 @@
 """Shared test helpers (seeded inputs identical to oracle/gen_golden.py)."""
 import os
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -228,22 +229,16 @@ class FakeVq:
     value quantised to 0..63 (so token arithmetic and mask geometry can be checked without a GPU)."""
 
     def __init__(self):
-        from types import SimpleNamespace
-
         self.config = SimpleNamespace(block_out_channels=[1, 1], latent_channels=1)
         self.device = torch.device("cpu")
 
     def encode(self, x):
-        from types import SimpleNamespace
-
         return SimpleNamespace(latents=torch.nn.functional.avg_pool2d(x[:, :1], 2))
 
     def quantize(self, latents):
         return None, None, (None, None, (latents.reshape(-1) * 63).round().long())
 
     def decode(self, codes, force_not_quantize=False, shape=None):
-        from types import SimpleNamespace
-
         assert force_not_quantize and tuple(shape) == (codes.shape[0], codes.shape[1], codes.shape[2], 1)
         g = codes.float() / 63.0 * 1.2 - 0.1                               # leaves [0, 1] on both sides: the clip matters
         x = torch.stack([g, 1.0 - g, g * g], 1)
@@ -271,25 +266,13 @@ _TP_STREAMS = []
 
 def tp_group(cfg_base, sd, tp, max_rows, dev="cuda:0", transport="pull", exchange_cus=0):
     """The ranks of a tensor-parallel group as separate handles of ONE process, each on its own stream, connected with
-    mmada_comm_connect_local (tests/test_gpu_tp.py explains why this is the multi-device code path unchanged)."""
-    import ctypes as C
-
-    from mmada_parallel_amd import LLaDAForMultiModalGeneration, abi
+    connect_local_group (tests/test_gpu_tp.py explains why this is the multi-device code path unchanged)."""
+    from mmada_parallel_amd import LLaDAForMultiModalGeneration
+    from mmada_parallel_amd.tp_link import connect_local_group
 
     cfg = synth.full_config(cfg_base)
-    ranks = [LLaDAForMultiModalGeneration.from_state_dict(cfg, sd, device=dev, tp_rank=r, tp_size=tp) for r in range(tp)]
-    lib = ranks[0]._lib
-    for m in ranks:
-        abi.check(lib.mmada_comm_create(m._handle, max_rows, None), "comm_create")
-        m._comm_rows = max_rows
-    arr = (C.c_void_p * tp)(*[m._handle.value for m in ranks])
-    for m in ranks:
-        abi.check(lib.mmada_comm_connect_local(m._handle, arr), "connect_local")
-        m._comm_in_library, m.tp_collective = True, transport
-        if transport == "copy":   # the same mapped buffers, bytes moved by the copy engines (csrc/tp_comm.hip mode 4)
-            abi.check(lib.mmada_comm_set_mode(m._handle, 4), "set_mode")
-        if exchange_cus:
-            abi.check(lib.mmada_comm_set_partition(m._handle, exchange_cus), "set_partition")
+    ranks = connect_local_group([LLaDAForMultiModalGeneration.from_state_dict(cfg, sd, device=dev, tp_rank=r, tp_size=tp)
+                                 for r in range(tp)], max_rows, transport=transport, exchange_cus=exchange_cus)
     # One pool of compute streams for every group this process ever builds: a rank's wait kernel spins until its peers'
     # launches run, so no two live streams may share a hardware queue (GPU_MAX_HW_QUEUES, tests/conftest.py) — fresh
     # streams per group would walk through the queues and end up doubling up (seen as hand-off timeouts, status.error).

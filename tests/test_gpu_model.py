@@ -458,7 +458,7 @@ def test_tensor_parallel_slices_on_one_gpu(tiny_model, tp):
 def test_microbatched_overlap_path_matches_single_context(tiny_model, monkeypatch):
     """The tensor-parallel overlap schedule (two activation contexts over shared weights, async all-reduce of one
     micro-batch under the other's kernels) exercised on one GPU with a single-rank RCCL group: results must be
-    bit-identical to the plain path, for forward_body / head_rows and for a whole generate_ti2ti run."""
+    bit-identical to the plain path, for forward_body / head_rows / token_logprobs and for a whole generate_ti2ti run."""
     import torch.distributed as dist
 
     from mmada_parallel_amd import generate_ti2ti
@@ -471,6 +471,12 @@ def test_microbatched_overlap_path_matches_single_context(tiny_model, monkeypatc
     tiny_model.forward_body(ids)
     ref_h = tiny_model.hidden_state().clone()
     ref_l = tiny_model.head_rows(rows, 100, 612).clone()
+    # scoring rows with UNEQUAL counts per sequence, over both micro-batches: every row of sequence 0, every third of the others
+    L = ids.shape[1]
+    srows = torch.cat([torch.arange(L), L + torch.arange(0, L, 3), 2 * L + torch.arange(0, L, 3)]).int().to(DEV)
+    targets = (srows.long() * 37 + 11) % tiny_model.vocab
+    targets[4], targets[L + 2] = -100, tiny_model.vocab + 5   # an ignored row; a target outside the vocabulary (in lane 1)
+    ref_s = [t.clone() for t in tiny_model.token_logprobs(srows, targets, return_stats=True)]
     kw = dict(text_steps=8, timesteps=4, temperature=0.0, text_temperature=0.0, cfg_scale=2.5, cfg_img=4.0,
               uncon_text=job["uncon_text"], uncon_image=job["uncon_image"], return_state=True)
     args = (job["text_start"], job["text_end"], job["image_start"], job["seq_len"], job["newline_every"])
@@ -488,6 +494,11 @@ def test_microbatched_overlap_path_matches_single_context(tiny_model, monkeypatc
         assert tiny_model._split == 2
         assert torch.equal(tiny_model.hidden_state(), ref_h)
         assert torch.equal(tiny_model.head_rows(rows, 100, 612), ref_l)
+        got_s = tiny_model.token_logprobs(srows, targets, return_stats=True)
+        assert tiny_model._split == 2 and int((srows < 2 * L).sum()) not in (0, srows.numel()), "rows in both lanes"
+        for name, got, want in zip(("logprob", "lse", "argmax", "max"), got_s, ref_s):
+            assert got.dtype == want.dtype and torch.equal(got, want), f"token_logprobs on the micro-batched forward: {name}"
+        assert ref_s[0][4].item() == 0.0 and ref_s[0][L + 2].item() == float("-inf")
         got_final = generate_ti2ti(tiny_model, ids, *args, **kw)[2]
         assert torch.equal(got_final, ref_final)
     finally:

@@ -4,7 +4,6 @@ into a published buffer, the ranks hand off, and every rank joins every row in t
 
 The ranks of a group are handles of ONE process on one device (helpers.tp_group / tp_each, see tests/test_gpu_tp.py): nothing
 may synchronise the host before every rank's work is enqueued."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -13,6 +12,7 @@ import torch
 
 from helpers import GOLDEN, PARITY_REPORT, tiny_sd, tp_each, tp_group
 from mmada_parallel_amd import abi, synth, tp as tp_plan
+from mmada_parallel_amd.tp_link import connect_local_group
 from test_gpu_score import LSE_TOL   # the bound of the one-rank head against float64 (derived there)
 
 pytestmark = pytest.mark.gpu
@@ -45,30 +45,18 @@ class single_rank_group:
         self.m = m = LLaDAForMultiModalGeneration.from_state_dict(synth.full_config(self.cfg), self.sd, device=DEV, tp_rank=0, tp_size=1)
         abi.check(lib.mmada_set_option(b"tp_allow_single_rank", 1), "set_option")
         try:
-            abi.check(lib.mmada_comm_create(m._handle, self.max_rows, None), "comm_create")
-            m._comm_rows = self.max_rows
-            if self.transport == "rccl":
-                path = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so").encode()
-                uid = C.create_string_buffer(128)
-                abi.check(lib.mmada_comm_unique_id(uid, path), "mmada_comm_unique_id")
-                abi.check(lib.mmada_comm_connect_rccl(m._handle, uid.raw, path), "mmada_comm_connect_rccl")
-            else:
-                abi.check(lib.mmada_comm_connect_local(m._handle, (C.c_void_p * 1)(m._handle.value)), "connect_local")
-                if self.transport == "copy":
-                    abi.check(lib.mmada_comm_set_mode(m._handle, 4), "set_mode")
-            m._comm_in_library, m.tp_collective = True, self.transport
-            assert m.comm_status()["mode"] == self.transport
+            connect_local_group([m], self.max_rows, transport=self.transport)
+            assert m._comm_in_library and m.tp_collective == self.transport and m.comm_status()["mode"] == self.transport
         except Exception:
             self.__exit__(None, None, None)
             raise
         return m
 
     def __exit__(self, *exc):
-        lib = abi.lib()
-        lib.mmada_set_option(b"tp_allow_single_rank", 0)
+        abi.lib().mmada_set_option(b"tp_allow_single_rank", 0)
         torch.cuda.synchronize()
-        lib.mmada_comm_destroy(self.m._handle)
-        self.m._comm_in_library = False
+        self.m.disconnect_tp()
+        assert not self.m._comm_in_library
         return False
 
 
@@ -141,7 +129,6 @@ def test_result_is_independent_of_rank_count_and_transport():
         t[16:16 + len(edge)] = torch.tensor(edge)
         targets[(c0, c1)] = t.to(DEV)
 
-    lib = abi.lib()
     results = {}
     xn_ref = planted = None
     for k in (1, 2, 4, 8):
@@ -160,8 +147,7 @@ def test_result_is_independent_of_rank_count_and_transport():
             for transport in ("pull", "copy"):
                 if transport == "copy":
                     for m in ranks:
-                        abi.check(lib.mmada_comm_set_mode(m._handle, 4), "set_mode")
-                        m.tp_collective = "copy"
+                        m.set_transport("copy")
 
                 def one(m):
                     m.debug_buffer(0).copy_(xn_ref)

@@ -8,7 +8,6 @@ the peer pointers come from the same process instead of hipIpc).  Nothing may sy
 work is enqueued — a rank's wait kernel spins until its peers' launches arrive.  The multi-PROCESS path (hipIpc handles,
 one process per rank) is covered by test_bench_multi_rank_tensor_parallel_on_one_gpu.
 """
-import ctypes as C
 import os
 
 import pytest
@@ -16,6 +15,7 @@ import torch
 
 from helpers import tiny_job, tiny_sd, tp_each, tp_group
 from mmada_parallel_amd import abi, synth
+from mmada_parallel_amd.tp_link import MODE_NO_EXCHANGE, MODE_OF, connect_local_group
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -208,24 +208,11 @@ def test_single_rank_group_runs_the_whole_transport_and_equals_the_plain_forward
     m = LLaDAForMultiModalGeneration.from_state_dict(synth.full_config(synth.CFG_TINY), tiny_sd(), device=DEV, tp_rank=0, tp_size=1)
     abi.check(lib.mmada_set_option(b"tp_allow_single_rank", 1), "set_option")
     try:
-        abi.check(lib.mmada_comm_create(m._handle, B * Lp, None), "comm_create")
-        m._comm_rows = B * Lp
+        connect_local_group([m], B * Lp, transport=transport, exchange_cus=cus)
         if transport == "rccl":
-            path = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so").encode()
-            uid = C.create_string_buffer(128)
-            abi.check(lib.mmada_comm_unique_id(uid, path), "mmada_comm_unique_id")
-            abi.check(lib.mmada_comm_connect_rccl(m._handle, uid.raw, path), "mmada_comm_connect_rccl")
-            assert lib.mmada_comm_rccl_nranks(m._handle) == 1
-        else:
-            arr = (C.c_void_p * 1)(m._handle.value)
-            abi.check(lib.mmada_comm_connect_local(m._handle, arr), "connect_local")
-            if transport == "copy":
-                abi.check(lib.mmada_comm_set_mode(m._handle, 4), "set_mode")
-        if cus:
-            abi.check(lib.mmada_comm_set_partition(m._handle, cus), "set_partition")
+            assert lib.mmada_comm_rccl_nranks(m._handle) == 1 and m.rccl_nranks() == 1
         assert lib.mmada_comm_partition(m._handle) == cus
-        m._comm_in_library, m.tp_collective = True, transport
-        assert m.comm_status()["mode"] == transport
+        assert m._comm_in_library and m.tp_collective == transport and m.comm_status()["mode"] == transport
         assert m.comm_selftest(iters=3, L=96), "exchange self-test (known partials vs the local expectation)"
         for chunks_L in (L, 40):   # two row chunks (M >= 32) and one
             x = ids[:, :chunks_L].contiguous()
@@ -259,18 +246,62 @@ def test_single_rank_group_runs_the_whole_transport_and_equals_the_plain_forward
         # the no-exchange diagnostic must be reported, not silently return tokens (round-4 advisor)
         from mmada_parallel_amd.generators.parallel_generator import check_tp_exchange
 
-        abi.check(lib.mmada_comm_set_mode(m._handle, 3), "set_mode")
+        abi.check(lib.mmada_comm_set_mode(m._handle, MODE_NO_EXCHANGE), "set_mode")
         with pytest.raises(abi.MmadaError):
             check_tp_exchange(m)
-        abi.check(lib.mmada_comm_set_mode(m._handle, {"rccl": 2, "pull": 1, "copy": 4}[transport]), "set_mode")
+        abi.check(lib.mmada_comm_set_mode(m._handle, MODE_OF[transport]), "set_mode")
         from helpers import save_parity
 
         save_parity(f"single_rank_{transport}_transport" + (f"_{cus}_exchange_cus" if cus else ""), {"bit_identical_to_plain_forward": True, "rccl_nranks": int(lib.mmada_comm_rccl_nranks(m._handle)),
                                                           "selftest": True, "vocab_parallel_head_equals_replicated": True})
     finally:
         lib.mmada_set_option(b"tp_allow_single_rank", 0)
-        lib.mmada_comm_destroy(m._handle)
-        m._comm_in_library = False
+        m.disconnect_tp()
+        assert not m._comm_in_library
+
+
+@pytest.mark.parametrize("transport", ["pull", "copy"])
+def test_connect_local_group_and_disconnect_tp(transport):
+    """The public pair that makes and ends an in-process rank group: connect_local_group (helpers.tp_group is that call on fresh
+    models plus the stream pool) leaves every rank connected, self-tested and agreeing bit for bit; disconnect_tp() leaves it
+    unconnected; a second connect of the same models gives the bits of the first.  B = 1 with L = 40 is one row chunk, L = 96 two
+    (M = 96 >= 4 * 8 * tp, tp.chunk_slices)."""
+    from mmada_parallel_amd import tp as tp_plan
+
+    tp, max_rows = 2, 2 * 96   # comm_selftest's carve is 2 x 96 rows; the forwards below need fewer
+    assert len(tp_plan.chunk_slices(40, tp)) == 1 and len(tp_plan.chunk_slices(96, tp)) == 2
+    ranks, streams = _group(synth.CFG_TINY, tiny_sd(), tp, max_rows, transport=transport)
+    ids = {L: ((torch.arange(L, device=DEV) * 7 + 3) % 1000).view(1, L) for L in (40, 96)}
+    lo, hi = synth.TEXT_VOCAB, synth.TEXT_VOCAB + 320
+
+    def connected_bits():
+        for m in ranks:
+            status = m.comm_status()
+            assert status["mode"] == transport and status["error"] == 0, status
+            assert m._comm_in_library and m.tp_collective == transport and max_rows == m._comm_rows
+        verdicts = _each(ranks, streams, lambda m: m.comm_selftest(wait=False))   # nothing synchronises between the ranks
+        assert all(bool(v) for v in verdicts) and all(m.comm_status()["error"] == 0 for m in ranks), "comm_selftest"
+        bits = []
+        for L, x in ids.items():
+            rows = torch.arange(L, dtype=torch.int32, device=DEV)
+            _each(ranks, streams, lambda m: m.forward_body(x))
+            lg = _each(ranks, streams, lambda m: m.head_rows(rows, lo, hi))
+            assert torch.equal(lg[0], lg[1]), f"{transport}, L = {L}: the ranks' logits differ"
+            bits.append(lg[0].clone())
+        assert all(m.comm_status()["error"] == 0 for m in ranks)
+        return bits
+
+    first = connected_bits()
+    for m in ranks:
+        m.disconnect_tp()
+        assert not m._comm_in_library and m.tp_collective is None
+        assert not m.vocab_parallel_head() and not m.graph_capturable()
+    assert connect_local_group(ranks, max_rows, transport=transport) is ranks
+    again = connected_bits()
+    for a, b in zip(first, again):
+        assert torch.equal(a, b), f"{transport}: a second connection of the same models computes other bits"
+    for m in ranks:
+        m.disconnect_tp()
 
 
 def test_dllm_cache_under_tensor_parallelism(tiny_tp1):

@@ -14,7 +14,7 @@ rounds are reported, plus the per-round ratio (c)/(a).  Weights are synthetic (s
     python tools/score_bench.py --tp 2 [--out profiles/score_tp_bench.txt]
 
 --tp k: a FUNCTIONAL rig, not a scaling measurement.  The k ranks of a tensor-parallel group are handles of this process on ONE
-device (mmada_comm_connect_local, pull transport): they share its compute units and no link is involved.  Timed, interleaved:
+device (tp_link.connect_local_group, pull transport): they share its compute units and no link is involved.  Timed, interleaved:
 
   (c)  fused, one rank     mmada_head_logprobs on a plain TP = 1 model
   (t)  fused, k ranks      the vocabulary-parallel call on every rank of the group, all enqueued before the window closes: the
@@ -40,21 +40,11 @@ from mmada_parallel_amd import LLaDAForMultiModalGeneration, synth  # noqa: E402
 
 def tp_rig(cfg, sd, k, max_rows, dev):
     """The k ranks of a tensor-parallel group as handles of this process, one stream each, pull transport."""
-    import ctypes as C
-
-    from mmada_parallel_amd import abi
+    from mmada_parallel_amd.tp_link import connect_local_group
 
     ranks = [LLaDAForMultiModalGeneration.from_state_dict(synth.full_config(cfg), sd, device=dev, tp_rank=r, tp_size=k, max_batch=2)
              for r in range(k)]
-    lib = ranks[0]._lib
-    for m in ranks:
-        abi.check(lib.mmada_comm_create(m._handle, max_rows, None), "comm_create")
-        m._comm_rows = max_rows
-    arr = (C.c_void_p * k)(*[m._handle.value for m in ranks])
-    for m in ranks:
-        abi.check(lib.mmada_comm_connect_local(m._handle, arr), "connect_local")
-        m._comm_in_library, m.tp_collective = True, "pull"
-    return ranks, [torch.cuda.Stream(device=dev) for _ in range(k)]
+    return connect_local_group(ranks, max_rows), [torch.cuda.Stream(device=dev) for _ in range(k)]
 
 
 def on_every_rank(ranks, streams, fn):

@@ -23,6 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from mmada_parallel_amd import LLaDAForMultiModalGeneration, abi, synth  # noqa: E402
+from mmada_parallel_amd.tp_link import connect_local_group  # noqa: E402
 
 
 def main():
@@ -40,10 +41,7 @@ def main():
     B, L = 1, 1220          # the owner share of one chunk at TP = 8: 9760 / 8 rows (a one-rank group owns every row it has)
     M = B * 1224
     abi.check(lib.mmada_set_option(b"tp_allow_single_rank", 1), "set_option")
-    abi.check(lib.mmada_comm_create(h, M, None), "comm_create")
-    arr = (C.c_void_p * 1)(h.value)
-    abi.check(lib.mmada_comm_connect_local(h, arr), "connect_local")
-    model._comm_in_library, model.tp_collective, model._comm_rows = True, "pull", M
+    connect_local_group([model], M)
     ids = torch.zeros((B, L), dtype=torch.long, device=dev)
     model._ensure_ws(B, L)
     st0 = abi.stream_ptr()
