@@ -1,4 +1,4 @@
-// handle.h — the library's private state behind the opaque mmada_handle (shared by api.hip and tp_comm.hip).
+// handle.h — the library's private state behind the opaque mmada_handle (shared by api.hip and the tensor-parallel units).
 #pragma once
 #include <utility>
 #include <vector>
@@ -6,7 +6,7 @@
 #include "../../include/mmada_mi355x.h"
 #include "kernels.h"
 
-struct TpComm;  // tp_comm.hip
+struct TpComm;  // tp_comm.h (private to tp_comm.hip / tp_heads.hip)
 
 struct LayerWeights {
     bf16_t* wqkv = nullptr;   // [(Hq_l + 2 Hkv_l) * 128, d]   fused, rotary-partner permuted
@@ -93,6 +93,7 @@ int tp_forward_body(mmada_handle* h, hipStream_t s);              // all blocks 
 int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s);  // residual stream rows of every owner -> [M, d]
 void tp_comm_free(mmada_handle* h);
 bool tp_comm_connected(const mmada_handle* h);   // a transport (or the no-exchange diagnostic) is active on this handle
+// tp_heads.hip
 int tp_head_gather(mmada_handle* h, const int32_t* rows, int R, hipStream_t s);  // xg[r] = xn[row r] (xn already = ln_f(x))
 // mmada_head_logprobs on a connected handle: the 256-column tiles split over the ranks, records exchanged, every rank joins
 int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,

@@ -1,5 +1,5 @@
 // rowstat_fold.h — the one fold of a row's column-tile records (EPI_ROWSTAT, kernels.h) into {max, sum exp(x - max), first
-// arg-max}, shared by the one-rank join (gemm.hip: rowstat_combine_kernel) and the tensor-parallel join (tp_comm.hip:
+// arg-max}, shared by the one-rank join (gemm.hip: rowstat_combine_kernel) and the tensor-parallel join (tp_heads.hip:
 // tp_score_join_kernel), so that the two cannot drift apart: the order below IS the result's definition.
 #pragma once
 #include "common.h"

@@ -1,0 +1,151 @@
+// tp_comm.h — state and small helpers shared by the two tensor-parallel units: tp_comm.hip (transports, the exchange, the
+// forward) and tp_heads.hip (the vocabulary-parallel text and scoring heads).  Private to them: every other unit sees the
+// opaque `struct TpComm;` and the function declarations of handle.h only.
+#pragma once
+#include <rccl/rccl.h>
+
+#include "handle.h"
+
+constexpr int TP_MAX = 8;
+constexpr int STAT_ROWS = 16384;   // text rows (B*T) a vocabulary-parallel select can take
+constexpr int SCORE_ROUND = 1280;  // rows per round of the vocabulary-parallel scoring head: whole 320 / 256 / 160 / 128-row GEMM tiles
+constexpr int SCORE_BN = 256;      // columns per record of EPI_ROWSTAT (kernels.h)
+
+// The values of the public header (mmada_comm_status / mmada_comm_set_mode) and of tp_link.py.
+enum TpMode {
+    TP_NONE = 0,         // buffers allocated, not connected
+    TP_PULL = 1,         // pull over mapped peer buffers
+    TP_RCCL = 2,
+    TP_NO_EXCHANGE = 3,  // DIAGNOSTIC: owner-side kernel on this rank's own partial only (wrong values, timing only)
+    TP_COPY = 4,         // copy engines over the mapped peer buffers (connected like pull)
+};
+
+// The four allocations a rank publishes to its peers, in the order of the export record (mmada_comm_create -> connect_ipc)
+enum PubBuf { PUB_PART = 0, PUB_HN, PUB_CTR, PUB_STATS, PUB_COUNT };
+
+struct TpPeers {  // passed to kernels by value
+    const bf16_t* part[TP_MAX];
+    const bf16_t* hn[TP_MAX];
+    const uint32_t* ctr[TP_MAX];
+    const TextStat* stats[TP_MAX];
+};
+
+struct RcclApi {
+    void* dl = nullptr;
+    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
+    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
+    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
+    ncclResult_t (*ReduceScatter)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
+    ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
+    const char* (*GetErrorString)(ncclResult_t) = nullptr;
+    ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;  // optional (reporting only)
+};
+
+// The published record allocation (stats_pub; one hipIpc handle covers it all): [STAT_ROWS] text records, then at text_bytes
+// the scoring head's two record buffers of buf_bytes each, used alternately.  One buffer = `round` target logits (fp32),
+// then at rec_off [tiles][ld] 16-byte tile records of this rank's tiles (ld = the round's rows, rounded up to 8).
+struct ScoreLayout {
+    int round;  // rows per round: min(SCORE_ROUND, ceil8(max_rows))
+    int tiles;  // 256-column tiles a rank can own: ceil(ceil(vocab / 256) / size)
+    size_t text_bytes, buf_bytes, total;
+    uint32_t rec_off;
+};
+inline ScoreLayout score_layout(int max_rows, int vocab, int size) {
+    ScoreLayout l;
+    l.round = min(SCORE_ROUND, (max_rows + 7) / 8 * 8);
+    l.tiles = ((vocab + SCORE_BN - 1) / SCORE_BN + size - 1) / size;
+    l.rec_off = (uint32_t)l.round * 4u;
+    l.buf_bytes = align_up((size_t)l.rec_off + (size_t)l.tiles * l.round * 16, 256);
+    l.text_bytes = (size_t)STAT_ROWS * sizeof(TextStat);
+    l.total = l.text_bytes + 2 * l.buf_bytes;
+    return l;
+}
+
+struct TpComm {
+    TpMode mode = TP_NONE;
+    int rank = 0, size = 1, max_rows = 0, d = 0;
+    bf16_t* part = nullptr;    // [max_rows + 8*size, d]  published: this rank's partial of the row-parallel GEMM
+    bf16_t* hn_pub = nullptr;  // [max_rows + 8*size, d]  published: normalised rows this rank owns (at their global row)
+    uint32_t* ctr = nullptr;   // [16] published sequence counter (fine-grained memory when the runtime grants it)
+    TextStat* stats_pub = nullptr;  // published: this rank's per-row record of the vocabulary-parallel text head + the score buffers
+    TextStat* stats_all = nullptr;  // [size][STAT_ROWS] RCCL transport: all-gathered records
+    // vocabulary-parallel scoring head (tp_head_logprobs)
+    ScoreLayout score{};
+    char* score_pub[2] = {nullptr, nullptr};  // the two published record buffers inside stats_pub's allocation
+    char* score_all = nullptr;      // [size][score.buf_bytes] private: the peers' buffers as gathered (RCCL) / staged (copy)
+    int score_flip = 0;             // the buffer the next round writes
+    bf16_t* head_buf = nullptr;     // [head_rows, ceil(V/size)] this rank's logit slice (allocated at first use)
+    size_t head_bytes = 0;
+    uint32_t* seq = nullptr;   // [1]  private: number of hand-offs this rank has published
+    int* err = nullptr;        // [1]  private: != 0 after a wait timed out (1 + the peer that never arrived)
+    bool ctr_fine = false, data_fine = false;
+    TpPeers peers{};
+    void* opened[TP_MAX][PUB_COUNT] = {};  // hipIpc mappings of the peers' published buffers (closed by tp_comm_free)
+    hipStream_t sc = nullptr;  // exchange stream
+    hipStream_t s_cmp = nullptr;  // CU partition: compute stream masked to the CUs the exchange stream does not own (else null)
+    int part_cus = 0;             // CUs of the exchange stream's mask (0: no partition)
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    bf16_t* stage = nullptr;   // copy transport: [size][ceil(max_rows / size) + 16, d] peer slices of this rank's rows
+    size_t stage_stride = 0;   // elements per peer
+    hipEvent_t ev_g[2] = {}, ev_c[2] = {};
+    int chunks = 2;
+    long long timeout = 0;     // hand-off timeout in wall_clock64 ticks (100 MHz)
+    // RCCL
+    RcclApi nccl;
+    ncclComm_t comm = nullptr;
+    bf16_t* rs_tmp = nullptr;  // [ceil(max_rows/size)+8, d]
+};
+
+// the peers' published buffers are mapped: hand-offs by counters, remote reads or copies
+inline bool peers_mapped(const TpComm* c) { return c->mode == TP_PULL || c->mode == TP_COPY; }
+// a transport that really exchanges is connected (not none, not the no-exchange diagnostic)
+inline bool transport_connected(const TpComm* c) { return c && c->mode != TP_NONE && c->mode != TP_NO_EXCHANGE; }
+
+// rank j's published buffers as this rank addresses them -> the table the kernels take
+inline void set_peer(TpPeers& p, int j, void* const buf[PUB_COUNT]) {
+    p.part[j] = (const bf16_t*)buf[PUB_PART]; p.hn[j] = (const bf16_t*)buf[PUB_HN];
+    p.ctr[j] = (const uint32_t*)buf[PUB_CTR]; p.stats[j] = (const TextStat*)buf[PUB_STATS];
+}
+
+// 16 bytes of a peer's buffer at system scope (sc0 sc1: never served from this agent's caches) as ONE 16-byte request.
+// A relaxed system-scope __hip_atomic_load lowers to an sc0 sc1 load only up to 8 bytes, and two of those per 16 bytes use
+// half of every 64-byte fabric request each and ask for every line twice (round-2 review: 2x read amplification on xGMI).
+// The buffer form carries the cache-policy bits in its aux operand (1 = sc0, 16 = sc1) and is counted by hipcc's own
+// s_waitcnt bookkeeping, unlike an inline-asm load.  `base` must be wave-uniform (a kernel argument): the descriptor is
+// built in SGPRs; the per-lane part is a 32-bit byte offset (mmada_comm_create refuses buffers of 4 GiB or more).
+MM_DEVICE u32x4 load_sys16(const void* base, uint32_t byte_off) {
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0xffffffffu, 0x00020000);
+    return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 17);
+}
+
+// One hand-off on stream s: publish this rank's next sequence number, then wait (bounded) for every peer's (tp_comm.hip)
+int signal_wait(TpComm* c, hipStream_t s);
+
+inline int nccl_fail(TpComm* c, const char* what, ncclResult_t r) {
+    return mm_fail("%s: %s", what, c->nccl.GetErrorString ? c->nccl.GetErrorString(r) : "RCCL error");
+}
+
+struct Slice { int m0, m1, slice, r0, r1; };
+
+// chunk k of `nch` over M rows; every chunk but the last is a multiple of 8*tp rows, so only the last one is padded
+inline Slice chunk_slice(int M, int tp, int rank, int nch, int k) {
+    Slice s;
+    const int unit = 8 * tp;
+    const int first = nch == 2 ? (M / 2 + unit - 1) / unit * unit : M;
+    s.m0 = k == 0 ? 0 : min(first, M);
+    s.m1 = (k == nch - 1) ? M : min(first, M);
+    const int rows = s.m1 - s.m0;
+    s.slice = max(8, ((rows + tp - 1) / tp + 7) / 8 * 8);
+    s.r0 = min(s.m1, s.m0 + rank * s.slice);
+    s.r1 = min(s.m1, s.r0 + s.slice);
+    return s;
+}
+
+// The row chunks of a forward over M rows: two (the exchange of one runs under the GEMM of the other) once M is large enough
+struct ChunkPlan { int n; Slice sl[2]; };
+inline ChunkPlan chunk_plan(const TpComm* c, int M) {
+    ChunkPlan p;
+    p.n = (c->chunks >= 2 && M >= 4 * 8 * c->size) ? 2 : 1;
+    for (int k = 0; k < p.n; ++k) p.sl[k] = chunk_slice(M, c->size, c->rank, p.n, k);
+    return p;
+}

@@ -35,86 +35,17 @@
 // Overlap: the M rows are cut into two chunks; the exchange of chunk i runs on a second (high-priority) stream under the
 // row-parallel GEMM of chunk i+1 / the next column-parallel GEMM of chunk i-1 — also at batch 1, the only join point is
 // the attention (needs every key).
+// The LM heads on top of these transports (text select, scoring) are tp_heads.hip; the state both units share is tp_comm.h.
 #include <dlfcn.h>
-#include <rccl/rccl.h>
 
 #include <cstdlib>
 #include <cstring>
 
-#include "handle.h"
-#include "rowstat_fold.h"
+#include "tp_comm.h"
 
 namespace {
 
-constexpr int TP_MAX = 8;
 constexpr int MAXCH = 8;  // 16-B chunks per lane: d <= 4096
-
-constexpr int STAT_ROWS = 16384;  // text rows (B*T) a vocabulary-parallel select can take
-constexpr int SCORE_ROUND = 1280;  // rows per round of the vocabulary-parallel scoring head: whole 320 / 256 / 160 / 128-row GEMM tiles
-constexpr int SCORE_BN = 256;      // columns per record of EPI_ROWSTAT (kernels.h)
-
-struct TpPeers {
-    const bf16_t* part[TP_MAX];
-    const bf16_t* hn[TP_MAX];
-    const uint32_t* ctr[TP_MAX];
-    const TextStat* stats[TP_MAX];
-};
-
-struct RcclApi {
-    void* dl = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*ReduceScatter)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-    ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;  // optional (reporting only)
-};
-
-}  // namespace
-
-struct TpComm {
-    int mode = 0;  // 0: buffers allocated, not connected; 1: pull over mapped peer buffers; 2: RCCL;
-                   // 3: DIAGNOSTIC "no exchange" (owner-side kernel on this rank's own partial only: wrong values, timing only)
-                   // 4: copy engines over the mapped peer buffers (connected like 1)
-    int rank = 0, size = 1, max_rows = 0, d = 0;
-    bf16_t* part = nullptr;    // [max_rows + 8*size, d]  published: this rank's partial of the row-parallel GEMM
-    bf16_t* hn_pub = nullptr;  // [max_rows + 8*size, d]  published: normalised rows this rank owns (at their global row)
-    uint32_t* ctr = nullptr;   // [16] published sequence counter (fine-grained memory when the runtime grants it)
-    TextStat* stats_pub = nullptr;  // [STAT_ROWS] published: this rank's per-row record of the vocabulary-parallel text head
-    TextStat* stats_all = nullptr;  // [size][STAT_ROWS] RCCL transport: all-gathered records
-    // vocabulary-parallel scoring head (tp_head_logprobs).  Two published record buffers, used alternately, in stats_pub's
-    // allocation behind the STAT_ROWS text records (one hipIpc handle covers both).  One buffer = score_round target logits
-    // (fp32), then [score_tiles][ld] 16-byte tile records of this rank's tiles (ld = the round's rows, rounded up to 8)
-    char* score_pub[2] = {nullptr, nullptr};
-    char* score_all = nullptr;      // [size][score_buf_bytes] private: the peers' buffers as gathered (RCCL) / staged (copy)
-    size_t score_buf_bytes = 0;
-    int score_round = 0;            // rows per round: min(SCORE_ROUND, ceil8(max_rows))
-    int score_tiles = 0;            // 256-column tiles a rank can own: ceil(ceil(vocab / 256) / size)
-    int score_flip = 0;             // the buffer the next round writes
-    bf16_t* head_buf = nullptr;     // [head_rows, ceil(V/size)] this rank's logit slice (allocated at first use)
-    size_t head_bytes = 0;
-    uint32_t* seq = nullptr;   // [1]  private: number of hand-offs this rank has published
-    int* err = nullptr;        // [1]  private: != 0 after a wait timed out (1 + the peer that never arrived)
-    bool ctr_fine = false, data_fine = false;
-    TpPeers peers{};
-    void* opened[4][TP_MAX] = {};
-    hipStream_t sc = nullptr;  // exchange stream
-    hipStream_t s_cmp = nullptr;  // CU partition: compute stream masked to the CUs the exchange stream does not own (else null)
-    int part_cus = 0;             // CUs of the exchange stream's mask (0: no partition)
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    bf16_t* stage = nullptr;   // copy transport: [size][ceil(max_rows / size) + 16, d] peer slices of this rank's rows
-    size_t stage_stride = 0;   // elements per peer
-    hipEvent_t ev_g[2] = {}, ev_c[2] = {};
-    int chunks = 2;
-    long long timeout = 0;     // hand-off timeout in wall_clock64 ticks (100 MHz)
-    // RCCL
-    RcclApi nccl;
-    ncclComm_t comm = nullptr;
-    bf16_t* rs_tmp = nullptr;  // [ceil(max_rows/size)+8, d]
-};
-
-namespace {
 
 // ---- hand-off ------------------------------------------------------------------------------------------------------
 // `seq` (private) and `ctr` (published) live in one fine-grained block and are only ever touched with system-scope atomics:
@@ -144,17 +75,6 @@ __global__ void tp_wait_kernel(const uint32_t* seq, TpPeers p, int size, int ran
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-}
-
-// 16 bytes of a peer's buffer at system scope (sc0 sc1: never served from this agent's caches) as ONE 16-byte request.
-// A relaxed system-scope __hip_atomic_load lowers to an sc0 sc1 load only up to 8 bytes, and two of those per 16 bytes use
-// half of every 64-byte fabric request each and ask for every line twice (round-2 review: 2x read amplification on xGMI).
-// The buffer form carries the cache-policy bits in its aux operand (1 = sc0, 16 = sc1) and is counted by hipcc's own
-// s_waitcnt bookkeeping, unlike an inline-asm load.  `base` must be wave-uniform (a kernel argument): the descriptor is
-// built in SGPRs; the per-lane part is a 32-bit byte offset (mmada_comm_create refuses buffers of 4 GiB or more).
-MM_DEVICE u32x4 load_sys16(const void* base, uint32_t byte_off) {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0xffffffffu, 0x00020000);
-    return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 17);
 }
 
 struct ReduceArgs {
@@ -291,110 +211,6 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const bf16_t* src, bf16_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// out[r] = src[b*Lp + l] for rows[r] = b*L + l (LM-head rows of an already normalised stream)
-__global__ __launch_bounds__(256) void gather_rows_kernel(const bf16_t* src, const int32_t* rows, int R, int L, int Lp, int d,
-                                                          int nflat, bf16_t* out) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;
-    const int flat = min(max(rows[r], 0), nflat - 1);
-    const int b = flat / L, l = flat - b * L;
-    const u32x4* s = (const u32x4*)(src + ((size_t)b * Lp + l) * d);
-    for (int c = threadIdx.x & 63; c < (d >> 3); c += 64) ((u32x4*)(out + (size_t)r * d))[c] = s[c];
-}
-
-// Vocabulary-parallel text head: combine the tp per-rank records of every row into the conf (fp64 soft-max probability of
-// the arg-max, generators/parallel_generator.py:185-205) and x0 the one-rank kernel writes.  One thread per row.
-__global__ void tp_text_combine_kernel(TpPeers p, int size, int rank, const TextStat* own, const TextStat* gathered,
-                                       int stat_stride, int R, double* conf_out, int32_t* x0_out) {
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= R) return;
-    if (!gathered) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    TextStat st[TP_MAX];
-    for (int j = 0; j < size; ++j) {
-        if (gathered) st[j] = gathered[(size_t)j * stat_stride + row];
-        else if (j == rank) st[j] = own[row];
-        else {
-            const u32x4 v = load_sys16(p.stats[j], (uint32_t)row * 16u);  // one 16-byte record
-            st[j].lmax = __uint_as_float(v[0]);
-            st[j].arg = (int32_t)v[1];
-            st[j].sum = __longlong_as_double((long long)(((uint64_t)v[3] << 32) | v[2]));
-        }
-    }
-    float mx = -INFINITY;
-    int arg = 0;
-    for (int j = 0; j < size; ++j)
-        if (st[j].lmax > mx) { mx = st[j].lmax; arg = st[j].arg; }  // strict >: the lowest rank (lowest column) wins a tie
-    if (!(mx > -INFINITY)) {  // not a masked position (or an all -inf row)
-        conf_out[row] = -INFINITY;
-        x0_out[row] = 0;
-        return;
-    }
-    double tot = 0.0;
-    for (int j = 0; j < size; ++j)
-        if (st[j].lmax > -INFINITY) tot += st[j].sum * exp((double)st[j].lmax - (double)mx);
-    conf_out[row] = 1.0 / tot;  // exp(l[x0] - max) / sum with x0 the arg-max
-    x0_out[row] = arg;
-}
-
-// ---- vocabulary-parallel scoring head ---------------------------------------------------------------------------------------
-// tx[0, n) = -inf in a PUBLISHED buffer (a target outside a rank's columns leaves it behind): ends like every publishing kernel
-__global__ __launch_bounds__(256) void tp_score_reset_kernel(float* tx, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) tx[i] = -__builtin_inff();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-struct ScoreJoinArgs {
-    const char* src[TP_MAX];  // rank j's record buffer of this round where THIS rank reads it: its own memory, a peer's mapped
-                              // buffer (pull) or the gathered / staged copy (RCCL, copy)
-    int sys;                  // pull: src[j != rank] is remote, read with system-scope loads
-    int size, rank;
-    int q;                    // tiles per rank: tile t is record (t - owner * q) of rank owner = t / q
-    uint32_t rec_off;         // byte offset of the records behind the target logits
-    int ld, ntn, R, col_begin, col_end;
-    const int64_t* targets;
-    float *logprob, *lse;
-    int32_t* argmax;
-    float* vmax;
-};
-
-// The join of rowstat_combine_kernel (gemm.hip) with tile t's record taken from the rank that owns t: the same fold
-// (rowstat_fold.h), so every rank — and a one-rank handle — ends with the same bits.  Every rank joins every row.
-__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_score_join_kernel(ScoreJoinArgs a) {
-    if (a.sys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // see tp_reduce_norm_kernel
-    const int row = blockIdx.x * RS_ROWS + threadIdx.x % RS_ROWS;
-    auto fetch = [&](int t, int r) -> float4 {
-        const int owner = t / a.q;
-        const uint32_t off = a.rec_off + ((uint32_t)(t - owner * a.q) * (uint32_t)a.ld + (uint32_t)r) * 16u;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        // the lanes of a wave hold neighbouring tiles, which may belong to two owners: one pass per rank (unrolled: src[o] is a
-        // kernel argument in SGPRs) keeps the base pointer wave-uniform, as load_sys16's descriptor needs it
-#pragma unroll
-        for (int o = 0; o < TP_MAX; ++o) {
-            if (o != owner) continue;
-            if (a.sys && o != a.rank) v = load_sys16(a.src[o], off);
-            else v = *(const u32x4*)(a.src[o] + off);
-        }
-        return float4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
-    };
-    float m, sum;
-    int arg;
-    if (!rowstat_fold(fetch, row, a.R, a.ntn, m, sum, arg)) return;
-    const long long t = a.targets[row];
-    float tx = -__builtin_inff();
-    if (t >= a.col_begin && t < a.col_end) {  // the target logit lives with the rank that owns the target's tile
-        const int owner = (int)((t - a.col_begin) / SCORE_BN) / a.q;
-#pragma unroll
-        for (int o = 0; o < TP_MAX; ++o) {
-            if (o != owner) continue;
-            const float* p = (const float*)a.src[o] + row;
-            tx = (a.sys && o != a.rank) ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : *p;
-        }
-    }
-    rowstat_finish(row, m, sum, arg, t, tx, a.logprob, a.lse, a.argmax, a.vmax);
-}
-
 // One wave on (at least) every XCD writes that XCD's L2 back: for partials that were NOT produced by a publishing kernel
 // of this library (mmada_comm_exchange: the caller filled the buffer with its own kernels).  Workgroup b runs on XCD b % 8.
 __global__ void tp_flush_kernel() {
@@ -408,6 +224,8 @@ long long default_timeout_ticks() {
     return (long long)(sec * 100e6);  // wall_clock64 runs at 100 MHz on gfx9
 }
 
+}  // namespace
+
 int signal_wait(TpComm* c, hipStream_t s) {
     hipLaunchKernelGGL(tp_signal_kernel, dim3(1), dim3(1), 0, s, c->seq, c->ctr);
     hipLaunchKernelGGL(tp_wait_kernel, dim3(1), dim3(64), 0, s, c->seq, c->peers, c->size, c->rank, c->err, c->timeout);
@@ -415,106 +233,73 @@ int signal_wait(TpComm* c, hipStream_t s) {
     return 0;
 }
 
-struct Slice { int m0, m1, slice, r0, r1; };
+namespace {
 
-// chunk k of `nch` over M rows; every chunk but the last is a multiple of 8*tp rows, so only the last one is padded
-Slice chunk_slice(int M, int tp, int rank, int nch, int k) {
-    Slice s;
-    const int unit = 8 * tp;
-    const int first = nch == 2 ? (M / 2 + unit - 1) / unit * unit : M;
-    s.m0 = k == 0 ? 0 : min(first, M);
-    s.m1 = (k == nch - 1) ? M : min(first, M);
-    const int rows = s.m1 - s.m0;
-    s.slice = max(8, ((rows + tp - 1) / tp + 7) / 8 * 8);
-    s.r0 = min(s.m1, s.m0 + rank * s.slice);
-    s.r1 = min(s.m1, s.r0 + s.slice);
-    return s;
-}
-
-int nccl_fail(TpComm* c, const char* what, ncclResult_t r) {
-    return mm_fail("%s: %s", what, c->nccl.GetErrorString ? c->nccl.GetErrorString(r) : "RCCL error");
+// The owner kernel over `own` rows; tp = the compile-time rank count to use (0, or a count without an instantiation: run-time a.size)
+int launch_reduce_norm(const ReduceArgs& a, int own, int tp, hipStream_t s) {
+    const dim3 grid((own + 3) / 4), blk(256);
+    switch (tp) {
+        case 2: hipLaunchKernelGGL(tp_reduce_norm_kernel<2>, grid, blk, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(tp_reduce_norm_kernel<4>, grid, blk, 0, s, a); break;
+        case 8: hipLaunchKernelGGL(tp_reduce_norm_kernel<8>, grid, blk, 0, s, a); break;
+        default: hipLaunchKernelGGL(tp_reduce_norm_kernel<0>, grid, blk, 0, s, a);
+    }
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 // One exchange over rows [m0, m1): partial sums in c->part  ->  x (own rows), xn (all rows) ; on stream s
 int exchange(mmada_handle* h, const Slice& sl, const bf16_t* norm_w, hipStream_t s) {
     TpComm* c = h->tp;
-    const int d = h->cfg.d_model;
+    if (c->mode == TP_NONE) return mm_fail("tensor-parallel forward: no transport connected (mmada_comm_connect_ipc / _local / _rccl)");
+    const int d = h->cfg.d_model, tp = c->size, own = sl.r1 - sl.r0;
+    const bool mapped = peers_mapped(c);
+    // RCCL: every rank contributes its `slice` rows (rows past M are pad rows of the buffers: never read by a GEMM)
+    const size_t cnt = (size_t)sl.slice * d;
     ReduceArgs a{};
-    a.p = c->peers; a.size = c->size; a.rank = c->rank;
+    a.p = c->peers; a.size = tp; a.rank = c->rank; a.nsrc = mapped ? tp : 1;
     a.part = c->part; a.x = h->x; a.w = norm_w; a.hn_pub = c->hn_pub; a.xn = h->xn;
     a.r0 = sl.r0; a.r1 = sl.r1; a.d = d; a.eps = h->cfg.rms_eps;
-    const int own = sl.r1 - sl.r0;
-    if (c->mode == 1) {
-        if (signal_wait(c, s)) return 1;  // every rank's partial of this chunk is complete
-        a.nsrc = c->size;
-        if (own > 0) {
-            const dim3 grid((own + 3) / 4), blk(256);
-            switch (c->size) {
-                case 2: hipLaunchKernelGGL(tp_reduce_norm_kernel<2>, grid, blk, 0, s, a); break;
-                case 4: hipLaunchKernelGGL(tp_reduce_norm_kernel<4>, grid, blk, 0, s, a); break;
-                case 8: hipLaunchKernelGGL(tp_reduce_norm_kernel<8>, grid, blk, 0, s, a); break;
-                default: hipLaunchKernelGGL(tp_reduce_norm_kernel<0>, grid, blk, 0, s, a);
-            }
+    // ---- reduce-scatter half: the sources of the owner kernel (pull: the peers' buffers as they are mapped) ----
+    if (mapped && signal_wait(c, s)) return 1;  // every rank's partial of this chunk is complete
+    if (c->mode == TP_COPY) {
+        // the tp - 1 peer slices of MY rows -> local staging, by the copy engines; the kernel then sums local operands
+        // (src_row0[j] = r0: staging row 0 of peer j is stream row r0)
+        for (int j = 0; j < tp && own > 0; ++j) {
+            if (j == c->rank) { a.p.part[j] = c->part; continue; }
+            bf16_t* dst = c->stage + (size_t)j * c->stage_stride;
+            MM_CHECK_HIP(hipMemcpyAsync(dst, c->peers.part[j] + (size_t)sl.r0 * d, (size_t)own * d * 2, hipMemcpyDefault, s));
+            a.p.part[j] = dst;
+            a.src_row0[j] = sl.r0;
         }
-        if (signal_wait(c, s)) return 1;  // every owner's normalised rows are published
+    } else if (c->mode == TP_RCCL) {
+        ncclResult_t r = c->nccl.ReduceScatter(c->part + (size_t)sl.m0 * d, c->rs_tmp, cnt, ncclBfloat16, ncclSum, c->comm, s);
+        if (r != ncclSuccess) return nccl_fail(c, "ncclReduceScatter", r);
+        a.presum = c->rs_tmp;
+    } else if (c->mode == TP_NO_EXCHANGE) {  // diagnostic: the forward without its exchange (bench.py: exposed exchange time = real - this)
+        a.presum = c->part + (size_t)sl.r0 * d;
+    }
+    if (own > 0 && launch_reduce_norm(a, own, mapped ? tp : 0, s)) return 1;
+    // ---- all-gather half ----
+    if (mapped && signal_wait(c, s)) return 1;  // every owner's normalised rows are published
+    if (c->mode == TP_PULL) {
         hipLaunchKernelGGL(tp_gather_kernel, dim3((sl.m1 - sl.m0 + 3) / 4), dim3(256), 0, s, c->peers, c->rank, sl.m0, sl.m1,
                            sl.slice, d, h->xn, 0);
         MM_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
-    if (c->mode == 4) {
-        if (signal_wait(c, s)) return 1;  // every rank's partial of this chunk is complete
-        // the tp - 1 peer slices of MY rows -> local staging, by the copy engines; the kernel then sums local operands
-        // (src_row0[j] = r0: staging row 0 of peer j is stream row r0)
-        ReduceArgs b = a;
-        b.nsrc = c->size;
-        if (own > 0) {
-            for (int j = 0; j < c->size; ++j) {
-                if (j == c->rank) { b.p.part[j] = c->part; continue; }
-                bf16_t* dst = c->stage + (size_t)j * c->stage_stride;
-                MM_CHECK_HIP(hipMemcpyAsync(dst, c->peers.part[j] + (size_t)sl.r0 * d, (size_t)own * d * 2, hipMemcpyDefault, s));
-                b.p.part[j] = dst;
-                b.src_row0[j] = sl.r0;
-            }
-            const dim3 grid((own + 3) / 4), blk(256);
-            switch (c->size) {
-                case 2: hipLaunchKernelGGL(tp_reduce_norm_kernel<2>, grid, blk, 0, s, b); break;
-                case 4: hipLaunchKernelGGL(tp_reduce_norm_kernel<4>, grid, blk, 0, s, b); break;
-                case 8: hipLaunchKernelGGL(tp_reduce_norm_kernel<8>, grid, blk, 0, s, b); break;
-                default: hipLaunchKernelGGL(tp_reduce_norm_kernel<0>, grid, blk, 0, s, b);
-            }
-            MM_CHECK_HIP(hipGetLastError());
-        }
-        if (signal_wait(c, s)) return 1;  // every owner's normalised rows are published
-        for (int j = 0; j < c->size; ++j) {   // all-gather half: tp - 1 copies, no kernel
+    } else if (c->mode == TP_COPY) {  // tp - 1 copies, no kernel
+        for (int j = 0; j < tp; ++j) {
             if (j == c->rank) continue;
             const int j0 = min(sl.m1, sl.m0 + j * sl.slice), j1 = min(sl.m1, j0 + sl.slice);
             if (j1 > j0)
                 MM_CHECK_HIP(hipMemcpyAsync(h->xn + (size_t)j0 * d, c->peers.hn[j] + (size_t)j0 * d, (size_t)(j1 - j0) * d * 2,
                                             hipMemcpyDefault, s));
         }
-        return 0;
-    }
-    if (c->mode == 3) {  // diagnostic: the forward without its exchange (bench.py: exposed exchange time = real - this)
-        a.nsrc = 1; a.presum = c->part + (size_t)sl.r0 * d;
-        if (own > 0) hipLaunchKernelGGL(tp_reduce_norm_kernel<0>, dim3((own + 3) / 4), dim3(256), 0, s, a);
-        MM_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
-    if (c->mode == 2) {
-        const size_t cnt = (size_t)sl.slice * d;
-        ncclResult_t r = c->nccl.ReduceScatter(c->part + (size_t)sl.m0 * d, c->rs_tmp, cnt, ncclBfloat16, ncclSum, c->comm, s);
-        if (r != ncclSuccess) return nccl_fail(c, "ncclReduceScatter", r);
-        a.nsrc = 1; a.presum = c->rs_tmp;
-        if (own > 0) hipLaunchKernelGGL(tp_reduce_norm_kernel<0>, dim3((own + 3) / 4), dim3(256), 0, s, a);
-        MM_CHECK_HIP(hipGetLastError());
-        // every rank contributes its `slice` rows (rows past M are pad rows of the buffers: never read by a GEMM)
-        r = c->nccl.AllGather(c->hn_pub + (size_t)(sl.m0 + c->rank * sl.slice) * d, h->xn + (size_t)sl.m0 * d, cnt,
-                              ncclBfloat16, c->comm, s);
+    } else if (c->mode == TP_RCCL) {
+        ncclResult_t r = c->nccl.AllGather(c->hn_pub + (size_t)(sl.m0 + c->rank * sl.slice) * d, h->xn + (size_t)sl.m0 * d, cnt,
+                                           ncclBfloat16, c->comm, s);
         if (r != ncclSuccess) return nccl_fail(c, "ncclAllGather", r);
-        return 0;
     }
-    return mm_fail("tensor-parallel forward: no transport connected (mmada_comm_connect_ipc / _local / _rccl)");
+    return 0;
 }
 
 int load_rccl(RcclApi* api, const char* path) {
@@ -540,170 +325,18 @@ int load_rccl(RcclApi* api, const char* path) {
     return 0;
 }
 
-struct CommExport {  // what a rank hands its peers (mmada_comm_create -> mmada_comm_connect_ipc): 4 x 64 B
-    hipIpcMemHandle_t part, hn, ctr, stats;
-};
+// what a rank hands its peers (mmada_comm_create -> mmada_comm_connect_ipc): 4 x 64 B
+struct CommExport { hipIpcMemHandle_t buf[PUB_COUNT]; };
 
-}  // namespace
-
-// ---- forward ---------------------------------------------------------------------------------------------------------
-// All blocks of a tensor-parallel forward.  h->x holds the embeddings (replicated), every rank keeps its own rows of the
-// residual stream from here on.  Compute on `s`, exchanges on the library's second stream.
-static int tp_forward_body_on(mmada_handle* h, hipStream_t s);
-
-int tp_forward_body(mmada_handle* h, hipStream_t s_user) {
-    TpComm* c = h->tp;
-    if (!c || c->mode == 0) return mm_fail("tensor-parallel forward: no transport connected (mmada_comm_create + connect)");
-    if (!c->s_cmp) return tp_forward_body_on(h, s_user);
-    // CU partition: the blocks run on the library's masked compute stream, forked from and joined to the caller's stream
-    MM_CHECK_HIP(hipEventRecord(c->ev_in, s_user));
-    MM_CHECK_HIP(hipStreamWaitEvent(c->s_cmp, c->ev_in, 0));
-    const int rc = tp_forward_body_on(h, c->s_cmp);
-    MM_CHECK_HIP(hipEventRecord(c->ev_out, c->s_cmp));
-    MM_CHECK_HIP(hipStreamWaitEvent(s_user, c->ev_out, 0));
-    return rc;
+// this rank's own published buffers, in export order
+void own_pubs(const TpComm* c, void* buf[PUB_COUNT]) {
+    buf[PUB_PART] = c->part; buf[PUB_HN] = c->hn_pub; buf[PUB_CTR] = c->ctr; buf[PUB_STATS] = c->stats_pub;
 }
 
-static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
+// mmada_comm_create behind its argument checks: fills the (empty) comm the handle already owns; on a failing exit the caller
+// frees it with whatever was allocated up to there
+int comm_init(mmada_handle* h, int max_rows, void* export_out) {
     TpComm* c = h->tp;
-    if (h->M > c->max_rows) return mm_fail("tensor-parallel forward: %d rows exceed the comm buffers (%d)", h->M, c->max_rows);
-    const int d = h->cfg.d_model, tp = c->size, M = h->M, nl = h->cfg.n_layers;
-    if ((d >> 3) > 64 * MAXCH) return mm_fail("tensor-parallel forward: d_model > %d is not supported", 64 * MAXCH * 8);
-    const int nch = (c->chunks >= 2 && M >= 4 * 8 * tp) ? 2 : 1;
-    Slice sl[2];
-    for (int k = 0; k < nch; ++k) sl[k] = chunk_slice(M, tp, c->rank, nch, k);
-    const double rows_real = (double)h->B * h->L / M;  // fraction of stream rows that are not padding (FLOP accounting)
-    // first RMSNorm of the forward: the embeddings are replicated, no exchange needed
-    if (h->xn_is_layer0) h->xn_is_layer0 = false;  // fused into the embedding kernel
-    else if (launch_rmsnorm(h->x, h->layers[0].attn_norm, h->xn, M, d, h->cfg.rms_eps, s)) return 1;
-    bool pending[2] = {false, false};  // chunk k's xn rows are being produced on the exchange stream
-    auto after_gemm_exchange = [&](int k, const bf16_t* w) -> int {
-        MM_CHECK_HIP(hipEventRecord(c->ev_g[k], s));
-        MM_CHECK_HIP(hipStreamWaitEvent(c->sc, c->ev_g[k], 0));
-        if (exchange(h, sl[k], w, c->sc)) return 1;
-        MM_CHECK_HIP(hipEventRecord(c->ev_c[k], c->sc));
-        pending[k] = true;
-        return 0;
-    };
-    auto need_xn = [&](int k) -> int {
-        if (pending[k]) {
-            MM_CHECK_HIP(hipStreamWaitEvent(s, c->ev_c[k], 0));
-            pending[k] = false;
-        }
-        return 0;
-    };
-    for (int layer = 0; layer < nl; ++layer) {
-        const LayerWeights& lw = h->layers[layer];
-        // ---- q/k/v (column-parallel: this rank's heads), RoPE in the epilogue; a dLLM cache step writes this rank's heads of the
-        // block's keys / values into the slot ----
-        for (int k = 0; k < nch; ++k) {
-            if (need_xn(k)) return 1;
-            const GemmArgs g = qkv_args(h, layer, sl[k].m0, sl[k].m1 - sl[k].m0);
-            ProfScope p(h, layer, 0, 2.0 * g.M * rows_real * g.N * g.K, s);
-            if (launch_gemm(EPI_QKV, g, s)) return 1;
-        }
-        // ---- attention over this rank's heads: the one join point (every key of a sequence) ----
-        if (block_attention(h, layer, s)) return 1;
-        // ---- attn_out (row-parallel) chunk by chunk; chunk k's exchange runs under chunk k+1's GEMM ----
-        for (int k = 0; k < nch; ++k) {
-            GemmArgs o = attn_out_args(h, layer, sl[k].m0, sl[k].m1 - sl[k].m0);
-            o.C = c->part + (size_t)sl[k].m0 * d; o.publish = c->mode == 1 || c->mode == 4;
-            {
-                ProfScope p(h, layer, 2, 2.0 * o.M * rows_real * o.N * o.K, s);
-                if (launch_gemm(EPI_STORE, o, s)) return 1;
-            }
-            if (after_gemm_exchange(k, lw.ff_norm)) return 1;
-        }
-        // ---- gate/up (column-parallel) + SiLU*mul, then down (row-parallel) ----
-        for (int k = 0; k < nch; ++k) {
-            if (need_xn(k)) return 1;
-            const GemmArgs g = gate_up_args(h, layer, sl[k].m0, sl[k].m1 - sl[k].m0);
-            ProfScope p(h, layer, 3, 2.0 * g.M * rows_real * g.N * g.K, s);
-            if (launch_gemm(EPI_SWIGLU, g, s)) return 1;
-        }
-        const bf16_t* next_w = layer + 1 < nl ? h->layers[layer + 1].attn_norm : h->ln_f;
-        for (int k = 0; k < nch; ++k) {
-            GemmArgs o = down_args(h, layer, sl[k].m0, sl[k].m1 - sl[k].m0);
-            o.C = c->part + (size_t)sl[k].m0 * d; o.publish = c->mode == 1 || c->mode == 4;
-            {
-                ProfScope p(h, layer, 4, 2.0 * o.M * rows_real * o.N * o.K, s);
-                if (launch_gemm(EPI_STORE, o, s)) return 1;
-            }
-            if (after_gemm_exchange(k, next_w)) return 1;
-        }
-    }
-    for (int k = 0; k < nch; ++k)
-        if (need_xn(k)) return 1;
-    h->xn_is_final = true;  // xn = ln_f(x) on every row
-    return 0;
-}
-
-// Residual stream of every owner -> full [M, d] (parity taps; the forward itself never moves the residual stream)
-int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s) {
-    TpComm* c = h->tp;
-    if (!c || c->mode == 0 || c->mode == 3) return mm_fail("tp_gather_stream: no transport connected (or the no-exchange diagnostic is on)");
-    const int d = h->cfg.d_model, M = h->M;
-    const int nch = (c->chunks >= 2 && M >= 4 * 8 * c->size) ? 2 : 1;
-    for (int k = 0; k < nch; ++k) {
-        const Slice sl = chunk_slice(M, c->size, c->rank, nch, k);
-        const int own = sl.r1 - sl.r0;
-        if (own > 0) {
-            hipLaunchKernelGGL(copy_rows_kernel, dim3((own + 3) / 4), dim3(256), 0, s, h->x, c->hn_pub, sl.r0, sl.r1, d);
-            hipLaunchKernelGGL(copy_rows_kernel, dim3((own + 3) / 4), dim3(256), 0, s, h->x, full_out, sl.r0, sl.r1, d);
-        }
-        if (c->mode == 1 || c->mode == 4) {
-            if (signal_wait(c, s)) return 1;
-            hipLaunchKernelGGL(tp_gather_kernel, dim3((sl.m1 - sl.m0 + 3) / 4), dim3(256), 0, s, c->peers, c->rank, sl.m0,
-                               sl.m1, sl.slice, d, full_out, 0);
-            if (signal_wait(c, s)) return 1;  // hn_pub may be overwritten only after every peer has pulled
-        } else {
-            ncclResult_t r = c->nccl.AllGather(c->hn_pub + (size_t)(sl.m0 + c->rank * sl.slice) * d,
-                                               full_out + (size_t)sl.m0 * d, (size_t)sl.slice * d, ncclBfloat16, c->comm, s);
-            if (r != ncclSuccess) return nccl_fail(c, "ncclAllGather", r);
-        }
-        MM_CHECK_HIP(hipGetLastError());
-    }
-    return 0;
-}
-
-bool tp_comm_connected(const mmada_handle* h) { return h->tp && h->tp->mode != 0; }
-
-void tp_comm_free(mmada_handle* h) {
-    TpComm* c = h->tp;
-    if (!c) return;
-    for (int j = 0; j < TP_MAX; ++j)
-        for (int b = 0; b < 4; ++b)
-            if (c->opened[b][j]) (void)hipIpcCloseMemHandle(c->opened[b][j]);
-    if (c->comm && c->nccl.CommDestroy) (void)c->nccl.CommDestroy(c->comm);
-    for (int k = 0; k < 2; ++k) {
-        if (c->ev_g[k]) (void)hipEventDestroy(c->ev_g[k]);
-        if (c->ev_c[k]) (void)hipEventDestroy(c->ev_c[k]);
-    }
-    if (c->sc) (void)hipStreamDestroy(c->sc);
-    if (c->s_cmp) (void)hipStreamDestroy(c->s_cmp);
-    if (c->ev_in) (void)hipEventDestroy(c->ev_in);
-    if (c->ev_out) (void)hipEventDestroy(c->ev_out);
-    (void)hipFree(c->stage);
-    (void)hipFree(c->part); (void)hipFree(c->hn_pub); (void)hipFree(c->ctr);
-    (void)hipFree(c->rs_tmp); (void)hipFree(c->stats_pub); (void)hipFree(c->stats_all); (void)hipFree(c->head_buf);
-    (void)hipFree(c->score_all);
-    delete c;
-    h->tp = nullptr;
-}
-
-extern "C" {
-
-int mmada_comm_export_bytes(void) { return (int)sizeof(CommExport); }
-
-int mmada_comm_create(mmada_handle* h, int max_rows, void* export_out) {
-    if (!h || max_rows <= 0) return mm_fail("mmada_comm_create: bad argument");
-    // tp_size == 1 behind mmada_set_option("tp_allow_single_rank", 1): a one-rank group runs EVERY line of the exchange (RCCL
-    // reduce-scatter / all-gather of one rank are copies, the pull transport has no peer to wait for) and must reproduce the
-    // plain forward bit for bit — the test that executes the RCCL transport without a second GPU (tests/test_gpu_tp.py)
-    if ((h->cfg.tp_size < 2 && !(h->cfg.tp_size == 1 && switches().tp_allow_single_rank)) || h->cfg.tp_size > TP_MAX)
-        return mm_fail("mmada_comm_create: tp_size must be 2..%d", TP_MAX);
-    if (h->tp) tp_comm_free(h);
-    TpComm* c = new TpComm();
     c->rank = h->cfg.tp_rank; c->size = h->cfg.tp_size; c->d = h->cfg.d_model;
     c->max_rows = max_rows;
     const size_t rows = (size_t)max_rows + 8 * c->size;
@@ -742,15 +375,12 @@ int mmada_comm_create(mmada_handle* h, int max_rows, void* export_out) {
     MM_CHECK_HIP(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
     MM_CHECK_HIP(hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
     // the scoring head's record buffers are sized here, once: a call never allocates (and so never synchronises the host)
-    c->score_round = min(SCORE_ROUND, (max_rows + 7) / 8 * 8);
-    c->score_tiles = ((h->cfg.vocab + SCORE_BN - 1) / SCORE_BN + c->size - 1) / c->size;
-    c->score_buf_bytes = align_up((size_t)c->score_round * 4 + (size_t)c->score_tiles * c->score_round * 16, 256);
-    const size_t text_bytes = (size_t)STAT_ROWS * sizeof(TextStat), stat_bytes = text_bytes + 2 * c->score_buf_bytes;
-    if (stat_bytes >= (1ull << 32)) return mm_fail("mmada_comm_create: %zu bytes of published records exceed 4 GiB", stat_bytes);
-    MM_CHECK_HIP(alloc_pub((void**)&c->stats_pub, stat_bytes, true, nullptr));
-    MM_CHECK_HIP(hipMemset(c->stats_pub, 0, stat_bytes));
-    for (int b = 0; b < 2; ++b) c->score_pub[b] = (char*)c->stats_pub + text_bytes + (size_t)b * c->score_buf_bytes;
-    MM_CHECK_HIP(hipMalloc(&c->score_all, (size_t)c->size * c->score_buf_bytes));
+    c->score = score_layout(max_rows, h->cfg.vocab, c->size);
+    if (c->score.total >= (1ull << 32)) return mm_fail("mmada_comm_create: %zu bytes of published records exceed 4 GiB", c->score.total);
+    MM_CHECK_HIP(alloc_pub((void**)&c->stats_pub, c->score.total, true, nullptr));
+    MM_CHECK_HIP(hipMemset(c->stats_pub, 0, c->score.total));
+    for (int b = 0; b < 2; ++b) c->score_pub[b] = (char*)c->stats_pub + c->score.text_bytes + (size_t)b * c->score.buf_bytes;
+    MM_CHECK_HIP(hipMalloc(&c->score_all, (size_t)c->size * c->score.buf_bytes));
     MM_CHECK_HIP(hipMalloc(&c->stats_all, (size_t)c->size * STAT_ROWS * sizeof(TextStat)));
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // the exchange must not queue behind a whole round of GEMM workgroups
@@ -763,20 +393,173 @@ int mmada_comm_create(mmada_handle* h, int max_rows, void* export_out) {
     c->chunks = e ? atoi(e) : 2;
     c->timeout = default_timeout_ticks();
     MM_CHECK_HIP(hipDeviceSynchronize());
-    h->tp = c;
     if (export_out) {
         CommExport ex;
         memset(&ex, 0, sizeof(ex));
-        hipError_t e1 = hipIpcGetMemHandle(&ex.part, c->part), e2 = hipIpcGetMemHandle(&ex.hn, c->hn_pub),
-                   e3 = hipIpcGetMemHandle(&ex.ctr, c->ctr);
-        if (e3 == hipSuccess) e3 = hipIpcGetMemHandle(&ex.stats, c->stats_pub);
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+        void* own[PUB_COUNT];
+        own_pubs(c, own);
+        for (int b = 0; b < PUB_COUNT; ++b) {
+            const hipError_t e = hipIpcGetMemHandle(&ex.buf[b], own[b]);
+            if (e == hipSuccess) continue;
             (void)hipGetLastError();
             memset(export_out, 0, sizeof(ex));
             return mm_fail("mmada_comm_create: hipIpcGetMemHandle failed (%s): peers in other processes cannot map this rank; "
-                           "use mmada_comm_connect_rccl", hipGetErrorString(e1 != hipSuccess ? e1 : (e2 != hipSuccess ? e2 : e3)));
+                           "use mmada_comm_connect_rccl", hipGetErrorString(e));
         }
         memcpy(export_out, &ex, sizeof(ex));
+    }
+    return 0;
+}
+
+}  // namespace
+
+// ---- forward ---------------------------------------------------------------------------------------------------------
+// All blocks of a tensor-parallel forward.  h->x holds the embeddings (replicated), every rank keeps its own rows of the
+// residual stream from here on.  Compute on `s`, exchanges on the library's second stream.
+static int tp_forward_body_on(mmada_handle* h, hipStream_t s);
+
+int tp_forward_body(mmada_handle* h, hipStream_t s_user) {
+    TpComm* c = h->tp;
+    if (!c || c->mode == TP_NONE) return mm_fail("tensor-parallel forward: no transport connected (mmada_comm_create + connect)");
+    if (!c->s_cmp) return tp_forward_body_on(h, s_user);
+    // CU partition: the blocks run on the library's masked compute stream, forked from and joined to the caller's stream
+    MM_CHECK_HIP(hipEventRecord(c->ev_in, s_user));
+    MM_CHECK_HIP(hipStreamWaitEvent(c->s_cmp, c->ev_in, 0));
+    const int rc = tp_forward_body_on(h, c->s_cmp);
+    MM_CHECK_HIP(hipEventRecord(c->ev_out, c->s_cmp));
+    MM_CHECK_HIP(hipStreamWaitEvent(s_user, c->ev_out, 0));
+    return rc;
+}
+
+static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
+    TpComm* c = h->tp;
+    if (h->M > c->max_rows) return mm_fail("tensor-parallel forward: %d rows exceed the comm buffers (%d)", h->M, c->max_rows);
+    const int d = h->cfg.d_model, M = h->M, nl = h->cfg.n_layers;
+    if ((d >> 3) > 64 * MAXCH) return mm_fail("tensor-parallel forward: d_model > %d is not supported", 64 * MAXCH * 8);
+    const ChunkPlan plan = chunk_plan(c, M);
+    const double rows_real = (double)h->B * h->L / M;  // fraction of stream rows that are not padding (FLOP accounting)
+    // first RMSNorm of the forward: the embeddings are replicated, no exchange needed
+    if (h->xn_is_layer0) h->xn_is_layer0 = false;  // fused into the embedding kernel
+    else if (launch_rmsnorm(h->x, h->layers[0].attn_norm, h->xn, M, d, h->cfg.rms_eps, s)) return 1;
+    bool pending[2] = {false, false};  // chunk k's xn rows are being produced on the exchange stream
+    using ArgsOf = GemmArgs (*)(const mmada_handle*, int, int, int);  // handle.h: qkv_args, gate_up_args, attn_out_args, down_args
+    // a column-parallel GEMM (ProfScope kind `kind`) chunk by chunk: wait for the chunk's xn rows, multiply
+    auto column_parallel = [&](int layer, int kind, int epi, ArgsOf args_of) -> int {
+        for (int k = 0; k < plan.n; ++k) {
+            if (pending[k]) {
+                MM_CHECK_HIP(hipStreamWaitEvent(s, c->ev_c[k], 0));
+                pending[k] = false;
+            }
+            const GemmArgs g = args_of(h, layer, plan.sl[k].m0, plan.sl[k].m1 - plan.sl[k].m0);
+            ProfScope p(h, layer, kind, 2.0 * g.M * rows_real * g.N * g.K, s);
+            if (launch_gemm(epi, g, s)) return 1;
+        }
+        return 0;
+    };
+    // a row-parallel GEMM into c->part chunk by chunk; chunk k's exchange (RMSNorm weight w) runs on the exchange stream under
+    // chunk k+1's GEMM
+    auto row_parallel = [&](int layer, int kind, ArgsOf args_of, const bf16_t* w) -> int {
+        for (int k = 0; k < plan.n; ++k) {
+            GemmArgs o = args_of(h, layer, plan.sl[k].m0, plan.sl[k].m1 - plan.sl[k].m0);
+            o.C = c->part + (size_t)plan.sl[k].m0 * d; o.publish = peers_mapped(c);
+            {
+                ProfScope p(h, layer, kind, 2.0 * o.M * rows_real * o.N * o.K, s);
+                if (launch_gemm(EPI_STORE, o, s)) return 1;
+            }
+            MM_CHECK_HIP(hipEventRecord(c->ev_g[k], s));
+            MM_CHECK_HIP(hipStreamWaitEvent(c->sc, c->ev_g[k], 0));
+            if (exchange(h, plan.sl[k], w, c->sc)) return 1;
+            MM_CHECK_HIP(hipEventRecord(c->ev_c[k], c->sc));
+            pending[k] = true;
+        }
+        return 0;
+    };
+    for (int layer = 0; layer < nl; ++layer) {
+        // q/k/v (column-parallel: this rank's heads), RoPE in the epilogue; a dLLM cache step writes this rank's heads of the
+        // block's keys / values into the slot
+        if (column_parallel(layer, 0, EPI_QKV, qkv_args)) return 1;
+        // attention over this rank's heads: the one join point (every key of a sequence)
+        if (block_attention(h, layer, s)) return 1;
+        if (row_parallel(layer, 2, attn_out_args, h->layers[layer].ff_norm)) return 1;
+        // gate/up (column-parallel) + SiLU*mul, then down (row-parallel)
+        if (column_parallel(layer, 3, EPI_SWIGLU, gate_up_args)) return 1;
+        if (row_parallel(layer, 4, down_args, layer + 1 < nl ? h->layers[layer + 1].attn_norm : h->ln_f)) return 1;
+    }
+    for (int k = 0; k < plan.n; ++k)
+        if (pending[k]) MM_CHECK_HIP(hipStreamWaitEvent(s, c->ev_c[k], 0));
+    h->xn_is_final = true;  // xn = ln_f(x) on every row
+    return 0;
+}
+
+// Residual stream of every owner -> full [M, d] (parity taps; the forward itself never moves the residual stream)
+int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s) {
+    TpComm* c = h->tp;
+    if (!transport_connected(c)) return mm_fail("tp_gather_stream: no transport connected (or the no-exchange diagnostic is on)");
+    const int d = h->cfg.d_model;
+    const ChunkPlan plan = chunk_plan(c, h->M);
+    for (int k = 0; k < plan.n; ++k) {
+        const Slice& sl = plan.sl[k];
+        const int own = sl.r1 - sl.r0;
+        if (own > 0) {
+            hipLaunchKernelGGL(copy_rows_kernel, dim3((own + 3) / 4), dim3(256), 0, s, h->x, c->hn_pub, sl.r0, sl.r1, d);
+            hipLaunchKernelGGL(copy_rows_kernel, dim3((own + 3) / 4), dim3(256), 0, s, h->x, full_out, sl.r0, sl.r1, d);
+        }
+        if (peers_mapped(c)) {
+            if (signal_wait(c, s)) return 1;
+            hipLaunchKernelGGL(tp_gather_kernel, dim3((sl.m1 - sl.m0 + 3) / 4), dim3(256), 0, s, c->peers, c->rank, sl.m0,
+                               sl.m1, sl.slice, d, full_out, 0);
+            if (signal_wait(c, s)) return 1;  // hn_pub may be overwritten only after every peer has pulled
+        } else {
+            ncclResult_t r = c->nccl.AllGather(c->hn_pub + (size_t)(sl.m0 + c->rank * sl.slice) * d,
+                                               full_out + (size_t)sl.m0 * d, (size_t)sl.slice * d, ncclBfloat16, c->comm, s);
+            if (r != ncclSuccess) return nccl_fail(c, "ncclAllGather", r);
+        }
+        MM_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+bool tp_comm_connected(const mmada_handle* h) { return h->tp && h->tp->mode != TP_NONE; }
+
+void tp_comm_free(mmada_handle* h) {
+    TpComm* c = h->tp;
+    if (!c) return;
+    for (int j = 0; j < TP_MAX; ++j)
+        for (int b = 0; b < PUB_COUNT; ++b)
+            if (c->opened[j][b]) (void)hipIpcCloseMemHandle(c->opened[j][b]);
+    if (c->comm && c->nccl.CommDestroy) (void)c->nccl.CommDestroy(c->comm);
+    for (int k = 0; k < 2; ++k) {
+        if (c->ev_g[k]) (void)hipEventDestroy(c->ev_g[k]);
+        if (c->ev_c[k]) (void)hipEventDestroy(c->ev_c[k]);
+    }
+    if (c->sc) (void)hipStreamDestroy(c->sc);
+    if (c->s_cmp) (void)hipStreamDestroy(c->s_cmp);
+    if (c->ev_in) (void)hipEventDestroy(c->ev_in);
+    if (c->ev_out) (void)hipEventDestroy(c->ev_out);
+    (void)hipFree(c->stage);
+    (void)hipFree(c->part); (void)hipFree(c->hn_pub); (void)hipFree(c->ctr);
+    (void)hipFree(c->rs_tmp); (void)hipFree(c->stats_pub); (void)hipFree(c->stats_all); (void)hipFree(c->head_buf);
+    (void)hipFree(c->score_all);
+    delete c;
+    h->tp = nullptr;
+}
+
+extern "C" {
+
+int mmada_comm_export_bytes(void) { return (int)sizeof(CommExport); }
+
+int mmada_comm_create(mmada_handle* h, int max_rows, void* export_out) {
+    if (!h || max_rows <= 0) return mm_fail("mmada_comm_create: bad argument");
+    // tp_size == 1 behind mmada_set_option("tp_allow_single_rank", 1): a one-rank group runs EVERY line of the exchange (RCCL
+    // reduce-scatter / all-gather of one rank are copies, the pull transport has no peer to wait for) and must reproduce the
+    // plain forward bit for bit — the test that executes the RCCL transport without a second GPU (tests/test_gpu_tp.py)
+    if ((h->cfg.tp_size < 2 && !(h->cfg.tp_size == 1 && switches().tp_allow_single_rank)) || h->cfg.tp_size > TP_MAX)
+        return mm_fail("mmada_comm_create: tp_size must be 2..%d", TP_MAX);
+    if (h->tp) tp_comm_free(h);
+    h->tp = new TpComm();  // the handle owns it from here: a failing exit releases everything allocated so far (the error message stays)
+    if (comm_init(h, max_rows, export_out)) {
+        tp_comm_free(h);
+        return 1;
     }
     return 0;
 }
@@ -785,25 +568,22 @@ int mmada_comm_connect_ipc(mmada_handle* h, const void* exports) {
     if (!h || !h->tp || !exports) return mm_fail("mmada_comm_connect_ipc: call mmada_comm_create first");
     TpComm* c = h->tp;
     const CommExport* ex = (const CommExport*)exports;
+    void* own[PUB_COUNT];
+    own_pubs(c, own);
     for (int j = 0; j < c->size; ++j) {
-        if (j == c->rank) {
-            c->peers.part[j] = c->part; c->peers.hn[j] = c->hn_pub; c->peers.ctr[j] = c->ctr; c->peers.stats[j] = c->stats_pub;
-            continue;
-        }
-        void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-        const hipIpcMemHandle_t* hd[4] = {&ex[j].part, &ex[j].hn, &ex[j].ctr, &ex[j].stats};
-        for (int b = 0; b < 4; ++b) {
-            hipError_t e = hipIpcOpenMemHandle(&p[b], *hd[b], hipIpcMemLazyEnablePeerAccess);
+        if (j == c->rank) { set_peer(c->peers, j, own); continue; }
+        for (int b = 0; b < PUB_COUNT; ++b) {
+            void* p = nullptr;
+            hipError_t e = hipIpcOpenMemHandle(&p, ex[j].buf[b], hipIpcMemLazyEnablePeerAccess);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 return mm_fail("mmada_comm_connect_ipc: hipIpcOpenMemHandle(rank %d, buffer %d): %s", j, b, hipGetErrorString(e));
             }
-            c->opened[b][j] = p[b];
+            c->opened[j][b] = p;
         }
-        c->peers.part[j] = (const bf16_t*)p[0]; c->peers.hn[j] = (const bf16_t*)p[1]; c->peers.ctr[j] = (const uint32_t*)p[2];
-        c->peers.stats[j] = (const TextStat*)p[3];
+        set_peer(c->peers, j, c->opened[j]);
     }
-    c->mode = 1;
+    c->mode = TP_PULL;
     return 0;
 }
 
@@ -813,10 +593,11 @@ int mmada_comm_connect_local(mmada_handle* h, mmada_handle* const* ranks) {
     for (int j = 0; j < c->size; ++j) {
         if (!ranks[j] || !ranks[j]->tp) return mm_fail("mmada_comm_connect_local: rank %d has no comm", j);
         if (ranks[j]->cfg.tp_rank != j) return mm_fail("mmada_comm_connect_local: handle %d is tp_rank %d", j, ranks[j]->cfg.tp_rank);
-        c->peers.part[j] = ranks[j]->tp->part; c->peers.hn[j] = ranks[j]->tp->hn_pub; c->peers.ctr[j] = ranks[j]->tp->ctr;
-        c->peers.stats[j] = ranks[j]->tp->stats_pub;
+        void* theirs[PUB_COUNT];
+        own_pubs(ranks[j]->tp, theirs);
+        set_peer(c->peers, j, theirs);
     }
-    c->mode = 1;
+    c->mode = TP_PULL;
     return 0;
 }
 
@@ -839,7 +620,7 @@ int mmada_comm_connect_rccl(mmada_handle* h, const void* unique_id128, const cha
     memcpy(&id, unique_id128, sizeof(id));
     ncclResult_t r = c->nccl.CommInitRank(&c->comm, c->size, id, c->rank);
     if (r != ncclSuccess) return nccl_fail(c, "ncclCommInitRank", r);
-    c->mode = 2;
+    c->mode = TP_RCCL;
     MM_CHECK_HIP(hipMemset(c->err, 0, sizeof(int)));  // a failed attempt with the pull transport must not stick to this one
     return 0;
 }
@@ -875,14 +656,14 @@ int mmada_comm_status(mmada_handle* h, int* mode_out, int* err_out, int* finegra
 int mmada_comm_set_mode(mmada_handle* h, int mode) {
     if (!h || !h->tp) return mm_fail("mmada_comm_set_mode: no comm");
     TpComm* c = h->tp;
+    if (mode < TP_PULL || mode > TP_COPY) return mm_fail("mmada_comm_set_mode: mode must be 1 (pull), 2 (RCCL), 3 (diagnostic: no exchange) or 4 (copy engines)");
     const int other = c->size == 1 ? 0 : (c->rank == 0 ? 1 : 0);
-    if (mode == 1 && !c->peers.ctr[other]) return mm_fail("mmada_comm_set_mode: the pull transport was never connected");
-    if (mode == 2 && !c->comm) return mm_fail("mmada_comm_set_mode: the RCCL transport was never connected");
-    if (mode == 3 && c->mode == 0) return mm_fail("mmada_comm_set_mode: connect a transport before the no-exchange diagnostic");
-    if (mode == 4 && !c->peers.ctr[other]) return mm_fail("mmada_comm_set_mode: the copy transport needs the mapped peer buffers (connect_ipc / connect_local)");
-    if (mode < 1 || mode > 4) return mm_fail("mmada_comm_set_mode: mode must be 1 (pull), 2 (RCCL), 3 (diagnostic: no exchange) or 4 (copy engines)");
-    if (mode == 4 && !c->stage) MM_CHECK_HIP(hipMalloc(&c->stage, c->stage_stride * c->size * 2));  // pull / RCCL users never pay for it
-    c->mode = mode;
+    if (mode == TP_PULL && !c->peers.ctr[other]) return mm_fail("mmada_comm_set_mode: the pull transport was never connected");
+    if (mode == TP_RCCL && !c->comm) return mm_fail("mmada_comm_set_mode: the RCCL transport was never connected");
+    if (mode == TP_NO_EXCHANGE && c->mode == TP_NONE) return mm_fail("mmada_comm_set_mode: connect a transport before the no-exchange diagnostic");
+    if (mode == TP_COPY && !c->peers.ctr[other]) return mm_fail("mmada_comm_set_mode: the copy transport needs the mapped peer buffers (connect_ipc / connect_local)");
+    if (mode == TP_COPY && !c->stage) MM_CHECK_HIP(hipMalloc(&c->stage, c->stage_stride * c->size * 2));  // pull / RCCL users never pay for it
+    c->mode = (TpMode)mode;
     return 0;
 }
 
@@ -953,56 +734,8 @@ int mmada_comm_exchange(mmada_handle* h, const void* norm_w, void* stream) {
     if (!h || !h->tp || h->M == 0 || !norm_w) return mm_fail("mmada_comm_exchange: need a comm and a resident carve (mmada_embed)");
     const Slice sl = chunk_slice(h->M, h->tp->size, h->tp->rank, 1, 0);
     h->xn_is_layer0 = false;  // xn is about to be overwritten
-    if (h->tp->mode == 1 || h->tp->mode == 4) hipLaunchKernelGGL(tp_flush_kernel, dim3(256), dim3(64), 0, (hipStream_t)stream);
+    if (peers_mapped(h->tp)) hipLaunchKernelGGL(tp_flush_kernel, dim3(256), dim3(64), 0, (hipStream_t)stream);
     return exchange(h, sl, (const bf16_t*)norm_w, (hipStream_t)stream);
-}
-
-/* Vocabulary-parallel text step (generators/parallel_generator.py:185-217 at text_temperature == 0) after a
- * tensor-parallel forward: this rank multiplies the ln_f rows by ITS slice of ff_out.weight (vocab / tp_size columns; the
- * [B*T, vocab] logits exist nowhere), reduces each row to {max, first arg-max, fp64 sum-exp}, the tp records are exchanged
- * (16 bytes per row and rank) and combined, and the k[b] most confident masked positions are committed on every rank.
- * rows: device int32 [B*T] = b*L + text_start + t.  scratch: device, >= B*T*16 bytes (receives conf f64 / x0 i32). */
-int mmada_text_select_tp(mmada_handle* h, const int32_t* rows, int B, int T, int64_t* ids, int L, int text_start,
-                         const int32_t* k, void* scratch, void* stream) {
-    if (!h || !h->tp || h->tp->mode == 0 || h->tp->mode == 3) return mm_fail("mmada_text_select_tp: no tensor-parallel transport connected");
-    if (!h->xn_is_final || h->M == 0) return mm_fail("mmada_text_select_tp: no tensor-parallel forward resident");
-    if (!rows || !ids || !k || !scratch) return mm_fail("mmada_text_select_tp: null argument");
-    TpComm* c = h->tp;
-    const int R = B * T;
-    if (R <= 0) return 0;
-    if (R > STAT_ROWS || R > h->B * h->L) return mm_fail("mmada_text_select_tp: %d rows exceed the limit", R);
-    if (text_start < 0 || text_start + T > L) return mm_fail("mmada_text_select_tp: text span outside the sequence");
-    hipStream_t s = (hipStream_t)stream;
-    const int d = h->cfg.d_model, V = h->cfg.vocab;
-    const int w = ((V + c->size - 1) / c->size + 7) / 8 * 8;
-    const int v0 = min(V, c->rank * w), v1 = min(V, v0 + w);
-    const size_t need = (size_t)R * w * 2;
-    if (need > c->head_bytes) {  // first use (or a larger batch): not capturable, like every first call
-        (void)hipFree(c->head_buf);
-        c->head_buf = nullptr; c->head_bytes = 0;
-        MM_CHECK_HIP(hipMalloc(&c->head_buf, need));
-        c->head_bytes = need;
-    }
-    if (tp_head_gather(h, rows, R, s)) return 1;
-    if (v1 > v0) {
-        if (launch_gemm(EPI_STORE, gemm_bt_args(h->xg, h->lm_head + (size_t)v0 * d, c->head_buf, R, v1 - v0, d, w), s)) return 1;
-    }
-    if (launch_text_stats_partial(c->head_buf, B, T, v1 - v0, w, v0, ids, L, text_start, h->cfg.mask_token_id, c->stats_pub, s))
-        return 1;
-    double* conf = (double*)scratch;
-    int32_t* x0 = (int32_t*)((char*)scratch + (size_t)R * 8);
-    if (c->mode == 1 || c->mode == 4) {
-        if (signal_wait(c, s)) return 1;
-        hipLaunchKernelGGL(tp_text_combine_kernel, dim3((R + 255) / 256), dim3(256), 0, s, c->peers, c->size, c->rank,
-                           c->stats_pub, (const TextStat*)nullptr, 0, R, conf, x0);
-    } else {
-        ncclResult_t r = c->nccl.AllGather(c->stats_pub, c->stats_all, (size_t)R * sizeof(TextStat), ncclUint8, c->comm, s);
-        if (r != ncclSuccess) return nccl_fail(c, "ncclAllGather", r);
-        hipLaunchKernelGGL(tp_text_combine_kernel, dim3((R + 255) / 256), dim3(256), 0, s, c->peers, c->size, c->rank,
-                           c->stats_pub, c->stats_all, R, R, conf, x0);
-    }
-    MM_CHECK_HIP(hipGetLastError());
-    return launch_text_commit(scratch, B, T, ids, L, text_start, k, s);
 }
 
 int mmada_comm_destroy(mmada_handle* h) {
@@ -1011,101 +744,3 @@ int mmada_comm_destroy(mmada_handle* h) {
 }
 
 }  // extern "C"
-
-// Vocabulary-parallel scoring head (mmada_head_logprobs on a connected handle).  The launch's 256-column tiles are split over
-// the ranks in contiguous blocks (tp.py: score_tile_slice); each rank runs the one-rank EPI_ROWSTAT launch on its own tiles —
-// the same columns, col0-based arg-max indices and partial last tile, hence the same records — into a published buffer, the
-// ranks hand off, and every rank joins every row with the fold of the one-rank head.  Rows go in rounds of c->score_round.
-//
-// Buffer reuse (write after read).  A rank writes round i's records while a slower peer may still be joining an earlier
-// round, in this call or in the previous one (two calls with no forward between them are legal).  The two published buffers
-// alternate from round to round, ACROSS calls (c->score_flip; every rank makes the same calls, so the ranks agree on it).
-// Round i + 2 is the next writer of round i's buffer.  This rank enqueues those writes behind its wait of hand-off i + 1;
-// that wait returns only after every peer has signalled hand-off i + 1; a peer enqueues that signal behind its own join of
-// round i (same stream), and a kernel starts only after its predecessor in the stream has retired.  So every peer's reads of
-// round i are over before the first write of round i + 2 — whatever hand-off "i + 1" is: the next round's, the next call's,
-// or one of a forward in between.  A graph replay breaks the alternation (the buffer choice is frozen into the graph, and
-// eager calls and replays interleave freely), so a captured call brackets itself with a hand-off of its own at both ends:
-// behind the first every earlier join has retired, and nothing later writes before the last.  The RCCL transport needs neither
-// argument: an all-gather completes on a rank only when its send buffer may be reused.
-int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
-                     float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s) {
-    TpComm* c = h->tp;
-    if (!c || c->mode == 0 || c->mode == 3) return mm_fail("mmada_head_logprobs: no tensor-parallel transport connected");
-    if (!h->xn_is_final || h->M == 0) return mm_fail("mmada_head_logprobs: no tensor-parallel forward resident");
-    if (R <= 0) return 0;
-    if (R > c->max_rows)
-        return mm_fail("mmada_head_logprobs: %d rows exceed the %d rows this handle's comm was created for (mmada_comm_create max_rows)",
-                       R, c->max_rows);
-    if (R > h->B * h->L) return mm_fail("mmada_head_logprobs: R=%d exceeds B*L=%d", R, h->B * h->L);
-    if (col_begin < 0 || col_end > h->cfg.vocab || col_begin >= col_end) return mm_fail("mmada_head_logprobs: bad column range");
-    const int d = h->cfg.d_model, tp = c->size;
-    const int ntn = (col_end - col_begin + SCORE_BN - 1) / SCORE_BN, q = (ntn + tp - 1) / tp;
-    if (q > c->score_tiles) return mm_fail("mmada_head_logprobs: %d tiles per rank exceed the record buffers (%d)", q, c->score_tiles);
-    auto tiles_of = [&](int j) { return min(ntn, (j + 1) * q) - min(ntn, j * q); };
-    const int t0 = min(ntn, c->rank * q), nt_own = tiles_of(c->rank);
-    const int c0 = col_begin + t0 * SCORE_BN, n_own = nt_own > 0 ? min(col_end, c0 + nt_own * SCORE_BN) - c0 : 0;
-    const bool mapped = c->mode == 1 || c->mode == 4;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    const bool bracket = mapped && cs != hipStreamCaptureStatusNone;
-    const uint32_t rec_off = (uint32_t)c->score_round * 4u;
-    const size_t text_bytes = (size_t)STAT_ROWS * sizeof(TextStat);
-    if (tp_head_gather(h, rows, R, s)) return 1;
-    if (bracket && signal_wait(c, s)) return 1;
-    for (int r0 = 0; r0 < R; r0 += c->score_round) {
-        const int rr = min(c->score_round, R - r0), rp = (rr + 7) / 8 * 8;
-        char* buf = c->score_pub[c->score_flip];
-        float* tx = (float*)buf;
-        hipLaunchKernelGGL(tp_score_reset_kernel, dim3((rp + 255) / 256), dim3(256), 0, s, tx, rp);
-        MM_CHECK_HIP(hipGetLastError());
-        if (n_own > 0) {
-            GemmArgs g = gemm_bt_args(h->xg + (size_t)r0 * d, h->lm_head + (size_t)c0 * d, nullptr, rp, n_own, d, 8);
-            set_rowstat_args(g, RowStatArgs{(float4*)(buf + rec_off), tx, targets + r0, rr, rp, c0});
-            g.publish = mapped;
-            if (launch_gemm(EPI_ROWSTAT, g, s)) return 1;
-        }
-        ScoreJoinArgs a{};
-        a.sys = c->mode == 1; a.size = tp; a.rank = c->rank; a.q = q; a.rec_off = rec_off; a.ld = rp; a.ntn = ntn; a.R = rr;
-        a.col_begin = col_begin; a.col_end = col_end; a.targets = targets + r0;
-        a.logprob = logprob + r0; a.lse = lse ? lse + r0 : nullptr; a.argmax = argmax ? argmax + r0 : nullptr;
-        a.vmax = vmax ? vmax + r0 : nullptr;
-        if (mapped) {
-            if (signal_wait(c, s)) return 1;  // every rank's records of this round are complete
-            for (int j = 0; j < tp; ++j) {
-                const char* peer = (const char*)c->peers.stats[j] + text_bytes + (size_t)c->score_flip * c->score_buf_bytes;
-                if (j == c->rank) a.src[j] = buf;
-                else if (c->mode == 1) a.src[j] = peer;
-                else {  // copy engines: the peer's target logits and records of ITS tiles -> local staging
-                    char* dst = c->score_all + (size_t)j * c->score_buf_bytes;
-                    if (tiles_of(j) > 0)
-                        MM_CHECK_HIP(hipMemcpyAsync(dst, peer, (size_t)rec_off + (size_t)tiles_of(j) * rp * 16, hipMemcpyDefault, s));
-                    a.src[j] = dst;
-                }
-            }
-        } else {
-            const size_t cnt = (size_t)rec_off + (size_t)q * rp * 16;  // equal counts: a rank with fewer tiles sends stale bytes nobody reads
-            ncclResult_t r = c->nccl.AllGather(buf, c->score_all, cnt, ncclUint8, c->comm, s);
-            if (r != ncclSuccess) return nccl_fail(c, "ncclAllGather", r);
-            for (int j = 0; j < tp; ++j) a.src[j] = j == c->rank ? buf : c->score_all + (size_t)j * cnt;
-        }
-        hipLaunchKernelGGL(tp_score_join_kernel, dim3((rr + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, a);
-        MM_CHECK_HIP(hipGetLastError());
-        c->score_flip ^= 1;
-    }
-    if (bracket && signal_wait(c, s)) return 1;
-    return 0;
-}
-
-int tp_gather_rows(const bf16_t* src, const int32_t* rows, int R, int L, int Lp, int d, int nflat, bf16_t* out, hipStream_t s) {
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, s, src, rows, R, L, Lp, d, nflat, out);
-    MM_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int tp_head_gather(mmada_handle* h, const int32_t* rows, int R, hipStream_t s) {
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, s, h->xn, rows, R, h->L, h->Lp, h->cfg.d_model,
-                       h->B * h->L, h->xg);
-    MM_CHECK_HIP(hipGetLastError());
-    return 0;
-}

@@ -249,6 +249,12 @@ def test_single_rank_group_runs_the_whole_transport_and_equals_the_plain_forward
         abi.check(lib.mmada_comm_set_mode(m._handle, MODE_NO_EXCHANGE), "set_mode")
         with pytest.raises(abi.MmadaError):
             check_tp_exchange(m)
+        # ... and its values: with ONE rank "own partial only" is the whole sum, so this branch of the exchange too must
+        # reproduce the plain forward bit for bit
+        m.forward_body(ids)
+        diag_l = m.head_rows(rows, synth.TEXT_VOCAB, synth.TEXT_VOCAB + 512)
+        torch.cuda.synchronize()
+        assert torch.equal(diag_l, ref_logits), f"{transport}: no-exchange diagnostic of a one-rank group: logits differ"
         abi.check(lib.mmada_comm_set_mode(m._handle, MODE_OF[transport]), "set_mode")
         from helpers import save_parity
 

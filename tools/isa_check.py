@@ -344,7 +344,7 @@ def check_tp_score_join(asm=None):
     """The join of the vocabulary-parallel scoring head (tp_score_join_kernel): a peer's records arrive as single 16-byte
     system-scope loads through descriptors held in SGPRs (no waterfall loop), nothing spills, and the fold is the shared one
     (rowstat_fold.h: its three 16 x 16 LDS arrays)."""
-    asm = asm or device_asm("tp_comm.hip")
+    asm = asm or device_asm("tp_heads.hip")
     body, meta = kernels(asm)
     report, errors = [], []
     for name, lines in body.items():
