@@ -72,6 +72,15 @@ MM_DEVICE int vt_key_pos(int l) {
 
 int mm_fail(const char* fmt, ...);
 
+// `s` is under hipGraph capture, so the caller must not allocate, synchronise or record events on it.  A query that fails
+// counts as capturing (the cautious answer) and its HIP error is cleared.
+inline bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess) return cs != hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+    return true;
+}
+
 // Function attributes (the dynamic-LDS limit of a kernel) are per DEVICE: a process that drives several devices (the ranks of
 // a tensor-parallel group as handles of one process) must set them on each.  MM_ONCE_PER_DEVICE(once, stmts) runs `stmts`
 // the first time a launcher runs on the current device and marks the device only AFTER every statement succeeded (an

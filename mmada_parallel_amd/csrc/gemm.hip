@@ -296,11 +296,7 @@ static int device_consts(DeviceConsts* out, hipStream_t s) {
     MM_CHECK_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= 16) return 0;
     if (!ready[dev].load(std::memory_order_acquire)) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-            (void)hipGetLastError();
-            return 0;
-        }
+        if (stream_capturing(s)) return 0;
         std::lock_guard<std::mutex> lock(mu);
         if (!ready[dev].load(std::memory_order_acquire)) {
             bf16_t* zero = nullptr;

@@ -1,4 +1,5 @@
-// handle.h — the library's private state behind the opaque mmada_handle (shared by api.hip and the tensor-parallel units).
+// handle.h — the library's private state behind the opaque mmada_handle (shared by api.hip, forward.hip, cache.hip, heads.hip
+// and the tensor-parallel units).
 #pragma once
 #include <utility>
 #include <vector>
@@ -33,6 +34,26 @@ struct CacheSlot {
 };
 constexpr int MMADA_CACHE_SLOTS = 16;
 
+// Which forward is resident in the workspace (mmada_handle::res).  One rule, for every entry point:
+//   - a call that fails BEFORE it has written to the workspace leaves the resident forward as it was;
+//   - a call that fails AFTER that leaves none resident.
+// (A cache step and mmada_sdpa leave none resident when they succeed, too: what they wrote is not a plain forward.)
+struct Resident {
+    int B = 0, L = 0, Lp = 0, Lkv = 0;
+    int M = 0;   // stream rows B * Lp; 0: nothing is resident — read through resident(h), cleared through invalidate(h)
+    // consumed-row window (mmada_set_consumed_rows): while a forward whose last block ran windowed is resident, the stream is
+    // compact: cur_W rows per sequence starting at row cur_beg, Mcur rows in all (no window: cur_W = 0, Mcur = M)
+    int cur_W = 0, cur_beg = 0, Mcur = 0;
+    // xn already holds ln_f(x) for every row (the last reduce-scatter of a tensor-parallel forward applies ln_f on the owned rows)
+    bool xn_is_final = false;
+    bool xn_is_layer0 = false;  // mmada_embed already wrote xn = RMSNorm(x) * blocks[0].attn_norm (fused, K1)
+    // dLLM cache: the slot a forward in flight writes its keys / values into (non-null only inside a CacheStep); cc_pos: position
+    // map of a compute-mask step (null: every row is computed); cc_qshift >= 0: queries are rotated by row index + shift
+    const CacheSlot* cc = nullptr;
+    const int32_t* cc_pos = nullptr;
+    int cc_qshift = -1;
+};
+
 struct mmada_handle {
     mmada_cfg cfg;
     int hq_l, hkv_l, f_l;  // per-rank heads / mlp columns
@@ -46,38 +67,43 @@ struct mmada_handle {
     // workspace
     char* ws = nullptr;
     size_t ws_bytes = 0;
-    // current carve
-    int B = 0, L = 0, Lp = 0, Lkv = 0, M = 0;
+    // current carve, and the forward it holds
+    Resident res;
     bf16_t *x = nullptr, *y = nullptr, *xn = nullptr, *att = nullptr, *hbuf = nullptr, *q = nullptr, *k = nullptr,
            *vT = nullptr, *xg = nullptr;
     int32_t* rows_all = nullptr;
     int32_t* posmap = nullptr;  // [B*Lp] sequence position of every compact stream row (compute-mask forward)
-    // dLLM cache: slots, and the one a forward in flight writes its keys / values into (cc != null only inside
-    // mmada_forward_cached); cc_pos: position map of a compute-mask step (null: every row is computed)
     CacheSlot slots[MMADA_CACHE_SLOTS];
-    const CacheSlot* cc = nullptr;
-    const int32_t* cc_pos = nullptr;
-    int cc_qshift = -1;
-    // consumed-row window (mmada_set_consumed_rows): requested [win_beg, win_end) per sequence; while a forward whose
-    // last block ran windowed is resident, the stream is compact: cur_W rows per sequence starting at row cur_beg
-    int win_beg = 0, win_end = 0;
-    int cur_W = 0, cur_beg = 0, Mcur = 0;
+    int win_beg = 0, win_end = 0;  // mmada_set_consumed_rows: requested [win_beg, win_end) per sequence
     // live timing (mmada_profile_begin/end)
     int prof_layer = -1;
     struct ProfRec { int kind; hipEvent_t a, b; double flops; };
     std::vector<ProfRec> prof;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
-    // tensor-parallel collective engine (tp_comm.hip; mmada_comm_*).  xn_is_final: the resident xn already holds
-    // ln_f(x) for every row (the last reduce-scatter of a tensor-parallel forward applies ln_f on the owned rows)
-    TpComm* tp = nullptr;
-    bool xn_is_final = false;
+    TpComm* tp = nullptr;  // tensor-parallel collective engine (tp_comm.hip; mmada_comm_*)
     // record buffer of mmada_head_logprobs (kernels.h: head_rowstat_bytes), grown at first use, freed with the handle
     void* score_buf = nullptr;
     size_t score_bytes = 0;
-    bool xn_is_layer0 = false;  // mmada_embed already wrote xn = RMSNorm(x) * blocks[0].attn_norm (fused, K1)
 };
 
-// api.hip: one block's launches (the one-rank forward: m0 = 0, every row; the tensor-parallel forward: one row chunk each).  The
+inline bool resident(const mmada_handle* h) { return h->res.M != 0; }
+inline void invalidate(mmada_handle* h) { h->res.M = 0; }
+
+// forward.hip: the start of every forward — weights bound, workspace carved for (B, L) (a failure up to here leaves the resident
+// forward alone), then a fresh Resident: no window, xn = the first norm of the embedding kernel
+int begin_forward(mmada_handle* h, int B, int L, hipStream_t s);
+// forward.hip: the cache step of mmada_forward_cached.  While it lives, the block builders below read and write the slot's keys /
+// values; when it goes, on every exit, they no longer do and no forward is resident (the step ran on the compact stream of
+// the computed tokens, and its result lives in the slot)
+struct CacheStep {
+    mmada_handle* h;
+    CacheStep(mmada_handle* h, const CacheSlot* slot, const int32_t* pos, int qshift);
+    ~CacheStep();
+    CacheStep(const CacheStep&) = delete;
+    CacheStep& operator=(const CacheStep&) = delete;
+};
+
+// forward.hip: one block's launches (the one-rank forward: m0 = 0, every row; the tensor-parallel forward: one row chunk each).  The
 // GemmArgs of block `layer`'s projections on stream rows [m0, m0 + rows): xn -> q / k / vT + RoPE (a dLLM-cache step writes keys /
 // values into the slot), xn -> hbuf (SiLU·mul), att -> y and hbuf -> y (the caller adds its residual or its own target)
 GemmArgs qkv_args(const mmada_handle* h, int layer, int m0, int rows);
@@ -87,12 +113,18 @@ GemmArgs down_args(const mmada_handle* h, int layer, int m0, int rows);
 // the block's attention over this rank's heads, timed as kernel class 1: a cache step's queries against the slot, the row window
 // [wbeg, wbeg + W) of each sequence (W > 0: the one-rank forward's last block), or every row
 int block_attention(mmada_handle* h, int layer, hipStream_t s, int wbeg = 0, int W = 0);
+// every block of a one-rank forward, after the embedding
+int run_blocks(mmada_handle* h, void* stream);
+// heads.hip: the (R, limit, col_begin, col_end) checks of a head entry point named `who` (R <= 0 is the caller's early return)
+int check_head_range(const mmada_handle* h, const char* who, int R, int limit, int col_begin, int col_end);
 
 // tp_comm.hip
 int tp_forward_body(mmada_handle* h, hipStream_t s);              // all blocks of a tensor-parallel forward, after mmada_embed
 int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s);  // residual stream rows of every owner -> [M, d]
 void tp_comm_free(mmada_handle* h);
 bool tp_comm_connected(const mmada_handle* h);   // a transport (or the no-exchange diagnostic) is active on this handle
+// this handle's forward is the tensor-parallel one (a connected one-rank group: the tp_allow_single_rank test switch)
+inline bool runs_tensor_parallel(const mmada_handle* h) { return h->cfg.tp_size != 1 || tp_comm_connected(h); }
 // tp_heads.hip
 int tp_head_gather(mmada_handle* h, const int32_t* rows, int R, hipStream_t s);  // xg[r] = xn[row r] (xn already = ln_f(x))
 // mmada_head_logprobs on a connected handle: the 256-column tiles split over the ranks, records exchanged, every rank joins
@@ -101,14 +133,13 @@ int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin,
 // out[r] = src[b * Lp + l] for rows[r] = b * L + l: the plain row gather behind tp_head_gather, on any [B * Lp, d] buffer
 int tp_gather_rows(const bf16_t* src, const int32_t* rows, int R, int L, int Lp, int d, int nflat, bf16_t* out, hipStream_t s);
 
+// (forward.hip and tp_comm.hip both time their launches, so the bodies stay here)
 struct ProfScope {
     mmada_handle* h; hipStream_t s; bool on; hipEvent_t a{}, b{}; int kind; double flops;
     ProfScope(mmada_handle* h_, int layer, int kind_, double flops_, hipStream_t s_)
         : h(h_), s(s_), on(h_->prof_layer == layer), kind(kind_), flops(flops_) {
-        if (on) {  // a stream under hipGraph capture records nothing: event timing only exists for eager launches
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) on = false;
-        }
+        // a stream under hipGraph capture records nothing: event timing only exists for eager launches
+        if (on && stream_capturing(s)) on = false;
         if (!on) return;
         if (h->prof_pool.empty()) {
             (void)hipEventCreate(&a);
@@ -133,34 +164,4 @@ struct Carve {
     size_t x, y, xn, att, h, q, k, vT, xg, rows, posmap, total;
     int Lp, Lkv, M;
 };
-
-static Carve carve_for(const mmada_handle* h, int B, int L) {
-    Carve c;
-    const int d = h->cfg.d_model;
-    c.Lp = ceil_to(L, 8);
-    c.Lkv = ceil_to(L, 64);
-    c.M = B * c.Lp;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    // tensor parallel: a row chunk is split into tp equal owner slices of a multiple of 8 rows; the last chunk's slices
-    // may reach past M (equal counts for the RCCL reduce-scatter / all-gather), so the stream buffers carry pad rows
-    const size_t mrows = (size_t)c.M + (h->cfg.tp_size > 1 ? 8 * h->cfg.tp_size : 0);
-    c.x = take(mrows * d * 2);
-    c.y = take(mrows * d * 2);
-    c.xn = take(mrows * d * 2);
-    c.att = take((size_t)c.M * h->hq_l * 128 * 2);
-    c.h = take((size_t)c.M * h->f_l * 2);
-    c.q = take((size_t)B * h->hq_l * c.Lkv * 128 * 2);
-    c.k = take((size_t)B * h->hkv_l * c.Lkv * 128 * 2);
-    c.vT = take((size_t)B * h->hkv_l * 128 * c.Lkv * 2);
-    c.xg = take(((size_t)B * L + 8) * d * 2);   // + 8: the scoring head multiplies ceil8(R) rows (pad rows: any content)
-    c.rows = take((size_t)B * L * 4);
-    c.posmap = take((size_t)c.M * 4);
-    c.total = off;
-    return c;
-}
-
+Carve carve_for(const mmada_handle* h, int B, int L);  // forward.hip: the workspace layout of a (B, L) forward

@@ -1,0 +1,107 @@
+// heads.hip — the LM head on demand: logit rows of the resident forward (mmada_head_rows) or of a dLLM-cache slot
+// (mmada_cache_head_rows), and the fused scoring head (mmada_head_logprobs).  Host code only.
+#include "../../include/mmada_mi355x.h"
+#include "handle.h"
+
+int check_head_range(const mmada_handle* h, const char* who, int R, int limit, int col_begin, int col_end) {
+    if (R > limit) return mm_fail("%s: R=%d exceeds B*L=%d", who, R, limit);
+    if (col_begin < 0 || col_end > h->cfg.vocab || col_begin >= col_end) return mm_fail("%s: bad column range", who);
+    return 0;
+}
+
+// xg[i] = ln_f(x[rows[i]]) of the resident one-rank forward.  A windowed forward left the stream compact: row (b, l) sits at
+// b*cur_W + l - cur_beg; rows outside the window the caller declared with mmada_set_consumed_rows were never computed and must
+// not be requested
+static int gather_resident_rows(mmada_handle* h, const int32_t* rows, int R, hipStream_t s) {
+    const Resident& r = h->res;
+    return launch_rmsnorm_gather(h->x, h->ln_f, h->xg, rows, R, r.L, r.cur_W ? r.cur_W : r.Lp, h->cfg.d_model, h->cfg.rms_eps, s,
+                                 r.cur_beg, r.B * r.L);
+}
+
+// out [R, col_end - col_begin] = xg rows × lm_head[col_begin:col_end]
+static int store_logits(const mmada_handle* h, const bf16_t* xg, int R, int col_begin, int col_end, void* out, hipStream_t s) {
+    const int d = h->cfg.d_model, N = col_end - col_begin;
+    return launch_gemm(EPI_STORE, gemm_bt_args(xg, h->lm_head + (size_t)col_begin * d, (bf16_t*)out, R, N, d, N), s);
+}
+
+// the record buffer of mmada_head_logprobs holds at least `need` bytes
+static int grow_score_buffer(mmada_handle* h, size_t need, hipStream_t s) {
+    if (need <= h->score_bytes) return 0;
+    if (stream_capturing(s))
+        return mm_fail("mmada_head_logprobs: the record buffer must grow (%zu bytes): run the call once outside the capture", need);
+    MM_CHECK_HIP(hipStreamSynchronize(s));   // an earlier call on this stream may still read the old buffer
+    (void)hipFree(h->score_buf);
+    h->score_buf = nullptr; h->score_bytes = 0;
+    MM_CHECK_HIP(hipMalloc(&h->score_buf, need));
+    h->score_bytes = need;
+    return 0;
+}
+
+extern "C" {
+
+int mmada_cache_head_rows(mmada_handle* h, int slot, const int32_t* rows, int R, int col_begin, int col_end,
+                          void* logits_out, void* stream) {
+    if (!h || !rows || !logits_out) return mm_fail("mmada_cache_head_rows: null argument");
+    if (slot < 0 || slot >= MMADA_CACHE_SLOTS || !h->slots[slot].mem) return mm_fail("mmada_cache_head_rows: slot %d is not bound", slot);
+    const CacheSlot& c = h->slots[slot];
+    if (R <= 0) return 0;
+    if (check_head_range(h, "mmada_cache_head_rows", R, c.B * c.L, col_begin, col_end)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    const int d = h->cfg.d_model;
+    // staging rows for ln_f: the gather buffer of the workspace.  While a plain forward is resident its carve is live, so
+    // its own gather buffer (B*L rows of that forward) is the only region that may be written; otherwise the carve of the
+    // slot's shape applies
+    bf16_t* xg;
+    if (resident(h)) {
+        if ((size_t)R > (size_t)h->res.B * h->res.L)
+            return mm_fail("mmada_cache_head_rows: %d rows do not fit the resident forward's gather buffer (%d x %d rows); "
+                           "ask for fewer rows per call", R, h->res.B, h->res.L);
+        xg = h->xg;
+    } else {
+        const Carve cv = carve_for(h, c.B, c.L);
+        if (!h->ws || cv.total > h->ws_bytes) return mm_fail("mmada_cache_head_rows: workspace too small (%zu needed)", cv.total);
+        xg = (bf16_t*)(h->ws + cv.xg);
+    }
+    if (c.normalized) {   // rows written by a tensor-parallel forward: ln_f already applied by the owners
+        if (tp_gather_rows(c.xfin(h->cfg.n_layers), rows, R, c.L, c.Lp, d, c.B * c.L, xg, s)) return 1;
+    } else if (launch_rmsnorm_gather(c.xfin(h->cfg.n_layers), h->ln_f, xg, rows, R, c.L, c.Lp, d, h->cfg.rms_eps, s, 0, c.B * c.L))
+        return 1;
+    return store_logits(h, xg, R, col_begin, col_end, logits_out, s);
+}
+
+int mmada_head_rows(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, void* logits_out,
+                    void* stream) {
+    if (!h || !resident(h)) return mm_fail("mmada_head_rows: no forward resident");
+    if (!rows || !logits_out) return mm_fail("mmada_head_rows: null argument");
+    if (R <= 0) return 0;
+    if (check_head_range(h, "mmada_head_rows", R, h->res.B * h->res.L, col_begin, col_end)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    // tensor-parallel forward: the last exchange already applied ln_f on the owners' rows
+    if (h->res.xn_is_final ? tp_head_gather(h, rows, R, s) : gather_resident_rows(h, rows, R, s)) return 1;
+    return store_logits(h, h->xg, R, col_begin, col_end, logits_out, s);
+}
+
+int mmada_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
+                        float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out, void* stream) {
+    if (!h || !resident(h)) return mm_fail("mmada_head_logprobs: no forward resident");
+    if (!rows || !targets || !logprob_out) return mm_fail("mmada_head_logprobs: null argument");
+    // a connected handle (also a one-rank group): the vocabulary-parallel head, same records, same fold (tp_heads.hip)
+    if (tp_comm_connected(h))
+        return tp_head_logprobs(h, rows, R, col_begin, col_end, targets, logprob_out, lse_out, argmax_out, max_out, (hipStream_t)stream);
+    if (h->res.xn_is_final || h->cfg.tp_size != 1)
+        return mm_fail("mmada_head_logprobs: a tensor-parallel handle scores through the library's exchange only (mmada_comm_create + "
+                       "mmada_comm_connect_*): a vocabulary-parallel score exchanges the same records as mmada_text_select_tp");
+    if (R <= 0) return 0;
+    if (check_head_range(h, "mmada_head_logprobs", R, h->res.B * h->res.L, col_begin, col_end)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    const int d = h->cfg.d_model, N = col_end - col_begin;
+    if (grow_score_buffer(h, head_rowstat_bytes(R, N), s)) return 1;
+    // the same gather as mmada_head_rows (compact stream of a windowed forward; rows outside the window are an error there)
+    if (gather_resident_rows(h, rows, R, s)) return 1;
+    return launch_head_rowstat(h->xg, h->lm_head + (size_t)col_begin * d, R, N, d, col_begin, targets, h->score_buf, logprob_out,
+                               lse_out, argmax_out, max_out, s);
+}
+
+size_t mmada_score_buffer_bytes(const mmada_handle* h) { return h ? h->score_bytes : 0; }
+
+}  // extern "C"

@@ -433,13 +433,13 @@ int tp_forward_body(mmada_handle* h, hipStream_t s_user) {
 
 static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
     TpComm* c = h->tp;
-    if (h->M > c->max_rows) return mm_fail("tensor-parallel forward: %d rows exceed the comm buffers (%d)", h->M, c->max_rows);
-    const int d = h->cfg.d_model, M = h->M, nl = h->cfg.n_layers;
+    if (h->res.M > c->max_rows) return mm_fail("tensor-parallel forward: %d rows exceed the comm buffers (%d)", h->res.M, c->max_rows);
+    const int d = h->cfg.d_model, M = h->res.M, nl = h->cfg.n_layers;
     if ((d >> 3) > 64 * MAXCH) return mm_fail("tensor-parallel forward: d_model > %d is not supported", 64 * MAXCH * 8);
     const ChunkPlan plan = chunk_plan(c, M);
-    const double rows_real = (double)h->B * h->L / M;  // fraction of stream rows that are not padding (FLOP accounting)
+    const double rows_real = (double)h->res.B * h->res.L / M;  // fraction of stream rows that are not padding (FLOP accounting)
     // first RMSNorm of the forward: the embeddings are replicated, no exchange needed
-    if (h->xn_is_layer0) h->xn_is_layer0 = false;  // fused into the embedding kernel
+    if (h->res.xn_is_layer0) h->res.xn_is_layer0 = false;  // fused into the embedding kernel
     else if (launch_rmsnorm(h->x, h->layers[0].attn_norm, h->xn, M, d, h->cfg.rms_eps, s)) return 1;
     bool pending[2] = {false, false};  // chunk k's xn rows are being produced on the exchange stream
     using ArgsOf = GemmArgs (*)(const mmada_handle*, int, int, int);  // handle.h: qkv_args, gate_up_args, attn_out_args, down_args
@@ -487,7 +487,7 @@ static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
     }
     for (int k = 0; k < plan.n; ++k)
         if (pending[k]) MM_CHECK_HIP(hipStreamWaitEvent(s, c->ev_c[k], 0));
-    h->xn_is_final = true;  // xn = ln_f(x) on every row
+    h->res.xn_is_final = true;  // xn = ln_f(x) on every row
     return 0;
 }
 
@@ -496,7 +496,7 @@ int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s) {
     TpComm* c = h->tp;
     if (!transport_connected(c)) return mm_fail("tp_gather_stream: no transport connected (or the no-exchange diagnostic is on)");
     const int d = h->cfg.d_model;
-    const ChunkPlan plan = chunk_plan(c, h->M);
+    const ChunkPlan plan = chunk_plan(c, h->res.M);
     for (int k = 0; k < plan.n; ++k) {
         const Slice& sl = plan.sl[k];
         const int own = sl.r1 - sl.r0;
@@ -731,9 +731,9 @@ void* mmada_comm_part_ptr(mmada_handle* h) { return h && h->tp ? (void*)h->tp->p
  * buffer (mmada_comm_part_ptr, [B*Lp, d]) and the residual stream; afterwards x holds own rows + sum and xn (debug buffer
  * 0) the RMSNorm of every row with norm_w (device bf16 [d]).  Runs on `stream` (no second stream, no chunking). */
 int mmada_comm_exchange(mmada_handle* h, const void* norm_w, void* stream) {
-    if (!h || !h->tp || h->M == 0 || !norm_w) return mm_fail("mmada_comm_exchange: need a comm and a resident carve (mmada_embed)");
-    const Slice sl = chunk_slice(h->M, h->tp->size, h->tp->rank, 1, 0);
-    h->xn_is_layer0 = false;  // xn is about to be overwritten
+    if (!h || !h->tp || !resident(h) || !norm_w) return mm_fail("mmada_comm_exchange: need a comm and a resident carve (mmada_embed)");
+    const Slice sl = chunk_slice(h->res.M, h->tp->size, h->tp->rank, 1, 0);
+    h->res.xn_is_layer0 = false;  // xn is about to be overwritten
     if (peers_mapped(h->tp)) hipLaunchKernelGGL(tp_flush_kernel, dim3(256), dim3(64), 0, (hipStream_t)stream);
     return exchange(h, sl, (const bf16_t*)norm_w, (hipStream_t)stream);
 }

@@ -118,7 +118,7 @@ int tp_gather_rows(const bf16_t* src, const int32_t* rows, int R, int L, int Lp,
 }
 
 int tp_head_gather(mmada_handle* h, const int32_t* rows, int R, hipStream_t s) {
-    return tp_gather_rows(h->xn, rows, R, h->L, h->Lp, h->cfg.d_model, h->B * h->L, h->xg, s);
+    return tp_gather_rows(h->xn, rows, R, h->res.L, h->res.Lp, h->cfg.d_model, h->res.B * h->res.L, h->xg, s);
 }
 
 /* Vocabulary-parallel text step (generators/parallel_generator.py:185-217 at text_temperature == 0) after a
@@ -129,12 +129,12 @@ int tp_head_gather(mmada_handle* h, const int32_t* rows, int R, hipStream_t s) {
 extern "C" int mmada_text_select_tp(mmada_handle* h, const int32_t* rows, int B, int T, int64_t* ids, int L, int text_start,
                                     const int32_t* k, void* scratch, void* stream) {
     if (!h || !transport_connected(h->tp)) return mm_fail("mmada_text_select_tp: no tensor-parallel transport connected");
-    if (!h->xn_is_final || h->M == 0) return mm_fail("mmada_text_select_tp: no tensor-parallel forward resident");
+    if (!h->res.xn_is_final || !resident(h)) return mm_fail("mmada_text_select_tp: no tensor-parallel forward resident");
     if (!rows || !ids || !k || !scratch) return mm_fail("mmada_text_select_tp: null argument");
     TpComm* c = h->tp;
     const int R = B * T;
     if (R <= 0) return 0;
-    if (R > STAT_ROWS || R > h->B * h->L) return mm_fail("mmada_text_select_tp: %d rows exceed the limit", R);
+    if (R > STAT_ROWS || R > h->res.B * h->res.L) return mm_fail("mmada_text_select_tp: %d rows exceed the limit", R);
     if (text_start < 0 || text_start + T > L) return mm_fail("mmada_text_select_tp: text span outside the sequence");
     hipStream_t s = (hipStream_t)stream;
     const int d = h->cfg.d_model, V = h->cfg.vocab;
@@ -189,13 +189,12 @@ int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin,
                      float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s) {
     TpComm* c = h->tp;
     if (!transport_connected(c)) return mm_fail("mmada_head_logprobs: no tensor-parallel transport connected");
-    if (!h->xn_is_final || h->M == 0) return mm_fail("mmada_head_logprobs: no tensor-parallel forward resident");
+    if (!h->res.xn_is_final || !resident(h)) return mm_fail("mmada_head_logprobs: no tensor-parallel forward resident");
     if (R <= 0) return 0;
     if (R > c->max_rows)
         return mm_fail("mmada_head_logprobs: %d rows exceed the %d rows this handle's comm was created for (mmada_comm_create max_rows)",
                        R, c->max_rows);
-    if (R > h->B * h->L) return mm_fail("mmada_head_logprobs: R=%d exceeds B*L=%d", R, h->B * h->L);
-    if (col_begin < 0 || col_end > h->cfg.vocab || col_begin >= col_end) return mm_fail("mmada_head_logprobs: bad column range");
+    if (check_head_range(h, "mmada_head_logprobs", R, h->res.B * h->res.L, col_begin, col_end)) return 1;
     const int d = h->cfg.d_model, tp = c->size;
     const ScoreLayout& lay = c->score;
     const int ntn = (col_end - col_begin + SCORE_BN - 1) / SCORE_BN, q = (ntn + tp - 1) / tp;
