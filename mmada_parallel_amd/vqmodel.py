@@ -11,7 +11,7 @@ The reference loads the image tokenizer with `VQModel.from_pretrained(vae_ckpt, 
 
 `diffusers==0.34.0` is a third-party requirement that is NOT vendored in the reference tree, so the architecture is restated
 from its published source (autoencoders/vq_model.py, autoencoders/vae.py) and parity is UNPINNED: the tests compare against
-oracle/vqmodel_oracle.py, which carries the same caveat.  The arithmetic runs in libmmada_mi355x.so (csrc/vq_decoder.hip,
+oracle/vqmodel_oracle.py, which carries the same caveat.  The arithmetic runs in libmmada_mi355x.so (csrc/vq_net.hip,
 mmada_vq_create_vqmodel); there is no PyTorch fallback — without the HIP library or a GPU the constructor raises.
 """
 from __future__ import annotations
@@ -24,7 +24,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import abi
+from .vq_handle import VqHandles, read_state_dict
 
 # diffusers VQModel.__init__ defaults (autoencoders/vq_model.py)
 DEFAULT_CONFIG = dict(in_channels=3, out_channels=3, block_out_channels=[64], layers_per_block=1, act_fn="silu",
@@ -41,12 +41,11 @@ class VqModelCfg(C.Structure):
                 ("image_channels", C.c_int32), ("mid_block_add_attention", C.c_int32), ("norm_num_groups", C.c_int32)]
 
 
-class VQModel:
+class VQModel(VqHandles):
     """Drop-in for the reference's use of `diffusers.VQModel` (inference only, fp32 like the reference)."""
 
     def __init__(self, config: dict, state_dict: Dict[str, torch.Tensor], device: Optional[torch.device] = None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("VQModel (MI355X) needs a GPU: there is no CPU fallback")
+        super().__init__("VQModel", device)
         cfg = dict(DEFAULT_CONFIG)
         cfg.update({k: v for k, v in config.items() if not k.startswith("_")})
         if cfg["act_fn"] not in ("silu", "swish") or cfg["norm_type"] != "group":
@@ -55,10 +54,8 @@ class VQModel:
             raise NotImplementedError("in_channels != out_channels")
         cfg["vq_embed_dim"] = cfg["vq_embed_dim"] if cfg["vq_embed_dim"] is not None else cfg["latent_channels"]
         self.config = SimpleNamespace(**cfg)
-        self.device = torch.device(device if device is not None else "cuda:0")
         self.dtype = torch.float32
-        self._lib = abi.lib()
-        self._ws = self._dec = self._enc = self._last = None   # _last: encode()'s (latents, indices, version), see quantize()
+        self._dec = self._enc = self._last = None   # _last: encode()'s (latents, indices, version), see quantize()
         c = VqModelCfg()
         c.n_levels = len(cfg["block_out_channels"])
         if not 1 <= c.n_levels <= 8:
@@ -68,26 +65,14 @@ class VQModel:
         c.layers_per_block, c.latent_channels, c.vq_embed_dim = cfg["layers_per_block"], cfg["latent_channels"], cfg["vq_embed_dim"]
         c.num_vq_embeddings, c.image_channels = cfg["num_vq_embeddings"], cfg["in_channels"]
         c.mid_block_add_attention, c.norm_num_groups = int(bool(cfg["mid_block_add_attention"])), cfg["norm_num_groups"]
-        self._dec = self._build(c, False, state_dict)
-        self._enc = self._build(c, True, state_dict) if any(k.startswith("encoder.") for k in state_dict.keys()) else None
+        self._dec = self._network(c, False, state_dict)
+        self._enc = self._network(c, True, state_dict) if any(k.startswith("encoder.") for k in state_dict.keys()) else None
 
-    def _build(self, c: VqModelCfg, encoder: bool, sd) -> C.c_void_p:
-        h = C.c_void_p()
+    def _network(self, c: VqModelCfg, encoder: bool, sd) -> C.c_void_p:
         own = ("encoder.", "quant_conv.", "quantize.embedding.") if encoder else ("decoder.", "post_quant_conv.", "quantize.embedding.")
-        with torch.cuda.device(self.device):
-            abi.check(self._lib.mmada_vq_create_vqmodel(C.byref(c), int(encoder), C.byref(h)), "mmada_vq_create_vqmodel")
-            st = abi.stream_ptr()
-            for k in sd.keys():
-                if not k.startswith(own):
-                    continue
-                t = sd[k].to(device=self.device, dtype=torch.float32).contiguous()
-                abi.check(self._lib.mmada_vq_bind(h, k.encode(), t.data_ptr(), t.numel(), st), f"bind {k}")
-            torch.cuda.current_stream().synchronize()  # the staged tensors may be freed now
-        missing = self._lib.mmada_vq_num_unbound(h)
-        if missing:
-            self._lib.mmada_vq_destroy(h)
-            raise KeyError(f"{missing} {'encoder' if encoder else 'decoder'} tensors of the VQModel are missing from the state dict")
-        return h
+        return self._build(self._lib.mmada_vq_create_vqmodel, "mmada_vq_create_vqmodel", (C.byref(c), int(encoder)), sd,
+                           [k for k in sd.keys() if k.startswith(own)],
+                           f"{'encoder' if encoder else 'decoder'} tensors of the VQModel are missing from the state dict")
 
     # ---- loading ---------------------------------------------------------------------------------------------------------
     @classmethod
@@ -100,20 +85,7 @@ class VQModel:
         root = os.path.join(path, subfolder) if subfolder else path
         with open(os.path.join(root, "config.json")) as f:
             config = json.load(f)
-        sd: Dict[str, torch.Tensor] = {}
-        files = sorted(f for f in os.listdir(root) if f.endswith(".safetensors"))
-        if files:
-            from safetensors.torch import load_file
-
-            for fn in files:
-                sd.update(load_file(os.path.join(root, fn)))
-        else:
-            bins = sorted(f for f in os.listdir(root) if f.endswith(".bin"))
-            if not bins:
-                raise FileNotFoundError(f"no *.safetensors / *.bin under {root}")
-            for fn in bins:
-                sd.update(torch.load(os.path.join(root, fn), map_location="cpu"))
-        return cls(config, sd, **kw)
+        return cls(config, read_state_dict(root, "*.bin"), **kw)
 
     def to(self, device=None, *_a, **_k):
         """`.to(device)` of the reference (inference.py:95): a no-op for the device the weights already live on."""
@@ -133,13 +105,6 @@ class VQModel:
         return self
 
     # ---- the three calls of the reference ----------------------------------------------------------------------------------
-    def _workspace(self, handle, B, hz, wz):
-        need = self._lib.mmada_vq_workspace_bytes(handle, B, hz, wz)
-        if self._ws is None or self._ws.numel() < need + 256:
-            self._ws = None
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-        return (self._ws.data_ptr() + 255) // 256 * 256, need
-
     @property
     def scale(self) -> int:
         return 2 ** (len(self.config.block_out_channels) - 1)
@@ -157,8 +122,7 @@ class VQModel:
         ws, nb = self._workspace(self._enc, B, hz, wz)
         idx = torch.empty((B, hz * wz), dtype=torch.int64, device=self.device)
         z = torch.empty((B, hz * wz, D), dtype=torch.float32, device=self.device)
-        abi.check(self._lib.mmada_vq_get_code(self._enc, x.data_ptr(), B, H, W, ws, nb, idx.data_ptr(), z.data_ptr(),
-                                              abi.stream_ptr()), "mmada_vq_get_code")
+        self._call("mmada_vq_get_code", self._enc, x.data_ptr(), B, H, W, ws, nb, idx.data_ptr(), z.data_ptr())
         latents = z.view(B, hz, wz, D).permute(0, 3, 1, 2).contiguous()
         # quantize(latents) on this very (unmodified) tensor reuses the indices computed alongside
         self._last = (latents, idx, latents._version)
@@ -174,8 +138,7 @@ class VQModel:
         else:
             z = latents.to(device=self.device, dtype=torch.float32).permute(0, 2, 3, 1).contiguous()
             idx = torch.empty(B * hz * wz, dtype=torch.int64, device=self.device)
-            abi.check(self._lib.mmada_vq_nearest_code(self._dec, z.data_ptr(), B * hz * wz, idx.data_ptr(), abi.stream_ptr()),
-                      "mmada_vq_nearest_code")
+            self._call("mmada_vq_nearest_code", self._dec, z.data_ptr(), B * hz * wz, idx.data_ptr())
         return None, None, (None, None, idx)
 
     def decode(self, h: torch.Tensor, force_not_quantize: bool = False, return_dict: bool = True, shape=None):
@@ -197,15 +160,5 @@ class VQModel:
         f = self.scale
         ws, nb = self._workspace(self._dec, B, hz, wz)
         out = torch.empty((B, self.config.out_channels, hz * f, wz * f), dtype=torch.float32, device=self.device)
-        abi.check(self._lib.mmada_vq_decode_code(self._dec, idx.data_ptr(), B, hz, wz, ws, nb, out.data_ptr(), abi.stream_ptr()),
-                  "mmada_vq_decode_code")
+        self._call("mmada_vq_decode_code", self._dec, idx.data_ptr(), B, hz, wz, ws, nb, out.data_ptr())
         return SimpleNamespace(sample=out, commit_loss=None) if return_dict else (out,)
-
-    def __del__(self):
-        try:
-            for h in (self._dec, self._enc):
-                if h:
-                    self._lib.mmada_vq_destroy(h)
-            self._dec = self._enc = None
-        except Exception:
-            pass

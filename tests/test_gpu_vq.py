@@ -1,4 +1,4 @@
-"""GPU parity tests of the MAGVITv2 token -> pixel decode (csrc/vq_decoder.hip) through the C-ABI.
+"""GPU parity tests of the MAGVITv2 token -> pixel decode (csrc/vq_net.hip over csrc/vq_kernels.hip) through the C-ABI.
 
 The reference runs this network in fp32 (MMaDA-Parallel-M/inference.py:56-59), so does the HIP path; the comparison
 is against the fp32 CPU oracle (oracle/vq_oracle.py, pinned to the reference by tests/golden/vq_decode.npz) and

@@ -1,4 +1,4 @@
-"""GPU tests of the A-variant image tokenizer (mmada_parallel_amd.VQModel over csrc/vq_decoder.hip, C-ABI
+"""GPU tests of the A-variant image tokenizer (mmada_parallel_amd.VQModel over csrc/vq_net.hip, C-ABI
 mmada_vq_create_vqmodel / mmada_vq_decode_code / mmada_vq_get_code / mmada_vq_nearest_code) and of the pixel <-> token
 helpers of utils/image_utils.py.
 

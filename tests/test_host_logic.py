@@ -77,7 +77,7 @@ def test_prompt_template():
 
 def test_vq_state_dict_keys_match_the_reference_modules():
     """Checkpoint contract of the MAGVITv2 path: the key names and shapes the loader expects (synth.vq_*_param_shapes,
-    mirrored by the slot table of csrc/vq_decoder.hip) are those of the reference's VQGANDecoder / VQGANEncoder built with
+    mirrored by the slot table of csrc/vq_net.hip) are those of the reference's VQGANDecoder / VQGANEncoder built with
     their default arguments (recorded by oracle/gen_golden.py from the reference modules' own state_dict())."""
     import os
 
@@ -91,6 +91,72 @@ def test_vq_state_dict_keys_match_the_reference_modules():
         ref = [str(x) for x in np.load(os.path.join(GOLDEN, fixture))["full_keys"]]
         mine = [f"{k}:{tuple(v)}" for k, v in shapes.items()]
         assert sorted(ref) == sorted(mine)
+
+
+def test_vq_slot_table_matches_the_checkpoint_shapes():
+    """The slot table of csrc/vq_net.hip against the checkpoint shapes (synth.*_param_shapes) for the four network kinds at
+    their tiny and full configurations: as many slots as the checkpoint has tensors, every key known with the element count
+    of its shape, an unknown key refused.  Host arithmetic only: a bind with a wrong element count returns before any device
+    call, so no handle here ever allocates."""
+    import ctypes as C
+
+    from mmada_parallel_amd import abi
+    from mmada_parallel_amd.vq import VqCfg
+    from mmada_parallel_amd.vqmodel import VqModelCfg
+
+    lib = abi.lib()
+    dummy = C.create_string_buffer(16)
+
+    def magvit(cfg, encoder):
+        c = VqCfg()
+        c.ch, c.n_levels, c.z_channels = cfg["ch"], len(cfg["ch_mult"]), cfg["z_channels"]
+        c.out_ch = cfg["in_ch"] if encoder else cfg["out_ch"]
+        for i, (m, n) in enumerate(zip(cfg["ch_mult"], cfg["num_res_blocks"])):
+            c.ch_mult[i], c.num_res_blocks[i] = m, n
+        h = C.c_void_p()
+        abi.check((lib.mmada_vq_create_encoder if encoder else lib.mmada_vq_create)(C.byref(c), C.byref(h)), "create")
+        return h
+
+    def vqmodel(cfg, encoder):
+        c = VqModelCfg()
+        c.n_levels = len(cfg["block_out_channels"])
+        for i, v in enumerate(cfg["block_out_channels"]):
+            c.block_out_channels[i] = v
+        c.layers_per_block, c.latent_channels = cfg["layers_per_block"], cfg["latent_channels"]
+        c.vq_embed_dim = cfg["vq_embed_dim"] or cfg["latent_channels"]
+        c.num_vq_embeddings, c.image_channels = cfg["num_vq_embeddings"], cfg["in_channels"]
+        c.mid_block_add_attention, c.norm_num_groups = int(cfg["mid_block_add_attention"]), cfg["norm_num_groups"]
+        h = C.c_void_p()
+        abi.check(lib.mmada_vq_create_vqmodel(C.byref(c), int(encoder), C.byref(h)), "create_vqmodel")
+        return h
+
+    def owned(cfg, encoder):  # the keys VQModel._network hands to one direction's handle
+        own = ("encoder.", "quant_conv.", "quantize.embedding.") if encoder else ("decoder.", "post_quant_conv.", "quantize.embedding.")
+        return {k: v for k, v in synth.vqmodel_param_shapes(cfg).items() if k.startswith(own)}
+
+    prefixed = {"decoder." + k: v for k, v in synth.vq_decoder_param_shapes(synth.VQ_CFG_M).items()}
+    nets = [(magvit(synth.VQ_CFG_TINY, False), synth.vq_decoder_param_shapes(synth.VQ_CFG_TINY)),
+            (magvit(synth.VQ_CFG_M, False), prefixed),
+            (magvit(synth.VQ_ENC_CFG_TINY, True), synth.vq_encoder_param_shapes(synth.VQ_ENC_CFG_TINY)),
+            (magvit(synth.VQ_ENC_CFG_M, True), synth.vq_encoder_param_shapes(synth.VQ_ENC_CFG_M))]
+    for cfg in (synth.VQMODEL_CFG_TINY, synth.VQMODEL_CFG_A):
+        nets += [(vqmodel(cfg, False), owned(cfg, False)), (vqmodel(cfg, True), owned(cfg, True))]
+    counts = []
+    try:
+        for h, shapes in nets:
+            counts.append(lib.mmada_vq_num_unbound(h))
+            assert counts[-1] == len(shapes)
+            for key, shape in shapes.items():
+                assert lib.mmada_vq_bind(h, key.encode(), dummy, -1, None) != 0, key
+                msg = lib.mmada_last_error().decode()
+                assert msg.endswith(f"expected {math.prod(shape)}"), (key, msg)
+            assert lib.mmada_vq_bind(h, b"no.such.tensor", dummy, 1, None) != 0
+            assert "unexpected tensor" in lib.mmada_last_error().decode()
+            assert lib.mmada_vq_num_unbound(h) == len(shapes)
+    finally:
+        for h, _ in nets:
+            lib.mmada_vq_destroy(h)
+    assert counts == [62, 190, 62, 190, 71, 55, 159, 119]
 
 
 def test_generate_image_keep_schedule_matches_the_oracle_rule():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Time the MAGVITv2 token -> pixel decode (csrc/vq_decoder.hip) at the MMaDA-Parallel-M shape: 32x32 codes -> 512x512.
+"""Time the MAGVITv2 token -> pixel decode (csrc/vq_net.hip over csrc/vq_kernels.hip) at the MMaDA-Parallel-M shape: 32x32 codes -> 512x512.
 Measurement tool only (the headline bench is bench.py)."""
 import os
 import sys
