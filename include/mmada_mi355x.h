@@ -135,6 +135,27 @@ int mmada_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_beg
                         float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out, void* stream);
 size_t mmada_score_buffer_bytes(const mmada_handle* h);
 
+/* Top-k: the k likeliest columns of each row over logit columns [col_begin, col_end), again WITHOUT materialising the logits: the
+ * head GEMM of mmada_head_logprobs with an epilogue that also keeps every 256-column tile's eight best (bf16 logit, column) pairs
+ * — one 32-byte record per row and tile beside the 16-byte one — and a second kernel that joins the records of a row.
+ * Preconditions of mmada_head_logprobs (a forward resident, the same range and row-window rules), and 1 <= k <= MMADA_TOPK_MAX,
+ * k <= col_end - col_begin.
+ * ids_out: device int32 [R, k], column in the WHOLE vocabulary; logit_out: device fp32 [R, k], the bf16 logit (the accumulator
+ * rounded to bf16, what mmada_head_rows stores) as fp32, exact.  Order of a row's k entries: logit descending, then column ascending
+ * — what a stable descending sort of the row gives; entry 0 is the argmax_out / max_out of mmada_head_logprobs.  A logit of -0.0 is
+ * ordered and returned as +0.0 (a comparison sort cannot tell them apart; the lower column wins).  NaN logits: outside the contract.
+ * lse_out: device fp32 [R] or NULL: bit for bit the lse_out of mmada_head_logprobs on the same rows and range (the same records,
+ * fold and expression), so logit_out - lse_out in fp32 is mmada_head_logprobs' logprob_out of that column.
+ * Record buffer: the handle's (mmada_score_buffer_bytes), ceil(N / 256) * ceil8(R) * 48 + ceil8(R) * 4 bytes — 3/32 of the bf16
+ * logits the call stands for; the call synchronises the host only when the buffer must grow, and a call that fits is capturable.
+ * One rank only: a handle with a tensor-parallel exchange connected (also a one-rank group) or tp_size != 1 is an error. */
+#define MMADA_TOPK_MAX 8
+int mmada_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, int k, int32_t* ids_out,
+                    float* logit_out, float* lse_out, void* stream);
+/* The order value mmada_head_topk sorts by: bf16 bits -> 16 bits whose unsigned order is the logits' (diagnostic; -0.0 maps to
+ * the value of +0.0). */
+unsigned mmada_topk_order_key(unsigned bf16_bits);
+
 /* Declare which residual-stream rows the caller will read after the forwards that follow: only l in
  * [row_begin, row_end) of every sequence (e.g. the image + text span of generate_ti2ti; the prompt and the input image
  * are never decoded).  The LAST block then runs attention queries, attn_out and the MLP on those rows only — every

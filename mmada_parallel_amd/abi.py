@@ -42,6 +42,8 @@ SIGNATURES = {
     "mmada_head_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mmada_head_logprobs": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mmada_score_buffer_bytes": (c_size_t, [c_void_p]),
+    "mmada_head_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mmada_topk_order_key": (C.c_uint, [C.c_uint]),
     "mmada_cache_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "mmada_cache_bind": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "mmada_forward_cached": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -151,7 +151,8 @@ __global__ __launch_bounds__(NTHREADS, 4) void gemm_bt_kernel(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < T::FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     mainloop<BM, WM, WN>(g, smem, mt * BM, nt * BN, 0, g.K / BK, acc, wave, lane);
-    if constexpr (EPI == EPI_ROWSTAT) {
+    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK) {
+        static_assert(T::LDS_BYTES >= RowTopkLds::BYTES, "the row records reuse the stage buffers");
         __syncthreads();   // every wave has read its last K-tile: the stage buffers are free for the row records
         gemm_epilogue<EPI, T::TM, T::TN, WN>(g, mt * BM, nt * BN, acc, wave, lane, g.M, (int)(uintptr_t)(lptr_t)smem, BM);
     } else
@@ -230,8 +231,8 @@ Plan plan(const GemmArgs& g, int force) {
 template <int EPI>
 int launch_t(const GemmArgs& g, const Switches& sw, hipStream_t s) {
     Plan p = plan(g, sw.gemm_config);
-    if constexpr (EPI == EPI_ROWSTAT) {
-        // the row-statistics epilogue exists for 256-column tiles of four 64-column waves: a pinned configuration without one
+    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK) {
+        // the row-statistics epilogue (and its top-k form) exists for 256-column tiles of four 64-column waves: a pinned configuration without one
         // (320 x 128; the 16-wave kernel's 2 x 8 wave grids) gets the automatic pick, and that the next taller 4 x 4 grid
         if (p.p8 && p.code == GEMM8_320x128) p = plan(g, -1);
         if (p.p8 && p.code == GEMM8_320x128) p = {true, GEMM8_320x256};
@@ -348,6 +349,10 @@ int launch_gemm(int epi, const GemmArgs& g_in, hipStream_t s) {
             if (const RowStatArgs rs = rowstat_args(g); !rs.part || !rs.tx || !rs.target || rs.rows <= 0 || rs.rows > g.M || rs.ld < rs.rows)
                 return mm_fail("gemm/rowstat: record buffers missing");
             return launch_t<EPI_ROWSTAT>(g, sw, s);
+        case EPI_ROWTOPK:   // a null target is allowed here: no row has one
+            if (const RowTopkArgs tk = rowtopk_args(g); !tk.rs.part || !tk.rs.tx || !tk.topk || tk.rs.rows <= 0 || tk.rs.rows > g.M || tk.rs.ld < tk.rs.rows)
+                return mm_fail("gemm/rowtopk: record buffers missing");
+            return launch_t<EPI_ROWTOPK>(g, sw, s);
     }
     return mm_fail("gemm: bad epilogue %d", epi);
 }
@@ -385,6 +390,96 @@ int launch_head_rowstat(const bf16_t* A, const bf16_t* W, int R, int N, int K, i
     if (launch_gemm(EPI_ROWSTAT, g, s)) return 1;
     hipLaunchKernelGGL(rowstat_combine_kernel, dim3((R + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, rs.part, rs.tx,
                        targets, R, rp, ntn, logprob, lse, argmax, vmax);
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the top-k head: the same launch with EPI_ROWTOPK (gemm_epilogue.h), which also leaves every tile's eight best keys ------
+// Record buffer: the row-statistics records and ceil8(R) floats as above, then [ceil(N / 256)][ceil8(R)] key records of 32 bytes:
+// 3/32 of the bytes of the bf16 logits it stands for, plus 4 bytes per row.
+size_t head_rowtopk_bytes(int R, int N) {
+    const size_t rp = (size_t)((R + 7) / 8 * 8);
+    return head_rowstat_bytes(R, N) + rp * rowstat_tiles(N) * (TOPK_MAX * sizeof(uint32_t));
+}
+
+// A candidate of the join: {order value of the logit, ~column inside the launch} as one 64-bit number — logit descending, then
+// tile ascending, then column ascending is ONE unsigned compare, and candidates of a row are distinct.  0: no candidate.
+MM_DEVICE unsigned long long topk_cand(uint32_t key, int tile) {
+    if (key == 0u) return 0ull;
+    const uint32_t col = (uint32_t)tile * (uint32_t)BN + (255u - (key & 255u));
+    return ((unsigned long long)(key >> 16) << 32) | (unsigned long long)(~col);
+}
+// best[] stays sorted in descending order; c replaces the last entry and moves up to its place
+MM_DEVICE void topk_insert(unsigned long long (&best)[TOPK_MAX], unsigned long long c) {
+    best[TOPK_MAX - 1] = c;
+#pragma unroll
+    for (int i = TOPK_MAX - 1; i > 0; --i) {
+        const unsigned long long lo = best[i], hi = best[i - 1];
+        best[i - 1] = lo > hi ? lo : hi;
+        best[i] = lo > hi ? hi : lo;
+    }
+}
+
+// Thread (row, group j) walks the key records of tiles j, j + 16, ... and keeps the best eight candidates sorted in registers (a
+// record is sorted: its entries are taken until one does not beat the thread's eighth — most tiles end at their first); thread
+// (row, 0) merges the 16 lists of the row through LDS the same way and writes the first k.  The candidates are totally ordered, so
+// the walk's order does not show in the result.  lse: the fold and the expression of rowstat_combine_kernel on the same records.
+__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void rowtopk_combine_kernel(const float4* part, const uint32_t* topk, int R, int ld, int ntn,
+                                                                               int col0, int k, int32_t* ids, float* logits, float* lse_out,
+                                                                               float* spare /* [ld] */) {
+    __shared__ unsigned long long sk[RS_GROUPS][TOPK_MAX][RS_ROWS];
+    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
+    const int row = blockIdx.x * RS_ROWS + rl;
+    unsigned long long best[TOPK_MAX];
+#pragma unroll
+    for (int e = 0; e < TOPK_MAX; ++e) best[e] = 0ull;
+    if (row < R)
+        for (int t = j; t < ntn; t += RS_GROUPS) {
+            const u32x4* rec = (const u32x4*)(topk + ((size_t)t * ld + row) * TOPK_MAX);
+            const u32x4 lo = rec[0], hi = rec[1];
+            const uint32_t key[TOPK_MAX] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+            for (int e = 0; e < TOPK_MAX; ++e) {
+                const unsigned long long c = topk_cand(key[e], t);
+                if (c <= best[TOPK_MAX - 1]) break;
+                topk_insert(best, c);
+            }
+        }
+#pragma unroll
+    for (int e = 0; e < TOPK_MAX; ++e) sk[j][e][rl] = best[e];
+    float m, sum;
+    int arg;
+    // (its barrier also orders the candidate lists above)
+    if (!rowstat_fold([&](int t, int r) { return part[(size_t)t * ld + r]; }, row, R, ntn, m, sum, arg)) return;
+    for (int q = 1; q < RS_GROUPS; ++q)
+#pragma unroll
+        for (int e = 0; e < TOPK_MAX; ++e) {
+            const unsigned long long c = sk[q][e][rl];
+            if (c <= best[TOPK_MAX - 1]) break;
+            topk_insert(best, c);
+        }
+#pragma unroll
+    for (int e = 0; e < TOPK_MAX; ++e)
+        if (e < k) {
+            ids[(size_t)row * k + e] = col0 + (int)~(uint32_t)best[e];
+            logits[(size_t)row * k + e] = topk_key_logit((uint32_t)(best[e] >> 32) << 16);
+        }
+    rowstat_finish(row, m, sum, arg, -1, 0.f, spare, lse_out, nullptr, nullptr);
+}
+
+int launch_head_rowtopk(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, int k, void* part, int32_t* ids,
+                        float* logits, float* lse, hipStream_t s) {
+    if (R <= 0 || N <= 0) return 0;
+    if (k < 1 || k > TOPK_MAX || k > N) return mm_fail("head top-k: k=%d outside [1, min(%d, N=%d)]", k, TOPK_MAX, N);
+    const int rp = (R + 7) / 8 * 8, ntn = rowstat_tiles(N);
+    GemmArgs g = gemm_bt_args(A, W, nullptr, rp, N, K, 8);
+    RowTopkArgs tk;
+    tk.rs = RowStatArgs{(float4*)part, (float*)((float4*)part + (size_t)rp * ntn), nullptr, R, rp, col0};
+    tk.topk = (uint32_t*)(tk.rs.tx + rp);
+    set_rowtopk_args(g, tk);
+    if (launch_gemm(EPI_ROWTOPK, g, s)) return 1;
+    hipLaunchKernelGGL(rowtopk_combine_kernel, dim3((R + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, tk.rs.part, tk.topk,
+                       R, rp, ntn, col0, k, ids, logits, lse, tk.rs.tx);
     MM_CHECK_HIP(hipGetLastError());
     return 0;
 }

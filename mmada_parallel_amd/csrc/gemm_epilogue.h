@@ -99,6 +99,24 @@ MM_DEVICE int lds_ldi(int byte_off) { return *(lds_i32_ptr)(uint32_t)byte_off; }
 MM_DEVICE void lds_sti(int byte_off, int v) { *(lds_i32_ptr)(uint32_t)byte_off = v; }
 #pragma clang diagnostic pop
 
+// ---- EPI_ROWTOPK: EPI_ROWSTAT plus the tile's eight best logits per row (kernels.h: RowTopkArgs, topk_key).  The same three steps:
+//   1. also, per slot: the lane's keys (16 in the transposed layout, 4 in the other), then eight rounds of { the lane's best
+//      remaining key ; the best of the lanes that share the row (__shfl_xor, as for the maximum) ; the lane that holds the winner
+//      retires it — keys are distinct, an equality compare finds it }.  The writer lane stores the wave column's eight keys (two
+//      16-byte LDS stores) behind the RowStatLds arrays: 4 wave columns x 320 rows x 32 B;
+//   3. the thread that joins tile row r merges the four sorted lists (eight rounds over the four list heads) and writes the
+//      32-byte record as two 16-byte stores.
+// Columns beyond N carry key 0, below every real key (the order value of -inf is 0x007f); a retired key is 0 too.
+struct RowTopkLds {
+    static constexpr int KEYS = RowStatLds::BYTES, BYTES = KEYS + RowStatLds::ROWS * RowStatLds::WAVES * TOPK_MAX * 4;
+};
+typedef __attribute__((address_space(3))) u32x4* lds_u32x4_ptr;
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wint-to-pointer-cast"
+MM_DEVICE void lds_st128(int byte_off, u32x4 v) { *(lds_u32x4_ptr)(uint32_t)byte_off = v; }
+#pragma clang diagnostic pop
+MM_DEVICE uint32_t umax32(uint32_t a, uint32_t b) { return a > b ? a : b; }
+
 MM_DEVICE void rowstat_take(float& m, int& a, float om, int oa) {   // torch's arg-max tie rule: the first index wins
     if (om > m || (om == m && oa < a)) { m = om; a = oa; }
 }
@@ -113,7 +131,8 @@ MM_DEVICE int rowstat_target(const GemmArgs& g, const RowStatArgs& rs, int m) {
 }
 
 // TR: transposed accumulator layout (gemm_epilogue_t) or not (gemm_epilogue); lds: byte address of RowStatLds::BYTES free bytes
-template <bool TR, int TM, int TN, int WN>
+// (TOPK, the EPI_ROWTOPK form: RowTopkLds::BYTES)
+template <bool TR, int TM, int TN, int WN, bool TOPK = false>
 MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim, int lds,
                                  int bm /* rows of the workgroup's tile, <= RowStatLds::ROWS */) {
 #pragma clang fp contract(off)
@@ -141,7 +160,9 @@ MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[
 #pragma unroll
     for (int sl = 0; sl < NS; ++sl) {
         const int rt = slot_row(sl), m = m0 + rt;
-        const int tc = m < rows ? rowstat_target(g, rs, m) : -1;
+        int tc;
+        if constexpr (TOPK) tc = m < rows && rs.target ? rowstat_target(g, rs, m) : -1;
+        else tc = m < rows ? rowstat_target(g, rs, m) : -1;
         const int c0 = wcol0 + (TR ? lq * 4 : l15);
         float bm = NEG;
         int ba = c0;
@@ -172,6 +193,41 @@ MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[
         if (writer) {
             lds_stf(lds + RowStatLds::MAX + (wn * RowStatLds::ROWS + rt) * 4, bm);
             lds_sti(lds + RowStatLds::ARG + (wn * RowStatLds::ROWS + rt) * 4, ba);
+        }
+        if constexpr (TOPK) {
+            constexpr int NR = TR ? 4 : 1, NV = FN * NR;
+            uint32_t key[NV], win[TOPK_MAX];
+#pragma unroll
+            for (int ni = 0; ni < FN; ++ni)
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    const int ct = wn * TN + ni * 16 + (TR ? lq * 4 + r : l15);   // column inside the 256-column tile
+                    float a;
+                    if constexpr (TR) a = acc[sl][ni][r];
+                    else a = acc[sl >> 2][ni][sl & 3];
+                    key[ni * NR + r] = n0 + ct < g.N ? topk_key(bfround(a), ct) : 0u;
+                }
+#pragma unroll
+            for (int e = 0; e < TOPK_MAX; ++e) {
+                uint32_t b = key[0];
+#pragma unroll
+                for (int i = 1; i < NV; ++i) b = umax32(b, key[i]);
+                if constexpr (TR) {
+                    b = umax32(b, __shfl_xor(b, 16, 64));
+                    b = umax32(b, __shfl_xor(b, 32, 64));
+                } else {
+#pragma unroll
+                    for (int o = 1; o < 16; o <<= 1) b = umax32(b, __shfl_xor(b, o, 64));
+                }
+                win[e] = b;
+#pragma unroll
+                for (int i = 0; i < NV; ++i) key[i] = key[i] == b ? 0u : key[i];
+            }
+            if (writer) {
+                const int at = lds + RowTopkLds::KEYS + (wn * RowStatLds::ROWS + rt) * (TOPK_MAX * 4);
+                lds_st128(at, u32x4{win[0], win[1], win[2], win[3]});
+                lds_st128(at + 16, u32x4{win[4], win[5], win[6], win[7]});
+            }
         }
     }
     __syncthreads();
@@ -224,6 +280,30 @@ MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[
             if (mw[w] > mt) { mt = mw[w]; at = aw[w]; }   // wave columns ascend: a later equal maximum does not replace
         const float st = (sw[0] + sw[1]) + (sw[2] + sw[3]);
         rs.part[(size_t)(n0 / (TN * WN)) * rs.ld + m] = float4{mt, st, __int_as_float(at + rs.col0), 0.f};
+        if constexpr (TOPK) {
+            int at4[WN];
+            uint32_t head[WN], best[TOPK_MAX];
+#pragma unroll
+            for (int w = 0; w < WN; ++w) {
+                at4[w] = lds + RowTopkLds::KEYS + (w * RowStatLds::ROWS + rt) * (TOPK_MAX * 4);
+                head[w] = (uint32_t)lds_ldi(at4[w]);
+            }
+#pragma unroll
+            for (int e = 0; e < TOPK_MAX; ++e) {
+                const uint32_t b = umax32(umax32(head[0], head[1]), umax32(head[2], head[3]));
+                best[e] = b;
+                if (e + 1 < TOPK_MAX) {   // the list that held the winner moves on (b = 0: every list is exhausted, zeros follow)
+#pragma unroll
+                    for (int w = 0; w < WN; ++w) {
+                        at4[w] += head[w] == b ? 4 : 0;
+                        head[w] = (uint32_t)lds_ldi(at4[w]);
+                    }
+                }
+            }
+            u32x4* dst = (u32x4*)(rowtopk_args(g).topk + ((size_t)(n0 / (TN * WN)) * rs.ld + m) * TOPK_MAX);
+            dst[0] = u32x4{best[0], best[1], best[2], best[3]};
+            dst[1] = u32x4{best[4], best[5], best[6], best[7]};
+        }
     }
 }
 
@@ -232,9 +312,13 @@ MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[
 //     acc[mi][ni][r] = D[m][n],  m = m0 + wm*TM + mi*16 + (lane>>4)*4 + r,  n = n0 + wn*TN + ni*16 + (lane&15)
 template <int EPI, int TM, int TN, int WN>
 MM_DEVICE void gemm_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim,
-                             int lds = 0, int bm = 0 /* EPI_ROWSTAT: free LDS (byte address), rows of the tile */) {
+                             int lds = 0, int bm = 0 /* EPI_ROWSTAT, EPI_ROWTOPK: free LDS (byte address), rows of the tile */) {
     if constexpr (EPI == EPI_ROWSTAT) {
         if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<false, TM, TN, WN>(g, m0, n0, acc, wave, lane, m_lim, lds, bm);
+        return;
+    }
+    if constexpr (EPI == EPI_ROWTOPK) {
+        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<false, TM, TN, WN, true>(g, m0, n0, acc, wave, lane, m_lim, lds, bm);
         return;
     }
     constexpr int FM = TM / 16, FN = TN / 16;
@@ -399,6 +483,10 @@ MM_DEVICE void gemm_epilogue_t(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[T
                                 int lut_lds = -1 /* LDS byte address of the SiLU table, or -1 */) {
     if constexpr (EPI == EPI_ROWSTAT) {   // the 8-phase kernel owns the LDS from address 0; its main loop is behind a barrier
         if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<true, TM, TN, WN>(g, m0, n0, acc, wave, lane, m_lim, 0, TM * (8 / WN));
+        return;
+    }
+    if constexpr (EPI == EPI_ROWTOPK) {
+        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<true, TM, TN, WN, true>(g, m0, n0, acc, wave, lane, m_lim, 0, TM * (8 / WN));
         return;
     }
     constexpr int FM = TM / 16, FN = TN / 16;

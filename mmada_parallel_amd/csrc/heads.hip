@@ -1,5 +1,5 @@
 // heads.hip — the LM head on demand: logit rows of the resident forward (mmada_head_rows) or of a dLLM-cache slot
-// (mmada_cache_head_rows), and the fused scoring head (mmada_head_logprobs).  Host code only.
+// (mmada_cache_head_rows), the fused scoring head (mmada_head_logprobs) and its top-k form (mmada_head_topk).  Host code only.
 #include "../../include/mmada_mi355x.h"
 #include "handle.h"
 
@@ -24,7 +24,7 @@ static int store_logits(const mmada_handle* h, const bf16_t* xg, int R, int col_
     return launch_gemm(EPI_STORE, gemm_bt_args(xg, h->lm_head + (size_t)col_begin * d, (bf16_t*)out, R, N, d, N), s);
 }
 
-// the record buffer of mmada_head_logprobs holds at least `need` bytes
+// the record buffer of mmada_head_logprobs / mmada_head_topk holds at least `need` bytes
 static int grow_score_buffer(mmada_handle* h, size_t need, hipStream_t s) {
     if (need <= h->score_bytes) return 0;
     if (stream_capturing(s))
@@ -101,6 +101,28 @@ int mmada_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_beg
     return launch_head_rowstat(h->xg, h->lm_head + (size_t)col_begin * d, R, N, d, col_begin, targets, h->score_buf, logprob_out,
                                lse_out, argmax_out, max_out, s);
 }
+
+int mmada_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, int k, int32_t* ids_out,
+                    float* logit_out, float* lse_out, void* stream) {
+    if (k < 1 || k > MMADA_TOPK_MAX) return mm_fail("mmada_head_topk: k=%d outside [1, MMADA_TOPK_MAX=%d]", k, MMADA_TOPK_MAX);
+    if ((long long)k > (long long)col_end - col_begin)
+        return mm_fail("mmada_head_topk: k=%d exceeds the column range [%d, %d)", k, col_begin, col_end);
+    if (!h || !resident(h)) return mm_fail("mmada_head_topk: no forward resident");
+    if (!rows || !ids_out || !logit_out) return mm_fail("mmada_head_topk: null argument");
+    if (runs_tensor_parallel(h) || h->res.xn_is_final)
+        return mm_fail("mmada_head_topk: top-k runs on one rank (a handle without a tensor-parallel exchange): the vocabulary-parallel "
+                       "top-k, whose key records would ride the score exchange of mmada_head_logprobs, is a follow-up");
+    if (R <= 0) return 0;
+    if (check_head_range(h, "mmada_head_topk", R, h->res.B * h->res.L, col_begin, col_end)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    const int d = h->cfg.d_model, N = col_end - col_begin;
+    if (grow_score_buffer(h, head_rowtopk_bytes(R, N), s)) return 1;
+    if (gather_resident_rows(h, rows, R, s)) return 1;
+    return launch_head_rowtopk(h->xg, h->lm_head + (size_t)col_begin * d, R, N, d, col_begin, k, h->score_buf, ids_out, logit_out,
+                               lse_out, s);
+}
+
+unsigned mmada_topk_order_key(unsigned bf16_bits) { return topk_order(__builtin_bit_cast(float, (uint32_t)(bf16_bits & 0xffffu) << 16)) >> 16; }
 
 size_t mmada_score_buffer_bytes(const mmada_handle* h) { return h ? h->score_bytes : 0; }
 

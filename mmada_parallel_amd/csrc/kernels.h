@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include "common.h"
 
-enum GemmEpilogue { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_QKV = 3, EPI_ROWSTAT = 4 };
+enum GemmEpilogue { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_QKV = 3, EPI_ROWSTAT = 4, EPI_ROWTOPK = 5 };
 
 struct GemmArgs {
     const bf16_t* A;   // [M, lda]   activations, K-contiguous
@@ -70,6 +70,39 @@ static inline void set_rowstat_args(GemmArgs& g, const RowStatArgs& r) {
     g.rwin = r.rows; g.rlp = r.ld; g.rbeg = r.col0;
 }
 
+// EPI_ROWTOPK (the top-k head, launch_head_rowtopk): a superset of EPI_ROWSTAT.  The same 16-byte record with the same bits (and
+// the target logit, where `target` is not null — null: no row has one), plus per row and 256-column tile ONE 32-byte record
+// topk[(nt * ld + m) * 8 .. + 8): the tile's eight best logits as 32-bit keys in descending order (= logit descending, then
+// column ascending).  A key (topk_key below): high half = the bf16 bits of the logit mapped to an unsigned value of the same order,
+// low byte = 255 - column inside the tile; an unsigned compare is the whole order and the keys of a tile are distinct.  Places
+// beyond the tile's columns (N - 256 * nt < 8) hold 0, below every real key.  The extra pointer travels in GemmArgs::q.
+struct RowTopkArgs {
+    RowStatArgs rs;
+    uint32_t* topk;          // [ceil(N / 256)][ld][8] keys
+};
+static inline __host__ __device__ RowTopkArgs rowtopk_args(const GemmArgs& g) { return RowTopkArgs{rowstat_args(g), (uint32_t*)g.q}; }
+static inline void set_rowtopk_args(GemmArgs& g, const RowTopkArgs& r) {
+    set_rowstat_args(g, r.rs);
+    g.q = (bf16_t*)r.topk;
+}
+constexpr int TOPK_MAX = 8;   // = MMADA_TOPK_MAX (include/mmada_mi355x.h); entries of a tile's record
+// Order value of a bf16-rounded logit x (an fp32 whose low 16 bits are zero), in the HIGH half of the result: negatives with all
+// bits flipped, the rest with the sign bit flipped, so that an unsigned compare orders as the floats do.  -0.0 is taken as +0.0
+// first (x + 0.0f): torch's sort compares floats, for which the two are equal and the lower column wins.  NaN: outside the contract.
+static inline __host__ __device__ uint32_t topk_order(float x) {
+    const float c = x + 0.0f;
+    uint32_t u;
+    __builtin_memcpy(&u, &c, 4);
+    return u ^ ((uint32_t)((int32_t)u >> 31) & 0x7fff0000u) ^ 0x80000000u;
+}
+static inline __host__ __device__ uint32_t topk_key(float x, int col_in_tile) { return (topk_order(x) & 0xffff0000u) | (uint32_t)(255 - col_in_tile); }
+static inline __host__ __device__ float topk_key_logit(uint32_t key) {   // inverse of topk_order on the key's high half
+    const uint32_t o = key & 0xffff0000u, u = (o & 0x80000000u) ? o ^ 0x80000000u : o ^ 0xffff0000u;
+    float x;
+    __builtin_memcpy(&x, &u, 4);
+    return x;
+}
+
 // A plain C[M, ldc] = A[M, K] · W[N, K]^T on K-contiguous operands (lda = ldw = K), epilogue fields left zero.
 static inline GemmArgs gemm_bt_args(const bf16_t* A, const bf16_t* W, bf16_t* C, int M, int N, int K, int ldc) {
     GemmArgs g{};
@@ -93,6 +126,13 @@ Switches switches();
 size_t head_rowstat_bytes(int R, int N);
 int launch_head_rowstat(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, const int64_t* targets, void* part,
                         float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s);
+
+// gemm.hip: the top-k head.  Same operands; `part` holds head_rowtopk_bytes(R, N) bytes: the row-statistics records, ceil8(R)
+// floats, then the 32-byte key records (kernels.h: RowTopkArgs).  ids [R, k] (column in the whole vocabulary) and logits [R, k] in
+// the order logit descending, column ascending; lse [R] or null: the bits launch_head_rowstat returns.  1 <= k <= TOPK_MAX, k <= N.
+size_t head_rowtopk_bytes(int R, int N);
+int launch_head_rowtopk(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, int k, void* part, int32_t* ids,
+                        float* logits, float* lse, hipStream_t s);
 
 // elementwise.hip
 // norm_w != null: also xn = RMSNorm(x) * norm_w (the first norm of the forward, fused: SURVEY §2.3 K1)

@@ -83,6 +83,7 @@ IMAGE_START_TOKEN, IMAGE_END_TOKEN = 126349, 126350
 ANSWER_START_TOKEN, ANSWER_END_TOKEN = 126354, 126355
 BREAKLINE_TOKEN = 126084
 IGNORE_INDEX = -100
+TOPK_MAX = 8   # MMADA_TOPK_MAX (include/mmada_mi355x.h): entries the top-k head keeps per row
 
 
 def pad_id_lists(input_ids, labels=None):
@@ -460,6 +461,35 @@ class LLaDAForMultiModalGeneration(TpLinkMixin):
                 abi.check(self._lib.mmada_head_logprobs(handle, row_t.data_ptr(), hi - lo, col_begin, col_end, *ptrs,
                                                         abi.stream_ptr()), "mmada_head_logprobs")
         return (lp, *stats) if return_stats else lp
+
+    _TP_TOPK = ("top_logprobs runs on one rank: the library's top-k head (mmada_head_topk) refuses a tensor-parallel handle; the "
+                "vocabulary-parallel top-k, whose key records would ride the score exchange, is a follow-up")
+
+    def top_logprobs(self, rows: torch.Tensor, k: int, col_begin: int = 0, col_end: Optional[int] = None):
+        """The k likeliest columns of logits[rows[r], col_begin:col_end] after forward_body(), without materialising the logits
+        (mmada_head_topk: the scoring head's GEMM also keeps every 256-column tile's eight best).  Returns (ids int32 [R, k] —
+        column in the WHOLE vocabulary —, logprobs fp32 [R, k], lse fp32 [R]); 1 <= k <= 8, k <= col_end - col_begin.
+
+        Order of a row: logit descending, then column ascending (a stable descending sort).  logprobs = logit - lse in fp32, the
+        expression of token_logprobs: top_logprobs(rows, k)[1][:, j] equals token_logprobs(rows, ids[:, j]) bit for bit, and lse,
+        ids[:, 0] are its lse / argmax.  rows as in token_logprobs (batch-major on a micro-batched forward).  One rank only."""
+        if self.tp_size != 1 or self._comm_in_library:
+            raise NotImplementedError(self._TP_TOPK)
+        col_end = self.vocab if col_end is None else col_end
+        if not 1 <= k <= TOPK_MAX or k > col_end - col_begin:
+            raise ValueError(f"top_logprobs: k={k} outside [1, min({TOPK_MAX}, col_end - col_begin)]")
+        rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
+        R = rows.numel()
+        ids = torch.empty((R, k), dtype=torch.int32, device=self.device)
+        logit = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        lse = torch.empty(R, dtype=torch.float32, device=self.device)
+        res = self._resident
+        cut = None if res.split is None else counted_cut(rows, res.split * res.shape[1])
+        for handle, lo, hi, row_t in self._lane_calls(R, cut, rows):
+            if hi > lo:
+                abi.check(self._lib.mmada_head_topk(handle, row_t.data_ptr(), hi - lo, col_begin, col_end, k, ids[lo:hi].data_ptr(),
+                                                    logit[lo:hi].data_ptr(), lse[lo:hi].data_ptr(), abi.stream_ptr()), "mmada_head_topk")
+        return ids, logit - lse[:, None], lse
 
     def score(self, input_ids: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         """Per-token negative log-likelihood, fp32 [B, L]: -log softmax(logits[b, l])[labels[b, l]], 0 where labels == -100 —

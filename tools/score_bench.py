@@ -21,7 +21,17 @@ device (tp_link.connect_local_group, pull transport): they share its compute uni
                            SUMMED device time of the k ranks (k tile-range GEMMs + k hand-offs per round + k joins of every row)
   (h)  one TP rank, torch  head_rows + torch log_softmax + gather on rank 0 of the group (what a TP rank could do before)
 
-(t) / (c) is what the split and the k joins cost on top of the one-rank call; on k devices each rank's share runs in parallel."""
+(t) / (c) is what the split and the k joins cost on top of the one-rank call; on k devices each rank's share runs in parallel.
+
+    python tools/score_bench.py --topk 8 [--out profiles/topk_bench.txt]
+
+--topk K: the K likeliest columns of every row and the row's lse, three ways, timed the same way (interleaved, device events):
+
+  (a) torch     mmada_head_rows over the whole vocabulary + torch.topk(K) + torch.logsumexp on those logits (as fp32)
+  (c) fused     mmada_head_logprobs: the plain row-statistics head (one target per row, no top-k) — what (d) adds its work to
+  (d) top-k     mmada_head_topk: the same GEMM whose epilogue also keeps every tile's eight best + the key-joining kernel
+
+and the peak device memory (a) and (d) add while they run (torch's allocator; for (d) plus the library's record buffer)."""
 import argparse
 import os
 import statistics
@@ -131,15 +141,106 @@ def main_tp(args):
         f.write(text + "\n")
 
 
+def peak_added(fn, dev):
+    """Bytes torch's allocator holds at its peak while fn() runs, above what it held before."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    before = torch.cuda.memory_allocated(dev)
+    out = fn()
+    torch.cuda.synchronize()
+    grew = torch.cuda.max_memory_allocated(dev) - before
+    del out
+    return grew
+
+
+def main_topk(args):
+    from mmada_parallel_amd import abi
+
+    dev, K = "cuda:0", args.topk
+    cfg = dict(synth.CFG_8B, n_layers=1)
+    sd = synth.synthetic_state_dict(cfg, seed=3, device=dev)
+    model = LLaDAForMultiModalGeneration.from_state_dict(synth.full_config(cfg), sd, device=dev, max_batch=2)
+    del sd
+    V = model.vocab
+    lines = [f"score_bench --topk {K}: {torch.cuda.get_device_name(0)}, d = {cfg['d_model']}, V = {V}, {args.rounds} rounds x {args.reps} calls, "
+             "device events, ms per call"]
+    for B in (1, 2):
+        L = 2438
+        R = B * L
+        g = torch.Generator().manual_seed(5 + B)
+        ids = torch.randint(0, 126000, (B, L), generator=g).to(dev)
+        targets = torch.randint(0, V, (R,), generator=g).to(dev)
+        rows = torch.arange(R, dtype=torch.int32, device=dev)
+        model.forward_body(ids)
+
+        def run_a():
+            lf = model.head_rows(rows, 0, V).float()
+            v, i = torch.topk(lf, K, dim=1)
+            return i, v, torch.logsumexp(lf, 1)
+
+        def run_c():
+            return model.token_logprobs(rows, targets)
+
+        def run_d():
+            return model.top_logprobs(rows, K)
+
+        fns = {"a": run_a, "c": run_c, "d": run_d}
+        # the results agree: the same logits, the same lse to fp32 rounding (torch.topk leaves the order of ties to the build)
+        (ia, va, la), (idd, lpd, lsd) = run_a(), run_d()
+        torch.cuda.synchronize()
+        assert float((va - (lpd + lsd[:, None])).abs().max()) < 1e-4   # logprob + lse is the logit again, to fp32 rounding
+        same_ids = float((ia == idd).float().mean())
+        worst = float((la - lsd).abs().max())
+        del ia, va, la, idd, lpd, lsd
+        for f in fns.values():   # warm-up of every timed shape
+            f()
+        torch.cuda.synchronize()
+        mem_a, mem_d = peak_added(run_a, dev), peak_added(run_d, dev)
+        own = abi.lib().mmada_score_buffer_bytes(model._handle)
+        times = {k: [] for k in fns}
+        order = ["a", "c", "d"]
+        for r in range(args.rounds):
+            for k in order[r % 3:] + order[:r % 3]:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.reps):
+                    fns[k]()
+                e1.record()
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) / args.reps)
+        med = {k: statistics.median(v) for k, v in times.items()}
+        da = [d / a for a, d in zip(times["a"], times["d"])]
+        dc = [d / c for c, d in zip(times["c"], times["d"])]
+        lines.append(f"R = {R} (B = {B}, L = {L}); ids equal to torch.topk's on {100 * same_ids:.3f} % of the entries (ties: torch's order is "
+                     f"unspecified); max |lse - torch.logsumexp| {worst:.2e}")
+        names = {"a": f"(a) head_rows + torch.topk({K}) + logsumexp", "c": "(c) mmada_head_logprobs (fused, no top-k)", "d": "(d) mmada_head_topk"}
+        for k in order:
+            lines.append(f"  {names[k]:44s} median {med[k]:8.3f}  min {min(times[k]):8.3f}  max {max(times[k]):8.3f}")
+        lines.append(f"  (d) / (a): median of rounds {statistics.median(da):.4f}  min {min(da):.4f}  max {max(da):.4f};   "
+                     f"(d) / (c): median of rounds {statistics.median(dc):.4f}  min {min(dc):.4f}  max {max(dc):.4f}")
+        lines.append(f"  peak memory added: (a) {mem_a / 2**20:.1f} MiB (bf16 logits {R * V * 2 / 2**20:.1f} MiB + torch's fp32 temporaries);  "
+                     f"(d) {mem_d / 2**20:.3f} MiB of torch tensors + {own / 2**20:.1f} MiB record buffer held by the library")
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=12)
     ap.add_argument("--reps", type=int, default=4, help="calls per timed window")
     ap.add_argument("--tp", type=int, default=0, help="k > 1: the functional tensor-parallel rig (k ranks on one device)")
+    ap.add_argument("--topk", type=int, default=0, help="K in 1..8: top-k three ways (torch on the logits, the plain fused head, mmada_head_topk)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "score_tp_bench.txt" if args.tp else "score_bench.txt")
+        args.out = os.path.join(ROOT, "profiles", "score_tp_bench.txt" if args.tp else "topk_bench.txt" if args.topk else "score_bench.txt")
+    if args.topk:
+        if args.tp or not 1 <= args.topk <= 8:
+            ap.error("--topk takes K in 1..8 and no --tp")
+        return main_topk(args)
     if args.tp:
         if args.tp not in (2, 4, 8):
             ap.error("--tp must be 2, 4 or 8")
