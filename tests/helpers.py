@@ -293,3 +293,196 @@ def tp_each(ranks, streams, fn):
         cur.wait_stream(s)
     torch.cuda.synchronize()
     return out
+
+
+# ---- block 0, stage by stage, against the oracle (tests/test_gpu_model.py, tests/test_gpu_qkv.py) ----
+def relerr(got, ref):
+    got, ref = got.float().cpu(), ref.float().cpu()
+    return ((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item(), \
+           ((got - ref).abs().mean() / ref.abs().mean().clamp_min(1e-30)).item()
+
+
+def check_block_stages(model, cfg, sd, ids):
+    """Every intermediate of block 0 (RMSNorm, q/k after RoPE, V, SDPA output, residual adds, SiLU-gated hidden) of `model`
+    against the oracle's value of the same tensor; errors are relative to each tensor's own magnitude, so a wrong branch
+    cannot hide behind the (much larger) residual stream.  cfg: the checkpoint's base config (d_model, n_heads, rms_norm_eps,
+    rope_theta); the number of kv heads is the model's (grouped heads are expanded as the reference does, :666-669)."""
+    import torch.nn.functional as F
+    from mmada_parallel_amd import abi
+    from oracle import llada_oracle as lo
+
+    dev = model.device
+    B, L = ids.shape
+    H, Hkv, hd, eps = cfg["n_heads"], model.n_kv_heads, 128, cfg["rms_norm_eps"]
+    w = lo.layer_weights(sd, 0)
+    x0 = F.embedding(ids, sd["model.transformer.wte.weight"])
+    xn = lo.rms_norm(x0, w["attn_norm"], eps)
+    q = F.linear(xn, w["q_proj"]).view(B, L, H, hd).transpose(1, 2)
+    k = F.linear(xn, w["k_proj"]).view(B, L, Hkv, hd).transpose(1, 2)
+    v = F.linear(xn, w["v_proj"]).view(B, L, Hkv, hd).transpose(1, 2)
+    sin, cos = lo.rope_tables(L, hd, cfg["rope_theta"])
+    q, k = lo.apply_rope(q, sin, cos), lo.apply_rope(k, sin, cos)
+    ke, ve = (k, v) if Hkv == H else (k.repeat_interleave(H // Hkv, dim=1), v.repeat_interleave(H // Hkv, dim=1))
+    att = F.scaled_dot_product_attention(q, ke, ve).transpose(1, 2).contiguous().view(B, L, H * hd)
+    x1 = x0 + F.linear(att, w["attn_out"])
+    n2 = lo.rms_norm(x1, w["ff_norm"], eps)
+    hmid = F.silu(F.linear(n2, w["ff_proj"])) * F.linear(n2, w["up_proj"])
+    x2 = x1 + F.linear(hmid, w["ff_out"])
+
+    lib, h = model._lib, model._handle
+    ids_d = ids.to(dev)
+    model._ensure_ws(B, L)
+    model._shape = (B, L)
+    st = abi.stream_ptr()
+    abi.check(lib.mmada_embed(h, ids_d.data_ptr(), B, L, st), "embed")
+    e_x0 = relerr(model.hidden_state(), x0)
+    abi.check(lib.mmada_attn_partial(h, 0, st), "attn")
+    Lp = (L + 7) // 8 * 8
+    got = {
+        "xn": model.debug_buffer(0).view(B, Lp, -1)[:, :L],
+        "q": model.debug_buffer(1)[:, :, :L],
+        "k": model.debug_buffer(2)[:, :, :L],
+        "v": model.debug_buffer(3)[:, :, :, :L].transpose(2, 3),
+        "att": model.debug_buffer(4).view(B, Lp, -1)[:, :L],
+        "x1": model.hidden_state(),
+    }
+    got = {k_: v_.clone() for k_, v_ in got.items()}
+    abi.check(lib.mmada_mlp_partial(h, 0, st), "mlp")
+    got["n2"] = model.debug_buffer(0).view(B, Lp, -1)[:, :L].clone()
+    got["h"] = model.debug_buffer(5).view(B, Lp, -1)[:, :L].clone()
+    got["x2"] = model.hidden_state()
+    ref = {"xn": xn, "q": q, "k": k, "v": v, "att": att, "x1": x1, "n2": n2, "h": hmid, "x2": x2}
+    report = {"x0": e_x0}
+    for name in ref:
+        report[name] = relerr(got[name], ref[name])
+    print("stage errors (max/maxabs, mean/meanabs):", {k_: (f"{a:.2e}", f"{b:.2e}") for k_, (a, b) in report.items()})
+    assert report["x0"][0] == 0.0
+    # the branch deltas, not just the stream: attention and MLP contributions themselves
+    report["d_attn"] = relerr(got["x1"].float().cpu() - x0.float(), x1.float() - x0.float())
+    report["d_mlp"] = relerr(got["x2"].float().cpu() - got["x1"].float().cpu(), x2.float() - x1.float())
+    print("branch deltas:", report["d_attn"], report["d_mlp"])
+    for name, (emax, emean) in report.items():
+        # bf16 storage everywhere: a few ulps (2^-8) of the tensor's magnitude; deltas are differences of bf16 values
+        lim_max, lim_mean = (0.25, 0.05) if name.startswith("d_") else (2.0 ** -5, 2.0 ** -8)
+        assert emax < lim_max and emean < lim_mean, f"{name}: {emax:.3e} {emean:.3e}"
+    return report
+
+
+# ---- the QKV epilogue, exactly (tests/test_gpu_qkv.py, tests/test_qkv_host.py) ----
+# (n_heads, n_kv_heads): today's layout; grouped heads; multi_query_attention=True; a K head and the V head in ONE 256-column tile
+# (the fused projection has 3 + 1 + 1 heads of 128 columns: K is columns 384..511, V 512..639)
+QKV_LAYOUTS = [(2, 2), (4, 2), (4, 1), (3, 1)]
+QKV_VOCAB, QKV_MAX_SEQ = 1024, 4096
+QKV_SCALES = (0.5, 1.0, 2.0, -0.5, -1.0, -2.0)
+QKV_DIFF_CAP = 1e-4          # share of q / k elements that may differ from the oracle at all (each by one bf16 ulp at most)
+BF16_DENORMAL_STEP = 2.0 ** -133
+
+
+def qkv_exact_checkpoint(n_heads, n_kv_heads, seed=0):
+    """A one-layer checkpoint with d_model = 128 * n_heads whose q / k / v projections are EXACT: every row of q_proj, k_proj and
+    v_proj has one non-zero entry, a power of two from QKV_SCALES, in a column drawn from a seeded random map (no two rows of a
+    projection pull the same column), so each pre-activation is one product xn[col] * 2^e — the same bf16 value in the MFMA and
+    in the oracle's bf16 F.linear.  Everything else is the usual seeded random checkpoint, except wte ~ N(0, 1).
+
+    Returns a namespace: cfg (what the model class takes; (4, 1) is spelled multi_query_attention=True as a config would),
+    base (the same with n_kv_heads explicit: what synth and the oracle take), sd, maps {'q' | 'k' | 'v': (column, scale)}."""
+    d, kv = 128 * n_heads, 128 * n_kv_heads
+    base = dict(d_model=d, n_heads=n_heads, n_kv_heads=n_kv_heads, n_layers=1, mlp_hidden_size=512, vocab_size=QKV_VOCAB,
+                embedding_size=QKV_VOCAB, rms_norm_eps=1e-5, rope_theta=500000.0, max_sequence_length=QKV_MAX_SEQ)
+    sd = synth.synthetic_state_dict(base, seed=seed)
+    g = torch.Generator().manual_seed(7919 * seed + 16 * n_heads + n_kv_heads)
+    p = "model.transformer."
+    sd[p + "wte.weight"] = torch.randn(QKV_VOCAB, d, generator=g).to(torch.bfloat16)
+    maps = {}
+    for name, rows in (("q", d), ("k", kv), ("v", kv)):
+        col = torch.randperm(d, generator=g)[:rows]
+        scale = torch.tensor(QKV_SCALES)[torch.randint(0, len(QKV_SCALES), (rows,), generator=g)]
+        w = torch.zeros(rows, d)
+        w[torch.arange(rows), col] = scale
+        sd[f"{p}blocks.0.{name}_proj.weight"] = w.to(torch.bfloat16)
+        maps[name] = (col, scale)
+    cfg = synth.full_config(base)
+    if (n_heads, n_kv_heads) == (4, 1):
+        cfg.update(n_kv_heads=None, multi_query_attention=True)
+    return SimpleNamespace(cfg=cfg, base=base, sd=sd, maps=maps, n_heads=n_heads, n_kv_heads=n_kv_heads)
+
+
+_ROPE = {}
+
+
+def qkv_rope_rows(pos, theta=500000.0):
+    """(sin, cos) [B, 1, T, 128] of the oracle's fp32 tables at the rotary positions pos [B, T]."""
+    from oracle import llada_oracle as lo
+
+    if theta not in _ROPE:
+        _ROPE[theta] = lo.rope_tables(QKV_MAX_SEQ, 128, theta)
+    sin, cos = _ROPE[theta]
+    return sin[0, 0][pos][:, None], cos[0, 0][pos][:, None]
+
+
+def qkv_pre(ck, xn, name):
+    """The exact pre-activation of projection `name` ('q' | 'k' | 'v') for xn [B, T, d] bf16: [B, heads, T, 128] bf16."""
+    col, scale = ck.maps[name]
+    B, T, _ = xn.shape
+    t = (xn.float()[:, :, col] * scale).to(torch.bfloat16)       # one product by a power of two: exact
+    return t.view(B, T, col.numel() // 128, 128).transpose(1, 2).contiguous()
+
+
+def qkv_expected(ck, xn, pos_q, pos_k):
+    """What the QKV epilogue must write for the block input xn [B, T, d] (bf16, CPU): q rotated at pos_q [B, T], k rotated at
+    pos_k [B, T] — oracle.llada_oracle.apply_rope, the reference's fp32 arithmetic — and V as it is.  Returns (q, k, v, tq, tk),
+    [B, heads, T, 128] each; tq, tk are the un-rotated q and k (the operands of the rotation: qkv_rope_verdict's floor)."""
+    from oracle import llada_oracle as lo
+
+    theta = ck.base["rope_theta"]
+    tq, tk = qkv_pre(ck, xn, "q"), qkv_pre(ck, xn, "k")
+    q = lo.apply_rope(tq, *qkv_rope_rows(pos_q, theta))
+    k = lo.apply_rope(tk, *qkv_rope_rows(pos_k, theta))
+    return q, k, qkv_pre(ck, xn, "v"), tq, tk
+
+
+def same_values(a, b):
+    """Equal as VALUES (+0 == -0; a NaN equals nothing)."""
+    return bool((a.float() == b.float()).all())
+
+
+def qkv_rope_verdict(got, ref, pre):
+    """The conditions on a rotated tensor against the oracle's `ref`; `pre` is the un-rotated tensor.  Returns (every element
+    within one bf16 ulp of the oracle, the share of elements that differ at all, the number of elements that needed the floor).
+
+    One ulp: |got - ref| <= 2^-7 |ref| + floor.  The floor is the reference's OWN fp32 error, which a bf16 ulp of the result does
+    not cover where the rotation cancels: an output is fl(t1 * c) -+ fl(t2 * s) in fp32 (t1, t2: the element and its rotary
+    partner, c, s: table entries), torch's fp32 sin / cos is within one fp32 ulp of the correctly rounded value
+    rope_table_kernel stores, so each product may move by 2^-23 |t| for the table entry plus two roundings of 2^-24 |t|:
+    floor = 2^-22 (|t1| + |t2|), plus one bf16 denormal step.  With |ref| below 2^-15 of the operands that exceeds a bf16 ulp of
+    ref: measured, 1 element of 2 097 152 (q of layout (4, 2) at L = 4096: ref 2.98e-7, got 3.28e-7 from operands -0.586 and
+    0.719, the cosine one fp32 ulp apart), reproduced on the CPU with the kernel's table convention.  Anywhere else the floor is
+    2^-14 of a bf16 ulp."""
+    g, r, t = got.float(), ref.float(), pre.float().abs()
+    diff = (g - r).abs()
+    rel = 2.0 ** -7 * r.abs() + BF16_DENORMAL_STEP
+    floor = 2.0 ** -22 * (t + t.roll(64, dims=-1))
+    within = bool((diff <= rel + floor).all())
+    return within, float((diff > 0).float().mean()), int((diff > rel).sum())
+
+
+def qkv_assert_rope(name, got, ref, pre, record=None):
+    within, share, floored = qkv_rope_verdict(got, ref, pre)
+    print(f"{name}: share of elements that differ from the oracle {share:.3e} (cap {QKV_DIFF_CAP:.0e}), all within one ulp: {within}"
+          f" ({floored} of {got.numel()} under cancellation, by the fp32 floor)")
+    if record is not None:
+        record[name] = {"share_differing": share, "elements": got.numel(), "within_by_fp32_floor_only": floored}
+    assert within, f"{name}: an element is more than one bf16 ulp from the oracle"
+    assert share <= QKV_DIFF_CAP, f"{name}: {share:.3e} of the elements differ from the oracle"
+
+
+def vt_key_pos(l):
+    """csrc/common.h vt_key_pos restated: storage position of key l inside the K-major V buffer."""
+    c = (l >> 2) & 7
+    return (l & ~28) | ((c & 3) << 3) | ((c >> 2) << 2)
+
+
+def vt_unpermute(t):
+    """[..., Lkv] in vt_key_pos storage order -> key order."""
+    idx = torch.tensor([vt_key_pos(l) for l in range(t.shape[-1])], device=t.device)
+    return t[..., idx]

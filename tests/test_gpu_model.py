@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, ROOT, SAMPLER_CASES, STUB_CB, STUB_TEXT_VOCAB, bits, from_bits, golden_float, stub_logits, tiny_job, tiny_sd
+from helpers import (GOLDEN, ROOT, SAMPLER_CASES, STUB_CB, STUB_TEXT_VOCAB, bits, check_block_stages, from_bits, golden_float, stub_logits,
+                     tiny_job, tiny_sd)
 from mmada_parallel_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -30,78 +31,16 @@ def tiny_model():
 
 
 # ------------------------------------------------------------------------------------------------ (ii) model tolerance
-def _relerr(got, ref):
-    got, ref = got.float().cpu(), ref.float().cpu()
-    return ((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item(), \
-           ((got - ref).abs().mean() / ref.abs().mean().clamp_min(1e-30)).item()
-
-
 @pytest.mark.parametrize("B", [1, 2])
 def test_block_stages_vs_oracle(tiny_model, B):
     """Every intermediate of block 0 (RMSNorm, q/k after RoPE, V, SDPA output, residual adds, SiLU-gated hidden)
     against the oracle's value of the same tensor; errors are relative to each tensor's own magnitude, so a wrong
-    branch cannot hide behind the (much larger) residual stream."""
-    import torch.nn.functional as F
-    from mmada_parallel_amd import abi
-    from oracle import llada_oracle as lo
-
-    sd, cfg = tiny_sd(), synth.CFG_TINY
+    branch cannot hide behind the (much larger) residual stream (helpers.check_block_stages)."""
     job = tiny_job()
     ids = job["input_ids"].repeat(B, 1)
     if B > 1:
         ids[1, :8] = torch.arange(100, 108)
-    L = ids.shape[1]
-    H, Hkv, hd, eps = cfg["n_heads"], cfg["n_kv_heads"], 128, cfg["rms_norm_eps"]
-    w = lo.layer_weights(sd, 0)
-    x0 = F.embedding(ids, sd["model.transformer.wte.weight"])
-    xn = lo.rms_norm(x0, w["attn_norm"], eps)
-    q = F.linear(xn, w["q_proj"]).view(B, L, H, hd).transpose(1, 2)
-    k = F.linear(xn, w["k_proj"]).view(B, L, Hkv, hd).transpose(1, 2)
-    v = F.linear(xn, w["v_proj"]).view(B, L, Hkv, hd).transpose(1, 2)
-    sin, cos = lo.rope_tables(L, hd, cfg["rope_theta"])
-    q, k = lo.apply_rope(q, sin, cos), lo.apply_rope(k, sin, cos)
-    att = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).contiguous().view(B, L, H * hd)
-    x1 = x0 + F.linear(att, w["attn_out"])
-    n2 = lo.rms_norm(x1, w["ff_norm"], eps)
-    hmid = F.silu(F.linear(n2, w["ff_proj"])) * F.linear(n2, w["up_proj"])
-    x2 = x1 + F.linear(hmid, w["ff_out"])
-
-    lib, h = tiny_model._lib, tiny_model._handle
-    ids_d = ids.to(DEV)
-    tiny_model._ensure_ws(B, L)
-    tiny_model._shape = (B, L)
-    st = abi.stream_ptr()
-    abi.check(lib.mmada_embed(h, ids_d.data_ptr(), B, L, st), "embed")
-    e_x0 = _relerr(tiny_model.hidden_state(), x0)
-    abi.check(lib.mmada_attn_partial(h, 0, st), "attn")
-    Lp = (L + 7) // 8 * 8
-    got = {
-        "xn": tiny_model.debug_buffer(0).view(B, Lp, -1)[:, :L],
-        "q": tiny_model.debug_buffer(1)[:, :, :L],
-        "k": tiny_model.debug_buffer(2)[:, :, :L],
-        "v": tiny_model.debug_buffer(3)[:, :, :, :L].transpose(2, 3),
-        "att": tiny_model.debug_buffer(4).view(B, Lp, -1)[:, :L],
-        "x1": tiny_model.hidden_state(),
-    }
-    got = {k_: v_.clone() for k_, v_ in got.items()}
-    abi.check(lib.mmada_mlp_partial(h, 0, st), "mlp")
-    got["n2"] = tiny_model.debug_buffer(0).view(B, Lp, -1)[:, :L].clone()
-    got["h"] = tiny_model.debug_buffer(5).view(B, Lp, -1)[:, :L].clone()
-    got["x2"] = tiny_model.hidden_state()
-    ref = {"xn": xn, "q": q, "k": k, "v": v, "att": att, "x1": x1, "n2": n2, "h": hmid, "x2": x2}
-    report = {"x0": e_x0}
-    for name in ref:
-        report[name] = _relerr(got[name], ref[name])
-    print("stage errors (max/maxabs, mean/meanabs):", {k_: (f"{a:.2e}", f"{b:.2e}") for k_, (a, b) in report.items()})
-    assert report["x0"][0] == 0.0
-    # the branch deltas, not just the stream: attention and MLP contributions themselves
-    report["d_attn"] = _relerr(got["x1"].float().cpu() - x0.float(), x1.float() - x0.float())
-    report["d_mlp"] = _relerr(got["x2"].float().cpu() - got["x1"].float().cpu(), x2.float() - x1.float())
-    print("branch deltas:", report["d_attn"], report["d_mlp"])
-    for name, (emax, emean) in report.items():
-        # bf16 storage everywhere: a few ulps (2^-8) of the tensor's magnitude; deltas are differences of bf16 values
-        lim_max, lim_mean = (0.25, 0.05) if name.startswith("d_") else (2.0 ** -5, 2.0 ** -8)
-        assert emax < lim_max and emean < lim_mean, f"{name}: {emax:.3e} {emean:.3e}"
+    check_block_stages(tiny_model, synth.CFG_TINY, tiny_sd(), ids)
 
 
 def test_forward_hidden_and_logits_vs_oracle_and_reference(tiny_model):
