@@ -486,3 +486,198 @@ def vt_unpermute(t):
     """[..., Lkv] in vt_key_pos storage order -> key order."""
     idx = torch.tensor([vt_key_pos(l) for l in range(t.shape[-1])], device=t.device)
     return t[..., idx]
+
+
+# ---- the attention kernel: exact routing and a derived per-element bound (tests/test_gpu_attention.py, tests/test_attention_host.py) ----
+# (B, n_heads, n_kv_heads, L): the smallest shapes that reach each branch of csrc/attention.hip — one key, just under / exactly /
+# just over one 64-key tile, 3 and 4 key tiles (the vT ring of three wraps), a pair-major grid with a ragged last group, the
+# XCD grid with 6-7 groups per workgroup (late waves carry a group), 17-18 groups (3 early + 2 late per SIMD, a 1 + 3 split of
+# the DMA pieces) and 23-24 groups (3 + 3)
+ATT_SHAPES = [(1, 1, 1, 1), (1, 2, 2, 63), (1, 2, 1, 64), (2, 2, 2, 65), (1, 4, 2, 129), (1, 2, 2, 193), (3, 2, 1, 333), (8, 8, 2, 400),
+              (2, 32, 8, 1100), (2, 32, 8, 1530)]
+# the range the groups of 16 query rows per workgroup must stay in, under the launch plan, for the above to hold
+ATT_PLAN_GROUPS = {(1, 1, 1, 1): (1, 1), (8, 8, 2, 400): (6, 7), (2, 32, 8, 1100): (17, 18), (2, 32, 8, 1530): (23, 24)}
+ATT_KINDS = ("normal", "peaked", "spike", "negative", "ascending")
+ATT_U = 2.0 ** -8            # the unit of the bound: one bf16 ulp, relative
+ATT_E_CAP = 2.0 ** -11       # the inputs keep the fp32 score error below this (natural-log units)
+ATT_GAP = 64.0               # least lead of the matching key's score, log2 domain, in the one-hot construction
+ATT_CODE_SCALE = 8.0
+ATT_LOG2_SCALE = 1.4426950408889634 / 128 ** 0.5    # a dot product -> the kernel's log2-domain score
+
+
+def att_groups_per_workgroup(lib, B, H, L):
+    """(smallest, largest) number of 16-row query groups a workgroup of attn16_kernel carries under the library's launch plan."""
+    groups = (L + 15) // 16
+    chunks = lib.mmada_attention_plan(B * H, groups, L)
+    return groups // chunks, -(-groups // chunks)
+
+
+def att_code(L):
+    """[L, 128] code words of +-1: the bits of the key index (as many as L - 1 needs, at least one), the whole set repeated as
+    often as fits into 128 features, the remaining features 0.  Two indices differ in at least `repeats` features."""
+    nbits = max(1, (L - 1).bit_length())
+    rep = 128 // nbits
+    b = ((torch.arange(L)[:, None] >> torch.arange(nbits)) & 1).float() * 2.0 - 1.0
+    code = torch.zeros(L, 128)
+    code[:, :nbits * rep] = b.repeat(1, rep)
+    return code
+
+
+def att_random_finite_bf16(shape, g):
+    """Random finite bf16 values over many binades: random sign, random 7-bit mantissa, exponent 2^-20 ... 2^20 (no
+    zero — the kernel's +0 accumulator cannot return a -0 — and nothing whose sum over a row could overflow fp32)."""
+    sign = torch.randint(0, 2, shape, generator=g).float() * 2.0 - 1.0
+    man = 1.0 + torch.randint(0, 128, shape, generator=g).float() / 128.0
+    return (sign * man * torch.exp2(torch.randint(-20, 21, shape, generator=g).float())).to(torch.bfloat16)
+
+
+def att_onehot_inputs(B, H, Hkv, L, perm="random", seed=0):
+    """Inputs whose soft-max is exactly one-hot: k[b, g, j] = c * code(j) * s[b, g], q[b, h, i] = c * code(pi[b, h, i]) * s[b, h's kv
+    head] with a random sign vector s per (batch, kv head) — so the K of another head or batch does not match — and a permutation
+    pi per (batch, q head): 'random' (a fresh one each), 'identity' or 'reversal'.  v: att_random_finite_bf16.
+    Query i's score of key pi(i) is c^2 * (features used); any other key loses 2 c^2 per differing feature, at least
+    2 * 64 * repeats * log2(e) / sqrt(128) = 179 in the log2 domain at L <= 2048 (11 bits x 11 repeats), more at smaller L:
+    past ATT_GAP, and past 150, so exp2(-gap) — every other key's p, and the factor alpha that rescales what a row gathered
+    before its matching key arrived — is exactly 0 in fp32.  p of the matching key is 1, or 1 + a few 2^-24 |score| if the
+    compiler contracts s * scale - m into an fma; l and 1 / l then differ from 1 by that much and v * (1 / l) still rounds to v.
+    Returns q [B, H, L, 128], k, v [B, Hkv, L, 128] (bf16, CPU) and pi [B, H, L]."""
+    g = torch.Generator().manual_seed(1000003 * seed + 7919 * L + 31 * H + B)
+    code = att_code(L) * ATT_CODE_SCALE
+    if perm == "random":
+        pi = torch.stack([torch.randperm(L, generator=g) for _ in range(B * H)]).view(B, H, L)
+    else:
+        one = torch.arange(L) if perm == "identity" else torch.arange(L - 1, -1, -1)
+        pi = one.expand(B, H, L).contiguous()
+    s = torch.randint(0, 2, (B, Hkv, 1, 128), generator=g).float() * 2.0 - 1.0
+    k = (code * s).to(torch.bfloat16)
+    q = (code[pi] * s.repeat_interleave(H // Hkv, dim=1)).to(torch.bfloat16)
+    return q, k, att_random_finite_bf16((B, Hkv, L, 128), g), pi
+
+
+def att_onehot_gap(q, k, pi):
+    """The least lead, in the log2 domain, of the score of key pi(i) over every other key of query i (inf with a single key)."""
+    B, H, L, _ = q.shape
+    rep = H // k.shape[1]
+    gap = float("inf")
+    for b in range(B):
+        s = q[b].float() @ k[b].float().repeat_interleave(rep, dim=0).transpose(1, 2)      # integers below 2^24: exact
+        idx = pi[b].to(s.device)[..., None]
+        match = s.gather(2, idx)
+        if L > 1:
+            gap = min(gap, float((match - s.scatter(2, idx, float("-inf")).amax(2, keepdim=True)).min()) * ATT_LOG2_SCALE)
+    return gap
+
+
+def att_onehot_expected(v, pi):
+    """What the one-hot construction must return, in the kernel's output layout [B, L, H * 128]: v[b, h's kv head, pi[b, h, i]]."""
+    B, H, L = pi.shape
+    ve = v.repeat_interleave(H // v.shape[1], dim=1)
+    return ve.gather(2, pi.to(v.device)[..., None].expand(B, H, L, 128)).transpose(1, 2).reshape(B, L, H * 128)
+
+
+def att_counting_inputs(B, H, Hkv, L, seed=0):
+    """q = 0: every score is 0, every p exactly 1, l = L; v holds integers of [-8, 8], so the numerator is exact in fp32 in any
+    order.  k is random (it must not matter)."""
+    g = torch.Generator().manual_seed(1000003 * seed + 7919 * L + 31 * H + B + 1)
+    k = torch.randn(B, Hkv, L, 128, generator=g).to(torch.bfloat16)
+    v = torch.randint(-8, 9, (B, Hkv, L, 128), generator=g).to(torch.bfloat16)
+    return torch.zeros(B, H, L, 128, dtype=torch.bfloat16), k, v
+
+
+def bf16_nearest(x):
+    """fp64 -> the nearest bf16 value (ties to even), kept in fp64; for 0 and magnitudes in bf16's normal range.  Integer
+    arithmetic on the bit pattern (45 of the 52 mantissa bits go), so the CPU and the device give the same answer."""
+    i = x.contiguous().view(torch.int64)
+    i = (i + ((1 << 44) - 1) + ((i >> 45) & 1)) & ~((1 << 45) - 1)
+    return i.view(torch.float64)
+
+
+def att_counting_exact(v, H):
+    """sum_j v[j] / L in fp64 (one rounding, of the quotient), [B, 1, H * 128]: every query row of a sequence gets the same."""
+    B, Hkv, L, _ = v.shape
+    return (v.double().sum(2) / L).repeat_interleave(H // Hkv, dim=1).view(B, 1, H * 128)
+
+
+def att_counting_verdict(got, v, H):
+    """The number of elements of got [B, L, H * 128] that are NOT the bf16 rounding of some number within relative 2^-21 of the exact
+    sum_j v[j] / L (the kernel's only inexact steps are the reciprocal of l = L and one product: 2^-23 + 2^-24 with a one-ulp
+    reciprocal): got must equal bf16(exact), or bf16 of either end of that interval where exact lies that close to a boundary."""
+    exact = att_counting_exact(v, H)
+    g = got.double()
+    ok = (g == bf16_nearest(exact)) | (g == bf16_nearest(exact * (1.0 - 2.0 ** -21))) | (g == bf16_nearest(exact * (1.0 + 2.0 ** -21)))
+    return int((~ok).sum())
+
+
+def att_general_inputs(kind, B, H, Hkv, L, seed=0, device="cpu"):
+    """q [B, H, L, 128], k, v [B, Hkv, L, 128] (bf16, on `device`) for condition C:
+    'normal'    q, k, v ~ N(0, 1): a diffuse soft-max;
+    'peaked'    q scaled by 3: single keys carry a row;
+    'spike'     k[b, g, L // 2] scaled by 6: the running maximum jumps mid-sequence (the rescale branch);
+    'negative'  q + 2, k - 2: every real score is near -45, a zero pad key (score 0) would own the row;
+    'ascending' kv head 0 and its query heads: k[j] = 3 j / (L - 1) + N(0, 1/16), q = 1 + N(0, 1/100) — the score climbs by 49 in the
+                log2 domain from the first key to the last, so the maximum rises on every tile; the other heads as 'normal'.
+    E <= ATT_E_CAP asks for max_ij sum_f |q_if| |k_jf| <= 2^6 sqrt(128) = 724.  'spike' and 'negative' come within a few per cent
+    of that at the largest shapes (the largest of 10^8 such sums), on either side of it depending on the draw: where the
+    largest sum exceeds 0.98 of the cap, q as a whole is scaled down to put it there (the most for 'spike' at L = 1100: by 0.945)."""
+    g = torch.Generator().manual_seed(1000003 * seed + 7919 * L + 31 * H + B + 2 + ATT_KINDS.index(kind))
+    q = torch.randn(B, H, L, 128, generator=g)
+    k = torch.randn(B, Hkv, L, 128, generator=g)
+    v = torch.randn(B, Hkv, L, 128, generator=g)
+    if kind == "peaked":
+        q *= 3.0
+    elif kind == "spike":
+        k[:, :, L // 2] *= 6.0
+    elif kind == "negative":
+        q += 2.0
+        k -= 2.0
+    elif kind == "ascending":
+        ramp = 3.0 * torch.arange(L).float() / max(L - 1, 1)
+        k[:, 0] = 0.25 * k[:, 0] + ramp[:, None]
+        q[:, :H // Hkv] = 0.1 * q[:, :H // Hkv] + 1.0
+    q, k, v = q.to(device), k.to(device), v.to(device)
+    worst = max(float((q[b].abs() @ k[b].abs().repeat_interleave(H // Hkv, dim=0).transpose(1, 2)).max()) for b in range(B))
+    cap = 0.98 * ATT_E_CAP * 2.0 ** 17 * 128 ** 0.5          # 0.98: rounding q and k to bf16 may add 2^-8 of the sum
+    if worst > cap:
+        q *= cap / worst
+    return q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16)
+
+
+def att_reference(q, k, v):
+    """fp64 soft-max attention of the bf16 inputs q [B, H, Lq, 128], k, v [B, Hkv, Lk, 128], on their device, one kv head at a time.
+    Returns, in the kernel's output layout [B, Lq, H * 128] (fp64): ref = P V, A = P |V| and E, the row's worst-case fp32 score
+    error in natural-log units (att_general_verdict)."""
+    B, H, Lq, _ = q.shape
+    Hkv = k.shape[1]
+    rep = H // Hkv
+    ref = torch.empty(B, H, Lq, 128, dtype=torch.float64, device=q.device)
+    A, E = torch.empty_like(ref), torch.empty_like(ref)
+    for b in range(B):
+        for g in range(Hkv):
+            qd, kd, vd = q[b, g * rep:(g + 1) * rep].double(), k[b, g].double(), v[b, g].double()
+            p = torch.softmax(qd @ kd.t() / 128 ** 0.5, dim=-1)
+            ref[b, g * rep:(g + 1) * rep] = p @ vd
+            A[b, g * rep:(g + 1) * rep] = p @ vd.abs()
+            E[b, g * rep:(g + 1) * rep] = 2.0 ** -17 / 128 ** 0.5 * (qd.abs() @ kd.abs().t()).amax(-1, keepdim=True)
+    return tuple(t.transpose(1, 2).reshape(B, Lq, H * 128) for t in (ref, A, E))
+
+
+def att_general_verdict(got, ref, A, E):
+    """max over the elements of |got - ref| / bound (at most 1 passes; a NaN gives inf), bound = u A + u |ref| + 2 E (A + |ref|).
+
+    The kernel computes out = bf16(sum_j bf16(p_j) v_j / sum_j p_j) with p_j = exp2(fl(s_j) * scale - m) and everything but the two
+    roundings named in fp32; ref = sum_j P_j v_j with the exact weights P.
+      * Rounding p_j to bf16 moves it by at most 2^-9 p_j (round to nearest, 8 significant bits), the numerator by 2^-9 sum_j p_j
+        |v_j| and the output by 2^-9 A; rounding the result moves it by 2^-9 |out|.  The bound allows u = 2^-8 for each, twice
+        that: the other half covers every fp32 step that is not in E — the P V and l accumulations (at most (Lk + 4) 2^-24 <
+        2^-12 relative to A and |ref| at Lk < 4092), the product with the scale, exp2 (2^-22) and the reciprocal.
+      * The deferred maximum subtracts an m up to DEFER_LOG2 = 4 below the row's maximum, the same for every key of the row:
+        p and l grow by a common factor of at most 2^4 before the rounding, relative errors are unchanged.
+      * fl(s_j), the MFMA's fp32 accumulation of 128 exact products, is off by at most 127 * 2^-24 * sum_f |q_f| |k_jf| < 2^-17
+        sum_f |q_f| |k_jf|; in natural-log units (divided by sqrt(128)) that is at most E for every key of the row, E = 2^-17
+        max_j (sum_f |q_f| |k_jf|) / sqrt(128).  Each p_j is then off by a factor within exp(+-E): the numerator moves by (e^E -
+        1) A, the denominator's relative change moves the quotient by (e^E - 1) |ref|; with E <= 2^-11 e^E - 1 < 1.001 E, and
+        the bound's 2 E (A + |ref|) allows twice the sum."""
+    r = ref.abs()
+    bound = (ATT_U + 2.0 * E) * (A + r)
+    ratio = (got.double() - ref).abs() / bound.clamp_min(1e-300)
+    return float(torch.nan_to_num(ratio, nan=float("inf")).max())
