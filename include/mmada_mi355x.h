@@ -156,6 +156,38 @@ int mmada_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, 
  * the value of +0.0). */
 unsigned mmada_topk_order_key(unsigned bf16_bits);
 
+/* Sample: one token per row from softmax(logits[rows[r], col_begin:col_end] / temperature) with its log-probability, again WITHOUT
+ * materialising the logits or a noise tensor: a Gumbel-max draw in the epilogue of the head GEMM of mmada_head_logprobs.
+ *   ids_out[r] = argmax_c key(r, c),   key = fadd_rn(x, fmul_rn(temperature, g(seed, *counter, r, c)))
+ * x: the bf16 logit (what mmada_head_rows stores) as fp32; r: the row's index inside the call; c: the column in the WHOLE
+ * vocabulary; g = -log(-log(u)) in fp32, u = (2 * (word >> 9) + 1) * 2^-24, word = word (c & 3) of Philox4x32-10 on the counter
+ * block (c >> 2, r, counter low, counter high) with the key (seed low, seed high).  The draw is a pure function of (logits, seed,
+ * counter, r, c): the GEMM configuration and the column range do not show in it (a draw on a sub-range is the arg-max of the same
+ * keys restricted to the range).  The highest key wins, the lowest column on equal keys; temperature is finite and >= 0 (anything
+ * else is an error: an infinite one would turn g = 0 into a NaN key), and at 0 the draw is
+ * the argmax_out of mmada_head_logprobs.  NaN logits: outside the contract.
+ * counter: device uint64 [1], read by the launch and incremented by 1 by its last kernel, so consecutive calls — and replays
+ * of a captured call — draw fresh noise; the caller resets it to repeat a draw.
+ * logprob_out: device fp32 [R] = x_drawn - lse, the UNPERTURBED log-probability of the drawn column: bit for bit the logprob_out
+ * of mmada_head_logprobs(rows, targets = ids_out).  lse_out, argmax_out, max_out: device [R] or NULL, bit for bit those of
+ * mmada_head_logprobs on the same rows and range.  Preconditions and errors of mmada_head_topk (a forward resident, the same
+ * range and row-window rules).
+ * Record buffer: the handle's (mmada_score_buffer_bytes), ceil(N / 256) * ceil8(R) * 32 + ceil8(R) * 4 bytes — 1/16 of the bf16
+ * logits the call stands for; the call synchronises the host only when the buffer must grow, and a call that fits is capturable.
+ * One rank only: a handle with a tensor-parallel exchange connected (also a one-rank group) or tp_size != 1 is an error; the
+ * vocabulary-parallel form is a follow-up. */
+int mmada_head_sample(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, float temperature, uint64_t seed,
+                      uint64_t* counter, int32_t* ids_out, float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out,
+                      void* stream);
+/* The word above, and the map from a word to u, on the host (no device is touched; the code the kernels compile). */
+uint32_t mmada_sample_word(uint64_t seed, uint64_t counter, uint32_t row, uint32_t col);
+float mmada_sample_uniform(uint32_t word);
+/* Tests only: the device's words and Gumbel values elementwise.  words_out / g_out: device [R, N] or NULL (not both); element
+ * (r, c) is that of row row0 + r and column col0 + c.  row0 == -1, the enumeration mode: no generator runs; element i of the flat
+ * [R * N] output takes the word (col0 + i) << 9, so col0 = 0 and R * N = 2^23 enumerate every value of u in ascending order. */
+int mmada_probe_gumbel(uint64_t seed, uint64_t counter, int row0, int R, int col0, int N, uint32_t* words_out, float* g_out,
+                       void* stream);
+
 /* Declare which residual-stream rows the caller will read after the forwards that follow: only l in
  * [row_begin, row_end) of every sequence (e.g. the image + text span of generate_ti2ti; the prompt and the input image
  * are never decoded).  The LAST block then runs attention queries, attn_out and the MLP on those rows only — every
@@ -238,6 +270,16 @@ int mmada_text_select(mmada_handle* h, const void* logits, const void* noisy, in
 int mmada_text_select_random(mmada_handle* h, const void* logits, const void* noisy, const float* uniform, int B, int T,
                              int V, int ld_logits, int64_t* ids, int L, int text_start, const int32_t* k, void* scratch,
                              void* stream);
+
+/* The same step (low_confidence remasking) with the draw of mmada_head_sample instead of torch's noise, from the resident forward:
+ * neither the [B*T, V] logits nor a noise tensor exists.  rows: device int32 [B*T], rows[b*T + t] = b*L + text_start + t.
+ *   x0 = mmada_head_sample over the whole vocabulary (row index inside the call: b*T + t); conf = masked ? logprob(x0) : -inf —
+ *   ranking by the log-probability is ranking by the probability; the k[b] highest-confidence masked positions of row b get
+ *   ids[b, text_start + t] = x0 (confidence descending, then position ascending).
+ * The draws differ from torch's RNG stream by construction.  *counter advances by 1 per call.  One rank only, as mmada_head_sample.
+ * scratch: device, >= B*T*16 bytes. */
+int mmada_text_select_sampled(mmada_handle* h, const int32_t* rows, int B, int T, float temperature, uint64_t seed, uint64_t* counter,
+                              int64_t* ids, int L, int text_start, const int32_t* k, void* scratch, void* stream);
 
 /* Image step part 1, generators/parallel_generator.py:282-295,311: dual-CFG combine with the reference's per-op
  * bf16 rounding, softmax → bf16 probabilities, first-index argmax, probability of the argmax.

@@ -44,6 +44,13 @@ SIGNATURES = {
     "mmada_score_buffer_bytes": (c_size_t, [c_void_p]),
     "mmada_head_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mmada_topk_order_key": (C.c_uint, [C.c_uint]),
+    "mmada_head_sample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, C.c_uint64, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mmada_text_select_sampled": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, C.c_uint64, c_void_p, c_void_p, c_int, c_int,
+                                          c_void_p, c_void_p, c_void_p]),
+    "mmada_sample_word": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "mmada_sample_uniform": (c_float, [C.c_uint32]),
+    "mmada_probe_gumbel": (c_int, [C.c_uint64, C.c_uint64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mmada_cache_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "mmada_cache_bind": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "mmada_forward_cached": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -151,7 +151,7 @@ __global__ __launch_bounds__(NTHREADS, 4) void gemm_bt_kernel(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < T::FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     mainloop<BM, WM, WN>(g, smem, mt * BM, nt * BN, 0, g.K / BK, acc, wave, lane);
-    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK) {
+    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK || EPI == EPI_ROWSAMPLE) {
         static_assert(T::LDS_BYTES >= RowTopkLds::BYTES, "the row records reuse the stage buffers");
         __syncthreads();   // every wave has read its last K-tile: the stage buffers are free for the row records
         gemm_epilogue<EPI, T::TM, T::TN, WN>(g, mt * BM, nt * BN, acc, wave, lane, g.M, (int)(uintptr_t)(lptr_t)smem, BM);
@@ -231,8 +231,8 @@ Plan plan(const GemmArgs& g, int force) {
 template <int EPI>
 int launch_t(const GemmArgs& g, const Switches& sw, hipStream_t s) {
     Plan p = plan(g, sw.gemm_config);
-    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK) {
-        // the row-statistics epilogue (and its top-k form) exists for 256-column tiles of four 64-column waves: a pinned configuration without one
+    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK || EPI == EPI_ROWSAMPLE) {
+        // the row-statistics epilogue (and its top-k and sampling forms) exists for 256-column tiles of four 64-column waves: a pinned configuration without one
         // (320 x 128; the 16-wave kernel's 2 x 8 wave grids) gets the automatic pick, and that the next taller 4 x 4 grid
         if (p.p8 && p.code == GEMM8_320x128) p = plan(g, -1);
         if (p.p8 && p.code == GEMM8_320x128) p = {true, GEMM8_320x256};
@@ -353,6 +353,12 @@ int launch_gemm(int epi, const GemmArgs& g_in, hipStream_t s) {
             if (const RowTopkArgs tk = rowtopk_args(g); !tk.rs.part || !tk.rs.tx || !tk.topk || tk.rs.rows <= 0 || tk.rs.rows > g.M || tk.rs.ld < tk.rs.rows)
                 return mm_fail("gemm/rowtopk: record buffers missing");
             return launch_t<EPI_ROWTOPK>(g, sw, s);
+        case EPI_ROWSAMPLE:
+            if (const RowSampleArgs sa = rowsample_args(g); !sa.rs.part || !sa.rs.tx || !sa.samp || !sa.counter || sa.rs.rows <= 0 ||
+                                                            sa.rs.rows > g.M || sa.rs.ld < sa.rs.rows || !(sa.temperature >= 0.f) ||
+                                                            __builtin_isinf(sa.temperature))
+                return mm_fail("gemm/rowsample: record buffers or counter missing, or a temperature that is not finite and >= 0");
+            return launch_t<EPI_ROWSAMPLE>(g, sw, s);
     }
     return mm_fail("gemm: bad epilogue %d", epi);
 }
@@ -480,6 +486,68 @@ int launch_head_rowtopk(const bf16_t* A, const bf16_t* W, int R, int N, int K, i
     if (launch_gemm(EPI_ROWTOPK, g, s)) return 1;
     hipLaunchKernelGGL(rowtopk_combine_kernel, dim3((R + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, tk.rs.part, tk.topk,
                        R, rp, ntn, col0, k, ids, logits, lse, tk.rs.tx);
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the sampling head: the same launch with EPI_ROWSAMPLE (gemm_epilogue.h), which also leaves every tile's best key ---------
+// Record buffer: the row-statistics records and ceil8(R) floats as above, then [ceil(N / 256)][ceil8(R)] key records of 16 bytes:
+// 1/16 of the bytes of the bf16 logits it stands for, plus 4 bytes per row.
+size_t head_rowsample_bytes(int R, int N) {
+    const size_t rp = (size_t)((R + 7) / 8 * 8);
+    return head_rowstat_bytes(R, N) + rp * rowstat_tiles(N) * sizeof(float4);
+}
+
+// Thread (row, group j) walks the key records of tiles j, j + 16, ... in ascending order (a later equal key lies further right and
+// does not replace); thread (row, 0) folds the 16 groups through LDS, where the groups interleave the tiles and the lowest column
+// wins on equal keys.  The order of keys is total (key, then column), so neither the GEMM's tile order nor its configuration shows.
+// lse / argmax / max: the fold and the expression of rowstat_combine_kernel on the same records, with the drawn column's logit as
+// the target logit: logprob = x_drawn - lse.  The kernel is the last of the call: every workgroup of the GEMM has read *counter.
+__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void rowsample_combine_kernel(const float4* part, const float4* samp, int R, int ld, int ntn,
+                                                                                 int32_t* ids, float* logprob, float* lse_out, int32_t* argmax_out,
+                                                                                 float* max_out, uint64_t* counter) {
+    __shared__ float sk[RS_GROUPS][RS_ROWS], sx[RS_GROUPS][RS_ROWS];
+    __shared__ int sc[RS_GROUPS][RS_ROWS];
+    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
+    const int row = blockIdx.x * RS_ROWS + rl;
+    float bk = -__builtin_inff(), bx = -__builtin_inff();
+    int bc = 0x7fffffff;
+    if (row < R)
+        for (int t = j; t < ntn; t += RS_GROUPS) {
+            const float4 p = samp[(size_t)t * ld + row];
+            gemm_detail::rowsample_take(bk, bc, bx, p.x, __float_as_int(p.y), p.z);
+        }
+    sk[j][rl] = bk; sc[j][rl] = bc; sx[j][rl] = bx;
+    float m, sum;
+    int arg;
+    // (its barrier also orders the key triples above)
+    const bool mine = rowstat_fold([&](int t, int r) { return part[(size_t)t * ld + r]; }, row, R, ntn, m, sum, arg);
+    if (mine) {
+        for (int q = 1; q < RS_GROUPS; ++q) gemm_detail::rowsample_take(bk, bc, bx, sk[q][rl], sc[q][rl], sx[q][rl]);
+        ids[row] = bc;
+        rowstat_finish(row, m, sum, arg, bc, bx, logprob, lse_out, argmax_out, max_out);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *counter += 1;
+}
+
+int launch_head_rowsample(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, float temperature, uint64_t seed,
+                          uint64_t* counter, void* part, int32_t* ids, float* logprob, float* lse, int32_t* argmax, float* vmax,
+                          hipStream_t s) {
+    if (R <= 0 || N <= 0) return 0;
+    if (!(temperature >= 0.f) || __builtin_isinf(temperature))
+        return mm_fail("head sample: temperature %g is not a finite value >= 0", (double)temperature);
+    const int rp = (R + 7) / 8 * 8, ntn = rowstat_tiles(N);
+    GemmArgs g = gemm_bt_args(A, W, nullptr, rp, N, K, 8);
+    RowSampleArgs sa;
+    sa.rs = RowStatArgs{(float4*)part, (float*)((float4*)part + (size_t)rp * ntn), nullptr, R, rp, col0};
+    sa.samp = (float4*)(sa.rs.tx + rp);
+    sa.counter = counter;
+    sa.seed = seed;
+    sa.temperature = temperature;
+    set_rowsample_args(g, sa);
+    if (launch_gemm(EPI_ROWSAMPLE, g, s)) return 1;
+    hipLaunchKernelGGL(rowsample_combine_kernel, dim3((R + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, sa.rs.part, sa.samp, R,
+                       rp, ntn, ids, logprob, lse, argmax, vmax, counter);
     MM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -446,7 +446,7 @@ int launch_cfg8(const GemmArgs& g, const Switches& sw, hipStream_t s) {
 template <int EPI>
 int launch_epi8(int cfg, const GemmArgs& g, const Switches& sw, hipStream_t s) {
     constexpr int SW = EPI == EPI_QKV ? 2 : 1;
-    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK) {   // 256-column tiles only (gemm_epilogue.h: one record per row and 256 columns)
+    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK || EPI == EPI_ROWSAMPLE) {   // 256-column tiles only (gemm_epilogue.h: one record per row and 256 columns)
         switch (cfg) {
             case GEMM8_320x256: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 2>>(g, sw, s);
             case GEMM8_256x256: return launch_cfg8<EPI, Gemm8<256, 256, 2, 4, SW, 2>>(g, sw, s);
@@ -500,6 +500,7 @@ int launch_gemm8(int epi, int cfg, const GemmArgs& g, const Switches& sw, hipStr
         case EPI_QKV: return launch_epi8<EPI_QKV>(cfg, g, sw, s);
         case EPI_ROWSTAT: return launch_epi8<EPI_ROWSTAT>(cfg, g, sw, s);
         case EPI_ROWTOPK: return launch_epi8<EPI_ROWTOPK>(cfg, g, sw, s);
+        case EPI_ROWSAMPLE: return launch_epi8<EPI_ROWSAMPLE>(cfg, g, sw, s);
     }
     return mm_fail("gemm8: bad epilogue %d", epi);
 }

@@ -5,6 +5,7 @@
 // anything else touches it (model/modeling_llada.py:925-927, 741-744, 962-970).
 #pragma once
 #include "kernels.h"
+#include "sample_noise.h"
 
 namespace gemm_detail {
 
@@ -117,6 +118,23 @@ MM_DEVICE void lds_st128(int byte_off, u32x4 v) { *(lds_u32x4_ptr)(uint32_t)byte
 #pragma clang diagnostic pop
 MM_DEVICE uint32_t umax32(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
+// ---- EPI_ROWSAMPLE: EPI_ROWSTAT plus a Gumbel-max draw per row (kernels.h: RowSampleArgs; sample_noise.h: the noise).  The same
+// three steps:
+//   1. also, per slot: key = x + T * g of the lane's values, the lane's best {key, column, x} (the first column on equal keys),
+//      then the best of the lanes that share the row (__shfl_xor, as for the maximum).  In the transposed layout a lane's four
+//      consecutive columns cost one Philox evaluation (two when the launch's first column is no multiple of 4), in the other
+//      layout every value costs one.  The writer lane stores the wave column's triple behind the RowStatLds arrays;
+//   3. the thread that joins tile row r takes the best of the four wave columns (they ascend: a later equal key does not replace)
+//      and writes the second 16-byte record.
+struct RowSampleLds {
+    static constexpr int N1 = RowStatLds::ROWS * RowStatLds::WAVES * 4;
+    static constexpr int KEY = RowStatLds::BYTES, COL = KEY + N1, X = COL + N1, BYTES = X + N1;
+};
+static_assert(RowSampleLds::BYTES <= RowTopkLds::BYTES, "the sampling head fits the LDS the top-k head reserves");
+MM_DEVICE void rowsample_take(float& k, int& c, float& x, float ok, int oc, float ox) {   // highest key, then lowest column
+    if (ok > k || (ok == k && oc < c)) { k = ok; c = oc; x = ox; }
+}
+
 MM_DEVICE void rowstat_take(float& m, int& a, float om, int oa) {   // torch's arg-max tie rule: the first index wins
     if (om > m || (om == m && oa < a)) { m = om; a = oa; }
 }
@@ -131,8 +149,8 @@ MM_DEVICE int rowstat_target(const GemmArgs& g, const RowStatArgs& rs, int m) {
 }
 
 // TR: transposed accumulator layout (gemm_epilogue_t) or not (gemm_epilogue); lds: byte address of RowStatLds::BYTES free bytes
-// (TOPK, the EPI_ROWTOPK form: RowTopkLds::BYTES)
-template <bool TR, int TM, int TN, int WN, bool TOPK = false>
+// (TOPK, the EPI_ROWTOPK form: RowTopkLds::BYTES; SAMPLE, the EPI_ROWSAMPLE form: RowSampleLds::BYTES)
+template <bool TR, int TM, int TN, int WN, bool TOPK = false, bool SAMPLE = false>
 MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim, int lds,
                                  int bm /* rows of the workgroup's tile, <= RowStatLds::ROWS */) {
 #pragma clang fp contract(off)
@@ -148,11 +166,45 @@ MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[
     // else FM * 4 (row mi*16 + lq*4 + r, 4 values: column l15 of 4 fragments)
     constexpr int NS = TR ? FM : FM * 4;
     const bool writer = TR ? lq == 0 : l15 == 0;
+    RowSampleArgs sa{};
+    uint64_t ctr = 0;
+    if constexpr (SAMPLE) {
+        sa = rowsample_args(g);
+        ctr = *sa.counter;   // the same address in every lane: one scalar load per wave
+    }
+    // SAMPLE in the untransposed layout (the 16-wave kernel: 128 VGPRs per lane): the logits are needed as bf16 values only, so
+    // they are rounded once and kept two to a register — 40 registers instead of 80 at 320 rows — which is what lets the draw's
+    // Philox state and logarithms fit beside them without scratch.  Unpacking a value is one shift or mask, exact.
+    constexpr bool PACKED = SAMPLE && !TR;
+    uint32_t pk[PACKED ? FM : 1][PACKED ? FN : 1][2];
+    if constexpr (PACKED) {
+#pragma unroll
+        for (int mi = 0; mi < FM; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < FN; ++ni) {
+                pk[mi][ni][0] = pack_bf2(acc[mi][ni][0], acc[mi][ni][1]);
+                pk[mi][ni][1] = pack_bf2(acc[mi][ni][2], acc[mi][ni][3]);
+            }
+    }
+    // between two steps: the unpacked values of one step are not kept in registers for the next (the compiler would otherwise
+    // reuse them — all 80 again); every step unpacks what it needs, when it needs it
+    auto repack = [&]() {
+        if constexpr (PACKED) {
+#pragma unroll
+            for (int mi = 0; mi < FM; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < FN; ++ni) asm volatile("" : "+v"(pk[mi][ni][0]), "+v"(pk[mi][ni][1]));
+        }
+    };
+    repack();   // ... and the packing itself happens HERE, not where a value is first used (the fp32 accumulators die now)
     auto slot_row = [&](int sl) { return TR ? wm * TM + sl * 16 + l15 : wm * TM + (sl >> 2) * 16 + lq * 4 + (sl & 3); };
     auto val = [&](int sl, int ni, int r) {   // bf16-rounded logit; columns beyond N never win and add nothing
         const int n = wcol0 + ni * 16 + (TR ? lq * 4 + r : l15);
         float a;
-        if constexpr (TR) a = acc[sl][ni][r];
+        if constexpr (PACKED) {
+            const uint32_t p = pk[sl >> 2][ni][(sl & 3) >> 1];
+            return n < g.N ? __uint_as_float((sl & 1) ? p & 0xffff0000u : p << 16) : NEG;
+        } else if constexpr (TR) a = acc[sl][ni][r];
         else a = acc[sl >> 2][ni][sl & 3];
         return n < g.N ? bfround(a) : NEG;
     };
@@ -161,7 +213,8 @@ MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[
     for (int sl = 0; sl < NS; ++sl) {
         const int rt = slot_row(sl), m = m0 + rt;
         int tc;
-        if constexpr (TOPK) tc = m < rows && rs.target ? rowstat_target(g, rs, m) : -1;
+        if constexpr (SAMPLE) tc = -1;
+        else if constexpr (TOPK) tc = m < rows && rs.target ? rowstat_target(g, rs, m) : -1;
         else tc = m < rows ? rowstat_target(g, rs, m) : -1;
         const int c0 = wcol0 + (TR ? lq * 4 : l15);
         float bm = NEG;
@@ -229,7 +282,54 @@ MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[
                 lds_st128(at + 16, u32x4{win[4], win[5], win[6], win[7]});
             }
         }
+        if constexpr (SAMPLE) {
+            const uint32_t gc0 = (uint32_t)(rs.col0 + c0);     // column in the whole vocabulary of the lane's first value
+            const uint32_t sh = (uint32_t)rs.col0 & 3u;        // wave-uniform: c0 is a multiple of 4 in the transposed layout
+            float bk = NEG, bx = NEG;
+            int bc = c0;
+#pragma unroll
+            for (int ni = 0; ni < FN; ++ni) {
+                const uint32_t gc = gc0 + ni * 16;
+                uint32_t w0, w1 = 0u, w2 = 0u, w3 = 0u;
+                if constexpr (TR) {
+                    sample_words4(sa.seed, ctr, (uint32_t)m, gc >> 2, w0, w1, w2, w3);
+                    if (sh) {   // the lane's four columns straddle two blocks
+                        uint32_t q0, q1, q2, q3;
+                        sample_words4(sa.seed, ctr, (uint32_t)m, (gc >> 2) + 1u, q0, q1, q2, q3);
+                        const uint32_t a1 = w1, a2 = w2, a3 = w3;    // the columns are words sh .. sh + 3 of the pair
+                        w0 = sh == 1u ? a1 : sh == 2u ? a2 : a3;
+                        w1 = sh == 1u ? a2 : sh == 2u ? a3 : q0;
+                        w2 = sh == 1u ? a3 : sh == 2u ? q0 : q1;
+                        w3 = sh == 1u ? q0 : sh == 2u ? q1 : q2;
+                    }
+                } else
+                    w0 = sample_word(sa.seed, ctr, (uint32_t)m, gc);
+#pragma unroll
+                for (int r = 0; r < (TR ? 4 : 1); ++r) {
+                    const float x = val(sl, ni, r);
+                    const int n = wcol0 + ni * 16 + (TR ? lq * 4 + r : l15);
+                    const uint32_t w = r == 0 ? w0 : r == 1 ? w1 : r == 2 ? w2 : w3;
+                    const float key = n < g.N ? sample_key(x, sa.temperature, sample_gumbel(w)) : NEG;
+                    if (key > bk) { bk = key; bc = c0 + ni * 16 + r; bx = x; }
+                }
+            }
+            if constexpr (TR) {
+                rowsample_take(bk, bc, bx, __shfl_xor(bk, 16, 64), __shfl_xor(bc, 16, 64), __shfl_xor(bx, 16, 64));
+                rowsample_take(bk, bc, bx, __shfl_xor(bk, 32, 64), __shfl_xor(bc, 32, 64), __shfl_xor(bx, 32, 64));
+            } else {
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1)
+                    rowsample_take(bk, bc, bx, __shfl_xor(bk, o, 64), __shfl_xor(bc, o, 64), __shfl_xor(bx, o, 64));
+            }
+            if (writer) {
+                const int at = (wn * RowStatLds::ROWS + rt) * 4;
+                lds_stf(lds + RowSampleLds::KEY + at, bk);
+                lds_sti(lds + RowSampleLds::COL + at, bc);
+                lds_stf(lds + RowSampleLds::X + at, bx);
+            }
+        }
     }
+    repack();
     __syncthreads();
     // ---- 2: sums of exponentials against the tile's row max ----
 #pragma unroll
@@ -304,6 +404,17 @@ MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[
             dst[0] = u32x4{best[0], best[1], best[2], best[3]};
             dst[1] = u32x4{best[4], best[5], best[6], best[7]};
         }
+        if constexpr (SAMPLE) {
+            float bk = lds_ldf(lds + RowSampleLds::KEY + rt * 4), bx = lds_ldf(lds + RowSampleLds::X + rt * 4);
+            int bc = lds_ldi(lds + RowSampleLds::COL + rt * 4);
+#pragma unroll
+            for (int w = 1; w < WN; ++w) {
+                const int at = (w * RowStatLds::ROWS + rt) * 4;
+                const float ok = lds_ldf(lds + RowSampleLds::KEY + at);
+                if (ok > bk) { bk = ok; bc = lds_ldi(lds + RowSampleLds::COL + at); bx = lds_ldf(lds + RowSampleLds::X + at); }
+            }
+            sa.samp[(size_t)(n0 / (TN * WN)) * rs.ld + m] = float4{bk, __int_as_float(bc + rs.col0), bx, 0.f};
+        }
     }
 }
 
@@ -312,13 +423,17 @@ MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[
 //     acc[mi][ni][r] = D[m][n],  m = m0 + wm*TM + mi*16 + (lane>>4)*4 + r,  n = n0 + wn*TN + ni*16 + (lane&15)
 template <int EPI, int TM, int TN, int WN>
 MM_DEVICE void gemm_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim,
-                             int lds = 0, int bm = 0 /* EPI_ROWSTAT, EPI_ROWTOPK: free LDS (byte address), rows of the tile */) {
+                             int lds = 0, int bm = 0 /* EPI_ROWSTAT, EPI_ROWTOPK, EPI_ROWSAMPLE: free LDS (byte address), rows of the tile */) {
     if constexpr (EPI == EPI_ROWSTAT) {
         if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<false, TM, TN, WN>(g, m0, n0, acc, wave, lane, m_lim, lds, bm);
         return;
     }
     if constexpr (EPI == EPI_ROWTOPK) {
         if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<false, TM, TN, WN, true>(g, m0, n0, acc, wave, lane, m_lim, lds, bm);
+        return;
+    }
+    if constexpr (EPI == EPI_ROWSAMPLE) {
+        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<false, TM, TN, WN, false, true>(g, m0, n0, acc, wave, lane, m_lim, lds, bm);
         return;
     }
     constexpr int FM = TM / 16, FN = TN / 16;
@@ -487,6 +602,10 @@ MM_DEVICE void gemm_epilogue_t(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[T
     }
     if constexpr (EPI == EPI_ROWTOPK) {
         if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<true, TM, TN, WN, true>(g, m0, n0, acc, wave, lane, m_lim, 0, TM * (8 / WN));
+        return;
+    }
+    if constexpr (EPI == EPI_ROWSAMPLE) {
+        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<true, TM, TN, WN, false, true>(g, m0, n0, acc, wave, lane, m_lim, 0, TM * (8 / WN));
         return;
     }
     constexpr int FM = TM / 16, FN = TN / 16;

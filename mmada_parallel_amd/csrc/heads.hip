@@ -1,7 +1,9 @@
 // heads.hip — the LM head on demand: logit rows of the resident forward (mmada_head_rows) or of a dLLM-cache slot
-// (mmada_cache_head_rows), the fused scoring head (mmada_head_logprobs) and its top-k form (mmada_head_topk).  Host code only.
+// (mmada_cache_head_rows), the fused scoring head (mmada_head_logprobs), its top-k form (mmada_head_topk) and its sampling form
+// (mmada_head_sample, mmada_text_select_sampled; the noise: sample_noise.h).  Host code only.
 #include "../../include/mmada_mi355x.h"
 #include "handle.h"
+#include "sample_noise.h"
 
 int check_head_range(const mmada_handle* h, const char* who, int R, int limit, int col_begin, int col_end) {
     if (R > limit) return mm_fail("%s: R=%d exceeds B*L=%d", who, R, limit);
@@ -24,7 +26,7 @@ static int store_logits(const mmada_handle* h, const bf16_t* xg, int R, int col_
     return launch_gemm(EPI_STORE, gemm_bt_args(xg, h->lm_head + (size_t)col_begin * d, (bf16_t*)out, R, N, d, N), s);
 }
 
-// the record buffer of mmada_head_logprobs / mmada_head_topk holds at least `need` bytes
+// the record buffer of mmada_head_logprobs / mmada_head_topk / mmada_head_sample holds at least `need` bytes
 static int grow_score_buffer(mmada_handle* h, size_t need, hipStream_t s) {
     if (need <= h->score_bytes) return 0;
     if (stream_capturing(s))
@@ -123,6 +125,54 @@ int mmada_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, 
 }
 
 unsigned mmada_topk_order_key(unsigned bf16_bits) { return topk_order(__builtin_bit_cast(float, (uint32_t)(bf16_bits & 0xffffu) << 16)) >> 16; }
+
+int mmada_head_sample(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, float temperature, uint64_t seed,
+                      uint64_t* counter, int32_t* ids_out, float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out,
+                      void* stream) {
+    if (!h || !resident(h)) return mm_fail("mmada_head_sample: no forward resident");
+    if (!rows || !counter || !ids_out || !logprob_out) return mm_fail("mmada_head_sample: null argument");
+    if (!(temperature >= 0.f) || __builtin_isinf(temperature))
+        return mm_fail("mmada_head_sample: temperature %g is not a finite value >= 0", (double)temperature);
+    if (runs_tensor_parallel(h) || h->res.xn_is_final)
+        return mm_fail("mmada_head_sample: the draw runs on one rank (a handle without a tensor-parallel exchange): the "
+                       "vocabulary-parallel draw, whose key records would ride the score exchange of mmada_head_logprobs, is a follow-up");
+    if (R <= 0) return 0;
+    if (check_head_range(h, "mmada_head_sample", R, h->res.B * h->res.L, col_begin, col_end)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    const int d = h->cfg.d_model, N = col_end - col_begin;
+    if (grow_score_buffer(h, head_rowsample_bytes(R, N), s)) return 1;
+    if (gather_resident_rows(h, rows, R, s)) return 1;
+    return launch_head_rowsample(h->xg, h->lm_head + (size_t)col_begin * d, R, N, d, col_begin, temperature, seed, counter, h->score_buf,
+                                 ids_out, logprob_out, lse_out, argmax_out, max_out, s);
+}
+
+// The text step with the draw above (generators/parallel_generator.py:181-217, low-confidence re-masking).  scratch is the layout
+// of launch_text_commit, conf [B*T] fp64 | x0 [B*T] int32, and its last B*T*4 bytes hold the draws' log-probabilities meanwhile:
+// the head writes x0 and the log-probabilities in place, one small kernel turns the latter into the confidences.
+int mmada_text_select_sampled(mmada_handle* h, const int32_t* rows, int B, int T, float temperature, uint64_t seed, uint64_t* counter,
+                              int64_t* ids, int L, int text_start, const int32_t* k, void* scratch, void* stream) {
+    if (!h || !resident(h)) return mm_fail("mmada_text_select_sampled: no forward resident");
+    if (!rows || !counter || !ids || !k || !scratch) return mm_fail("mmada_text_select_sampled: null argument");
+    if (B <= 0 || T <= 0) return 0;
+    if (text_start < 0 || text_start + T > L) return mm_fail("mmada_text_select_sampled: text span outside the sequence");
+    if (T > 8192) return mm_fail("mmada_text_select_sampled: T=%d too large", T);
+    if ((long long)B * T > (long long)h->res.B * h->res.L) return mm_fail("mmada_text_select_sampled: B*T=%lld exceeds the resident forward", (long long)B * T);
+    const size_t n = (size_t)B * T;
+    int32_t* x0 = (int32_t*)((char*)scratch + n * 8);
+    float* logprob = (float*)((char*)scratch + n * 12);
+    if (mmada_head_sample(h, rows, B * T, 0, h->cfg.vocab, temperature, seed, counter, x0, logprob, nullptr, nullptr, nullptr, stream)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    if (launch_text_sampled_conf(logprob, B, T, ids, L, text_start, h->cfg.mask_token_id, scratch, s)) return 1;
+    return launch_text_commit(scratch, B, T, ids, L, text_start, k, s);
+}
+
+uint32_t mmada_sample_word(uint64_t seed, uint64_t counter, uint32_t row, uint32_t col) { return sample_word(seed, counter, row, col); }
+float mmada_sample_uniform(uint32_t word) { return sample_uniform(word); }
+
+int mmada_probe_gumbel(uint64_t seed, uint64_t counter, int row0, int R, int col0, int N, uint32_t* words_out, float* g_out, void* stream) {
+    if (R <= 0 || N <= 0 || col0 < 0 || row0 < -1 || (!words_out && !g_out)) return mm_fail("mmada_probe_gumbel: bad argument");
+    return launch_gumbel_probe(seed, counter, row0, R, col0, N, words_out, g_out, (hipStream_t)stream);
+}
 
 size_t mmada_score_buffer_bytes(const mmada_handle* h) { return h ? h->score_bytes : 0; }
 

@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include "common.h"
 
-enum GemmEpilogue { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_QKV = 3, EPI_ROWSTAT = 4, EPI_ROWTOPK = 5 };
+enum GemmEpilogue { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_QKV = 3, EPI_ROWSTAT = 4, EPI_ROWTOPK = 5, EPI_ROWSAMPLE = 6 };
 
 struct GemmArgs {
     const bf16_t* A;   // [M, lda]   activations, K-contiguous
@@ -103,6 +103,32 @@ static inline __host__ __device__ float topk_key_logit(uint32_t key) {   // inve
     return x;
 }
 
+// EPI_ROWSAMPLE (the sampling head, launch_head_rowsample): a superset of EPI_ROWSTAT, built like EPI_ROWTOPK.  The same 16-byte
+// record with the same bits (no row has a target), plus per row and 256-column tile ONE 16-byte record
+// samp[nt * ld + m] = {max key, its column in the whole vocabulary (int bits), the bf16 logit at that column as fp32, 0} —
+// key = x + T * g(seed, *counter, row m, column in the whole vocabulary) (sample_noise.h); highest key, then lowest column.
+// Columns beyond N carry the key -inf.  The extra arguments travel in GemmArgs fields of the QKV epilogue: q (records),
+// k (counter: one scalar load per wave), Hq / Hkv (seed, low / high half), Lq (bits of T).
+struct RowSampleArgs {
+    RowStatArgs rs;
+    float4* samp;              // [ceil(N / 256)][ld] records
+    const uint64_t* counter;   // device [1]
+    uint64_t seed;
+    float temperature;         // finite, T >= 0
+};
+static inline __host__ __device__ RowSampleArgs rowsample_args(const GemmArgs& g) {
+    float t;
+    __builtin_memcpy(&t, &g.Lq, 4);
+    return RowSampleArgs{rowstat_args(g), (float4*)g.q, (const uint64_t*)g.k, (uint64_t)(uint32_t)g.Hq | ((uint64_t)(uint32_t)g.Hkv << 32), t};
+}
+static inline void set_rowsample_args(GemmArgs& g, const RowSampleArgs& r) {
+    set_rowstat_args(g, r.rs);
+    g.q = (bf16_t*)r.samp;
+    g.k = (bf16_t*)r.counter;
+    g.Hq = (int)(uint32_t)r.seed; g.Hkv = (int)(uint32_t)(r.seed >> 32);
+    __builtin_memcpy(&g.Lq, &r.temperature, 4);
+}
+
 // A plain C[M, ldc] = A[M, K] · W[N, K]^T on K-contiguous operands (lda = ldw = K), epilogue fields left zero.
 static inline GemmArgs gemm_bt_args(const bf16_t* A, const bf16_t* W, bf16_t* C, int M, int N, int K, int ldc) {
     GemmArgs g{};
@@ -133,6 +159,15 @@ int launch_head_rowstat(const bf16_t* A, const bf16_t* W, int R, int N, int K, i
 size_t head_rowtopk_bytes(int R, int N);
 int launch_head_rowtopk(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, int k, void* part, int32_t* ids,
                         float* logits, float* lse, hipStream_t s);
+
+// gemm.hip: the sampling head.  Same operands; `part` holds head_rowsample_bytes(R, N) bytes: the row-statistics records, ceil8(R)
+// floats, then the 16-byte key records (kernels.h: RowSampleArgs).  ids [R]: arg-max of the key, column in the whole vocabulary;
+// logprob [R] = x_drawn - lse; lse / argmax / vmax [R] or null: the bits launch_head_rowstat returns.  *counter is read by the
+// GEMM's workgroups and incremented by the joining kernel, the last of the call.
+size_t head_rowsample_bytes(int R, int N);
+int launch_head_rowsample(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, float temperature, uint64_t seed,
+                          uint64_t* counter, void* part, int32_t* ids, float* logprob, float* lse, int32_t* argmax, float* vmax,
+                          hipStream_t s);
 
 // elementwise.hip
 // norm_w != null: also xn = RMSNorm(x) * norm_w (the first norm of the forward, fused: SURVEY §2.3 K1)
@@ -173,6 +208,10 @@ struct TextStat { float lmax; int32_t arg; double sum; };  // one rank's record 
 int launch_text_stats_partial(const bf16_t* logits, int B, int T, int Vl, int ld, int col_off, const int64_t* ids, int L,
                               int text_start, int mask_id, TextStat* out, hipStream_t s);
 int launch_text_commit(const void* scratch, int B, int T, int64_t* ids, int L, int text_start, const int32_t* k, hipStream_t s);
+// the scratch layout of launch_text_commit from a draw: x0 [B*T] int32 is already in place (scratch + B*T*8); conf[i] =
+// (double)logprob[i] where ids holds the mask token, else -inf
+int launch_text_sampled_conf(const float* logprob, int B, int T, const int64_t* ids, int L, int text_start, int mask_id, void* scratch,
+                             hipStream_t s);
 int launch_text_select(const bf16_t* logits, const bf16_t* noisy, const bf16_t* unc, float text_cfg, const int32_t* x0_in,
                        int B, int T, int V, int ld, int64_t* ids, int L, int text_start, const int32_t* k, void* scratch,
                        int mask_id, hipStream_t s, const float* rand_conf = nullptr);
@@ -184,4 +223,5 @@ int launch_image_commit(int64_t* ids, int B, int L, const int32_t* pos_map, int 
 
 // probe.hip: MFMA-only diagnostic (attainable roof at the sustained clock on random data)
 int launch_f2bf_probe(const float* in, bf16_t* out, long long n, hipStream_t s);
+int launch_gumbel_probe(uint64_t seed, uint64_t counter, int row0, int R, int col0, int N, uint32_t* words, float* g, hipStream_t s);
 int launch_mfma_probe(const bf16_t* data, float* sink, int iters, int launches, hipStream_t s, double* tflops_out, double* ms_out);

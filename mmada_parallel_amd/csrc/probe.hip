@@ -10,6 +10,7 @@
 // that moment; `roofline.frac` stays quoted against the 2.5 PFLOP/s datasheet peak.
 #include "../../include/mmada_mi355x.h"
 #include "kernels.h"
+#include "sample_noise.h"
 
 namespace {
 
@@ -171,6 +172,30 @@ int launch_f2bf_probe(const float* in, bf16_t* out, long long n, hipStream_t s) 
     return 0;
 }
 
+// ---- noise probe: the device functions of sample_noise.h elementwise (tests: words against the host, g against float64) ------
+// row0 >= 0: element (r, c) of [R, N] is (row0 + r, col0 + c).  row0 == -1, the enumeration mode: no Philox; element i of the
+// flat [R * N] output takes the word (col0 + i) << 9, so col0 = 0 and R * N = 2^23 walk every value of u in order.
+namespace {
+__global__ __launch_bounds__(256) void gumbel_probe_kernel(uint64_t seed, uint64_t counter, int row0, long long total, int col0, int N,
+                                                           uint32_t* __restrict__ words, float* __restrict__ g) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        uint32_t w;
+        if (row0 < 0) w = (uint32_t)((long long)col0 + i) << 9;
+        else w = sample_word(seed, counter, (uint32_t)(row0 + (int)(i / N)), (uint32_t)(col0 + (int)(i % N)));
+        if (words) words[i] = w;
+        if (g) g[i] = sample_gumbel(w);
+    }
+}
+}  // namespace
+int launch_gumbel_probe(uint64_t seed, uint64_t counter, int row0, int R, int col0, int N, uint32_t* words, float* g, hipStream_t s) {
+    const long long total = (long long)R * N;
+    if (total <= 0) return 0;
+    const long long blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(gumbel_probe_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, s, seed, counter, row0, total,
+                       col0, N, words, g);
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 
 // ---- which CUs a stream's CU mask selects (round 5: the tensor-parallel exchange's CU partition, tp_comm.hip) -------------------
 // Every workgroup records where it ran: out[b] = XCC_ID | HW_ID << 8 (HW_REG_XCC_ID bits 3:0; HW_REG_HW_ID: cu_id 11:8, sh_id 12,

@@ -494,3 +494,21 @@ int launch_text_commit(const void* scratch, int B, int T, int64_t* ids, int L, i
     MM_CHECK_HIP(hipGetLastError());
     return 0;
 }
+
+// conf of a draw (mmada_text_select_sampled): ranking by the log-probability is ranking by the probability, and needs no exp
+__global__ void text_sampled_conf_kernel(double* __restrict__ conf, const float* __restrict__ logprob, const int64_t* __restrict__ ids,
+                                         int T, int L, int text_start, int mask_id, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = i / T, t = i - b * T;
+    conf[i] = ids[(size_t)b * L + text_start + t] == (int64_t)mask_id ? (double)logprob[i] : -INFINITY;
+}
+
+int launch_text_sampled_conf(const float* logprob, int B, int T, const int64_t* ids, int L, int text_start, int mask_id, void* scratch,
+                             hipStream_t s) {
+    if (B <= 0 || T <= 0) return 0;
+    hipLaunchKernelGGL(text_sampled_conf_kernel, dim3((B * T + 255) / 256), dim3(256), 0, s, (double*)scratch, logprob, ids, T, L,
+                       text_start, mask_id, B * T);
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
+}

@@ -4,7 +4,8 @@
 Control flow (step schedule, which forwards run, CFG prefix overwrite, final read-out incl. the one random fill) is
 the reference's, line for line in meaning; what changed is *where* the math runs:
   * model forward            -> libmmada_mi355x (mmada_forward_body), LM head only on the rows/columns consumed
-  * text argmax/softmax/topk -> mmada_text_select        (reference :181-217)
+  * text argmax/softmax/topk -> mmada_text_select        (reference :181-217); opt-in text_sampler="device": the draw runs
+    inside the LM head's GEMM (mmada_text_select_sampled) and the logits are never materialised
   * VQ gather + CFG + softmax + argmax -> mmada_head_rows + mmada_image_probs   (:236-295)
   * keep-known / confidence / re-mask / write-back -> mmada_image_commit        (:221-233, :304-344, :23-70)
 All per-step counts (text k, image mask_len) are schedule-determined and precomputed on the host.
@@ -135,6 +136,8 @@ def _ti2ti_steps(
     image_step_list=None,
     rng=None,
     graph=None,
+    text_sampler="torch",
+    sampler_seed=None,
 ):
     """Generator core shared by generate_ti2ti and generate_ti2ti_stepwise: runs the reference loop and yields
     (step, ids, info) after every step; `info` carries the image step's sampled ids (before re-masking) when one ran.
@@ -144,7 +147,14 @@ def _ti2ti_steps(
     (mmada_graph_*): the launches of a step are a fixed sequence over fixed buffers because k, mask_len and the set of
     forwards are schedule-determined.  The first step of each kind runs eagerly, the second is captured,
     the rest replay.  Only at temperature == text_temperature == 0 (the image re-mask temperature is a by-value kernel
-    argument that changes every step otherwise) and when the forward issues no host-side collective."""
+    argument that changes every step otherwise) and when the forward issues no host-side collective.
+
+    `text_sampler="device"` (opt-in; the default "torch" is the reference's path, draw for draw): the text step is ONE
+    mmada_text_select_sampled call — a Gumbel-max draw inside the LM head's GEMM with a counter-based generator keyed by
+    `sampler_seed` (required) and a counter that starts at 0 per call and advances by 1 per text step.  Neither the [B*T, V] logits
+    nor the noise tensor exists.  The draws do not reproduce torch's RNG stream.  Only with text_temperature > 0,
+    remasking == 'low_confidence', on one rank and without micro-batched lanes: anything else raises ValueError.  The image step
+    (torch.multinomial included) is unchanged."""
     if not isinstance(model, LLaDAForMultiModalGeneration):
         raise TypeError("generate_ti2ti (MI355X) needs mmada_parallel_amd.LLaDAForMultiModalGeneration; "
                         "there is no PyTorch fallback path")
@@ -154,6 +164,23 @@ def _ti2ti_steps(
         # the reference asks torch.rand for an int64 uniform on this path (:195-196) and raises
         raise RuntimeError("remasking='random' with an explicit generator raises in the reference too "
                            "(torch.rand(dtype=int64)); pass generator=None")
+    if text_sampler not in ("torch", "device"):
+        raise ValueError(f"text_sampler={text_sampler!r}: 'torch' or 'device'")
+    dev_text = text_sampler == "device"
+    if dev_text:
+        why = None
+        if not text_temperature > 0:
+            why = "text_temperature > 0 (at 0 the text step is an arg-max: nothing is drawn)"
+        elif remasking != 'low_confidence':
+            why = "remasking == 'low_confidence'"
+        elif model.tp_size != 1 or model._comm_in_library:
+            why = "one rank (the vocabulary-parallel draw is a follow-up)"
+        elif input_ids.shape[0] >= 2 and os.environ.get("MMADA_MICROBATCH") == "1":
+            why = "a forward without micro-batched lanes (MMADA_MICROBATCH=1 splits the batch)"
+        elif sampler_seed is None:
+            why = "sampler_seed"
+        if why:
+            raise ValueError(f"text_sampler='device' needs {why}")
     lib, h = model._lib, model._handle
     device = model.device
     rng = rng or TorchRng()
@@ -206,7 +233,8 @@ def _ti2ti_steps(
     mlen_cur = torch.zeros(1, dtype=torch.int32, device=device)
     # the [B*T, V] logits are then never materialised (random re-masking ranks by a uniform draw: the one-rank kernels)
     vp_text = text_temperature == 0 and remasking == 'low_confidence' and model.vocab_parallel_head()
-    text_logits = None if vp_text else torch.empty((B * T, V), dtype=torch.bfloat16, device=device)
+    text_logits = None if vp_text or dev_text else torch.empty((B * T, V), dtype=torch.bfloat16, device=device)
+    draw_counter = torch.zeros(1, dtype=torch.int64, device=device) if dev_text else None
     cond_vq = torch.empty((B * N, CBs), dtype=torch.bfloat16, device=device) if img_steps else None
     unc = torch.empty((2 * B, L), dtype=torch.long, device=device) if need_uncond else None
     unc_vq = torch.empty((2 * B * N, CBs), dtype=torch.bfloat16, device=device) if need_uncond and img_steps else None
@@ -234,6 +262,11 @@ def _ti2ti_steps(
             # and only those 16 bytes per row travel (mmada_text_select_tp) — the [B*T, V] logits exist on no rank
             abi.check(lib.mmada_text_select_tp(h, text_rows.data_ptr(), B, T, ids.data_ptr(), L, text_start,
                                                k_cur.data_ptr(), scratch.data_ptr(), st), "mmada_text_select_tp")
+        elif need_text and dev_text:
+            abi.check(lib.mmada_text_select_sampled(h, text_rows.data_ptr(), B, T, float(text_temperature),
+                                                    int(sampler_seed) & 0xFFFFFFFFFFFFFFFF, draw_counter.data_ptr(), ids.data_ptr(),
+                                                    L, text_start, k_cur.data_ptr(), scratch.data_ptr(), st),
+                      "mmada_text_select_sampled")
         elif need_text:
             model.head_rows(text_rows, 0, V, out=text_logits)  # [B*T, V]
             noisy = None
@@ -388,19 +421,22 @@ def generate_ti2ti(
     return_state=False,
     rng=None,
     graph=None,
+    text_sampler="torch",
+    sampler_seed=None,
 ):
     """Joint text+image generation; returns (List[int] vq ids, str | List[int] text) like the reference
     (generators/parallel_generator.py:102-368).
 
     `graph=True` (or MMADA_GRAPH=1) replays every step as one hipGraph (see _ti2ti_steps; BASELINE configs[4]).
     `return_state=True` additionally returns the final `combined_input_ids` *before* the random fill of
-    still-masked image tokens (reference :360-362) — the quantity parity tests compare."""
+    still-masked image tokens (reference :360-362) — the quantity parity tests compare.
+    `text_sampler="device"` with `sampler_seed`: draw the text tokens inside the LM head's GEMM (see _ti2ti_steps)."""
     ids = pos_list = None
     for _step, ids, info in _ti2ti_steps(model, input_ids, text_start, text_end, image_start, seq_len, newline_every,
                                          text_steps, text_gen_length, text_block_length, timesteps, temperature,
                                          text_temperature, cfg_scale, cfg_img, uncon_text, uncon_image, tokenizer,
                                          remasking, noise_schedule, generator, text_vocab_size, codebook_size, rng=rng,
-                                         graph=graph):
+                                         graph=graph, text_sampler=text_sampler, sampler_seed=sampler_seed):
         pos_list = info.get("pos_list", pos_list)
 
     # ===== final read-out (reference :346-368) =====
@@ -431,7 +467,7 @@ def generate_ti2ti_stepwise(
     text_steps=100, temperature=1.0, text_temperature=0.7, cfg_scale=0.0, cfg_img=4.0,
     uncon_text=None, uncon_image=None, tokenizer=None, remasking='low_confidence',
     noise_schedule=cosine_schedule, generator=None, text_vocab_size=126356,
-    codebook_size=8192, vqvae=None, image_height=512, image_width=512,
+    codebook_size=8192, vqvae=None, image_height=512, image_width=512, text_sampler="torch", sampler_seed=None,
 ):
     """Token-level mirror of the reference's streaming sampler `generate_ti2ti_stepwise` (app.py:143-398): the same
     loop as generate_ti2ti with the Gradio schedule of image steps, yielding after every step
@@ -448,7 +484,8 @@ def generate_ti2ti_stepwise(
         for step, ids, info in _ti2ti_steps(model, input_ids, text_start, text_end, image_start, seq_len, newline_every,
                                             text_steps, 256, 64, 0, temperature, text_temperature, cfg_scale, cfg_img,
                                             uncon_text, uncon_image, tokenizer, remasking, noise_schedule, generator,
-                                            text_vocab_size, codebook_size, image_step_list=sched):
+                                            text_vocab_size, codebook_size, image_step_list=sched, text_sampler=text_sampler,
+                                            sampler_seed=sampler_seed):
             if step >= text_steps:
                 return
             show = step % 5 == 0 or info["image_step"] or step == text_steps - 1

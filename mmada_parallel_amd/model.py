@@ -491,6 +491,52 @@ class LLaDAForMultiModalGeneration(TpLinkMixin):
                                                     logit[lo:hi].data_ptr(), lse[lo:hi].data_ptr(), abi.stream_ptr()), "mmada_head_topk")
         return ids, logit - lse[:, None], lse
 
+    _TP_SAMPLE = ("sample_tokens runs on one rank: the library's sampling head (mmada_head_sample) refuses a tensor-parallel handle; "
+                  "the vocabulary-parallel draw, whose key records would ride the score exchange, is a follow-up")
+    _LANES_SAMPLE = ("sample_tokens on a forward resident in micro-batched lanes: the noise is indexed by the row's index inside "
+                     "the library call, which would restart per lane; run the forward without MMADA_MICROBATCH")
+
+    @property
+    def sample_counter(self) -> torch.Tensor:
+        """The model's own draw counter (int64 [1] on the device, created at 0 on first use): sample_tokens reads it and the
+        library adds 1 per call."""
+        if getattr(self, "_sample_counter", None) is None:
+            self._sample_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+        return self._sample_counter
+
+    def sample_tokens(self, rows: torch.Tensor, temperature: float, col_begin: int = 0, col_end: Optional[int] = None, *,
+                      seed: int, counter: Optional[torch.Tensor] = None, return_stats: bool = False):
+        """One token per row drawn from softmax(logits[rows[r], col_begin:col_end] / temperature) after forward_body(), without
+        materialising the logits or a noise tensor (mmada_head_sample: a Gumbel-max draw in the head GEMM's epilogue).  Returns
+        (ids int32 [R] — column in the WHOLE vocabulary —, logprobs fp32 [R], lse fp32 [R]) and, with return_stats, argmax int32 and
+        max fp32 as well.
+
+        logprobs is the unperturbed log-probability of the drawn token: token_logprobs(rows, ids) bit for bit; lse / argmax / max
+        are its return_stats values.  temperature is finite and >= 0; at 0 the draw is the arg-max.  The noise is a pure function of (seed,
+        counter, r, column) — r the row's index in `rows` — so a call is reproducible: `counter` (int64 [1] on the device, default
+        the model's own, `sample_counter`) is read by the call and incremented by 1 on the device; reset it to repeat a draw.
+        The draws do not reproduce torch's RNG stream.  One rank only, and not on a micro-batched forward."""
+        if self.tp_size != 1 or self._comm_in_library:
+            raise NotImplementedError(self._TP_SAMPLE)
+        if self._resident.split is not None:
+            raise NotImplementedError(self._LANES_SAMPLE)
+        if not 0 <= temperature < float("inf"):
+            raise ValueError(f"sample_tokens: temperature {temperature} is not a finite value >= 0")
+        counter = self.sample_counter if counter is None else counter
+        if counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != self.device:
+            raise ValueError("sample_tokens: counter must be an int64 [1] tensor on the model's device")
+        col_end = self.vocab if col_end is None else col_end
+        rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
+        R = rows.numel()
+        ids = torch.empty(R, dtype=torch.int32, device=self.device)
+        lp, lse = (torch.empty(R, dtype=torch.float32, device=self.device) for _ in range(2))
+        stats = (torch.empty(R, dtype=torch.int32, device=self.device), torch.empty(R, dtype=torch.float32, device=self.device)) if return_stats else ()
+        abi.check(self._lib.mmada_head_sample(self._handle, rows.data_ptr(), R, col_begin, col_end, float(temperature),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, counter.data_ptr(), ids.data_ptr(), lp.data_ptr(),
+                                              lse.data_ptr(), *[t_.data_ptr() for t_ in stats], *([None] * (2 - len(stats))),
+                                              abi.stream_ptr()), "mmada_head_sample")
+        return (ids, lp, lse, *stats)
+
     def score(self, input_ids: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         """Per-token negative log-likelihood, fp32 [B, L]: -log softmax(logits[b, l])[labels[b, l]], 0 where labels == -100 —
         F.cross_entropy(logits.view(-1, V), labels.view(-1), ignore_index=-100, reduction='none') of the reference

@@ -31,7 +31,18 @@ device (tp_link.connect_local_group, pull transport): they share its compute uni
   (c) fused     mmada_head_logprobs: the plain row-statistics head (one target per row, no top-k) — what (d) adds its work to
   (d) top-k     mmada_head_topk: the same GEMM whose epilogue also keeps every tile's eight best + the key-joining kernel
 
-and the peak device memory (a) and (d) add while they run (torch's allocator; for (d) plus the library's record buffer)."""
+and the peak device memory (a) and (d) add while they run (torch's allocator; for (d) plus the library's record buffer).
+
+    python tools/score_bench.py --sample [--out profiles/sample_bench.txt]
+
+--sample: a text step's draw at text_temperature 0.7 over R = 256 and R = 1024 rows, three ways, timed the same way:
+
+  (a) torch     mmada_head_rows over the whole vocabulary + the generator's add_gumbel_noise (a second [R, V] tensor and five
+                elementwise passes) + mmada_text_select: what generate_ti2ti(text_sampler="torch") runs per text step
+  (b) fused     mmada_head_logprobs: the plain row-statistics head — what (c) adds its work to
+  (c) sample    mmada_head_sample: the same GEMM whose epilogue also draws (Philox4x32-10, two logarithms per logit)
+
+and the peak device memory (a) adds while it runs against the record buffer (c) works in."""
 import argparse
 import os
 import statistics
@@ -227,16 +238,108 @@ def main_topk(args):
         f.write(text + "\n")
 
 
+def main_sample(args):
+    from mmada_parallel_amd import abi
+    from mmada_parallel_amd.generators.parallel_generator import add_gumbel_noise
+
+    dev, temp, seed = "cuda:0", 0.7, 20261019
+    cfg = dict(synth.CFG_8B, n_layers=1)
+    sd = synth.synthetic_state_dict(cfg, seed=3, device=dev)
+    model = LLaDAForMultiModalGeneration.from_state_dict(synth.full_config(cfg), sd, device=dev, max_batch=2)
+    del sd
+    lib, h, V = abi.lib(), model._handle, model.vocab
+    lines = [f"score_bench --sample: {torch.cuda.get_device_name(0)}, d = {cfg['d_model']}, V = {V}, text_temperature {temp}, "
+             f"{args.rounds} rounds x {args.reps} calls, device events, ms per call"]
+    for R in (256, 1024):
+        B, T = 1, R                                  # one sequence whose whole length is the text span, every position masked
+        g = torch.Generator().manual_seed(5 + R)
+        ids = torch.randint(0, 126000, (B, T), generator=g).to(dev)
+        model.forward_body(ids)
+        cur = torch.full((B, T), model.MASK_TOKEN, dtype=torch.long, device=dev)
+        rows = torch.arange(R, dtype=torch.int32, device=dev)
+        targets = torch.randint(0, V, (R,), generator=g).to(dev)
+        k = torch.full((B,), 8, dtype=torch.int32, device=dev)
+        scratch = torch.empty(B * T * 16, dtype=torch.uint8, device=dev)
+        logits = torch.empty((R, V), dtype=torch.bfloat16, device=dev)
+        counter = torch.zeros(1, dtype=torch.int64, device=dev)
+
+        def run_a():
+            model.head_rows(rows, 0, V, out=logits)
+            noisy = add_gumbel_noise(logits.view(B, T, V), temperature=temp).contiguous()
+            abi.check(lib.mmada_text_select(h, logits.data_ptr(), noisy.data_ptr(), B, T, V, V, cur.data_ptr(), T, 0, k.data_ptr(),
+                                            scratch.data_ptr(), abi.stream_ptr()), "mmada_text_select")
+
+        def run_b():
+            return model.token_logprobs(rows, targets)
+
+        def run_c():
+            return model.sample_tokens(rows, temp, seed=seed, counter=counter)
+
+        fns = {"a": run_a, "b": run_b, "c": run_c}
+        # (c) agrees with the scoring head: its log-probabilities are those of its own draws, its lse the same bits
+        ids_c, lp_c, lse_c = run_c()
+        lp_b, lse_b, _, _ = model.token_logprobs(rows, ids_c.long(), return_stats=True)
+        torch.cuda.synchronize()
+        assert torch.equal(lp_c, lp_b) and torch.equal(lse_c, lse_b)
+        for f in fns.values():   # warm-up of every timed shape
+            f()
+        torch.cuda.synchronize()
+        logits = None            # (a)'s peak counts its logits too
+        def run_a_alloc():
+            nonlocal logits
+            logits = torch.empty((R, V), dtype=torch.bfloat16, device=dev)
+            run_a()
+        mem_a, mem_c = peak_added(run_a_alloc, dev), peak_added(run_c, dev)
+        own = lib.mmada_score_buffer_bytes(h)
+        times = {n: [] for n in fns}
+        order = ["a", "b", "c"]
+        assert args.reps * 8 <= R                    # (a) commits 8 positions per call: a window never runs out of masked ones
+        for r in range(args.rounds):
+            for n in order[r % 3:] + order[:r % 3]:
+                cur.fill_(model.MASK_TOKEN)          # outside the timed window: re-masking is no part of a text step
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.reps):
+                    fns[n]()
+                e1.record()
+                e1.synchronize()
+                times[n].append(e0.elapsed_time(e1) / args.reps)
+        med = {n: statistics.median(v) for n, v in times.items()}
+        ca = [c / a for a, c in zip(times["a"], times["c"])]
+        cb = [c / b for b, c in zip(times["b"], times["c"])]
+        lines.append(f"R = {R}; log-probabilities and lse of (c) bit-identical to mmada_head_logprobs on its draws")
+        names = {"a": "(a) head_rows + add_gumbel_noise + mmada_text_select", "b": "(b) mmada_head_logprobs (fused, no draw)", "c": "(c) mmada_head_sample"}
+        for n in order:
+            lines.append(f"  {names[n]:54s} median {med[n]:8.3f}  min {min(times[n]):8.3f}  max {max(times[n]):8.3f}")
+        lines.append(f"  (c) / (a): median of rounds {statistics.median(ca):.4f}  min {min(ca):.4f}  max {max(ca):.4f};   "
+                     f"(c) / (b): median of rounds {statistics.median(cb):.4f}  min {min(cb):.4f}  max {max(cb):.4f}")
+        lines.append(f"  peak memory added: (a) {mem_a / 2**20:.1f} MiB of torch tensors (bf16 logits {R * V * 2 / 2**20:.1f} MiB, the noise and its "
+                     f"temporaries);  (c) {mem_c / 2**20:.3f} MiB of torch tensors + {own / 2**20:.2f} MiB record buffer held by the library")
+        del logits
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=12)
     ap.add_argument("--reps", type=int, default=4, help="calls per timed window")
     ap.add_argument("--tp", type=int, default=0, help="k > 1: the functional tensor-parallel rig (k ranks on one device)")
     ap.add_argument("--topk", type=int, default=0, help="K in 1..8: top-k three ways (torch on the logits, the plain fused head, mmada_head_topk)")
+    ap.add_argument("--sample", action="store_true", help="a text step's draw three ways (torch noise on the logits, the plain fused head, "
+                                                          "mmada_head_sample)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "score_tp_bench.txt" if args.tp else "topk_bench.txt" if args.topk else "score_bench.txt")
+        args.out = os.path.join(ROOT, "profiles", "score_tp_bench.txt" if args.tp else "topk_bench.txt" if args.topk else
+                                "sample_bench.txt" if args.sample else "score_bench.txt")
+    if args.sample:
+        if args.tp or args.topk:
+            ap.error("--sample takes no --tp / --topk")
+        return main_sample(args)
     if args.topk:
         if args.tp or not 1 <= args.topk <= 8:
             ap.error("--topk takes K in 1..8 and no --tp")
