@@ -11,7 +11,6 @@
 
 #include "../../include/mmada_mi355x.h"
 #include "handle.h"
-#include "gemm_epilogue.h"
 
 static thread_local char g_err[1024] = "";
 

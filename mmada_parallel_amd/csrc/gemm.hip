@@ -19,12 +19,12 @@
 //   * workgroup ids are remapped XCD-aware and in grouped order so each private L2 sees a compact patch of tiles.
 //
 // Epilogues reproduce the reference's rounding points exactly: every nn.Linear output is rounded to bf16 before
-// anything else touches it.
+// anything else touches it.  (The LM head's row heads launch through launch_gemm like every other epilogue; their own
+// launchers and joining kernels are row_heads.hip.)
 #include <atomic>
 #include <mutex>
 
 #include "gemm_epilogue.h"
-#include "rowstat_fold.h"
 
 namespace {
 
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(NTHREADS, 4) void gemm_bt_kernel(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < T::FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     mainloop<BM, WM, WN>(g, smem, mt * BM, nt * BN, 0, g.K / BK, acc, wave, lane);
-    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK || EPI == EPI_ROWSAMPLE) {
+    if constexpr (is_row_head(EPI)) {
         static_assert(T::LDS_BYTES >= RowTopkLds::BYTES, "the row records reuse the stage buffers");
         __syncthreads();   // every wave has read its last K-tile: the stage buffers are free for the row records
         gemm_epilogue<EPI, T::TM, T::TN, WN>(g, mt * BM, nt * BN, acc, wave, lane, g.M, (int)(uintptr_t)(lptr_t)smem, BM);
@@ -231,7 +231,7 @@ Plan plan(const GemmArgs& g, int force) {
 template <int EPI>
 int launch_t(const GemmArgs& g, const Switches& sw, hipStream_t s) {
     Plan p = plan(g, sw.gemm_config);
-    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK || EPI == EPI_ROWSAMPLE) {
+    if constexpr (is_row_head(EPI)) {
         // the row-statistics epilogue (and its top-k and sampling forms) exists for 256-column tiles of four 64-column waves: a pinned configuration without one
         // (320 x 128; the 16-wave kernel's 2 x 8 wave grids) gets the automatic pick, and that the next taller 4 x 4 grid
         if (p.p8 && p.code == GEMM8_320x128) p = plan(g, -1);
@@ -335,6 +335,8 @@ int launch_gemm(int epi, const GemmArgs& g_in, hipStream_t s) {
     if (g.M <= 0 || g.N <= 0) return 0;
     if (g.K % BK != 0 || g.K <= 0) return mm_fail("gemm: K=%d must be a positive multiple of %d", g.K, BK);
     if ((g.lda % 8) || (g.ldw % 8)) return mm_fail("gemm: lda/ldw must be multiples of 8 elements");
+    if (is_row_head(epi))   // (row_heads.h: what each head needs; a null target is allowed for top-k and sample only)
+        if (const char* fault = row_head_args_fault(epi, row_head_args(g), g.M)) return mm_fail("%s", fault);
     switch (epi) {
         case EPI_STORE: return launch_t<EPI_STORE>(g, sw, s);
         case EPI_RESID: return launch_t<EPI_RESID>(g, sw, s);
@@ -345,209 +347,9 @@ int launch_gemm(int epi, const GemmArgs& g_in, hipStream_t s) {
             if (g.N != (g.Hq + 2 * g.Hkv) * 128) return mm_fail("gemm/qkv: N mismatch");
             if (g.Lp % 8 || g.m_base % 8) return mm_fail("gemm/qkv: Lp and m_base must be multiples of 8");
             return launch_t<EPI_QKV>(g, sw, s);
-        case EPI_ROWSTAT:
-            if (const RowStatArgs rs = rowstat_args(g); !rs.part || !rs.tx || !rs.target || rs.rows <= 0 || rs.rows > g.M || rs.ld < rs.rows)
-                return mm_fail("gemm/rowstat: record buffers missing");
-            return launch_t<EPI_ROWSTAT>(g, sw, s);
-        case EPI_ROWTOPK:   // a null target is allowed here: no row has one
-            if (const RowTopkArgs tk = rowtopk_args(g); !tk.rs.part || !tk.rs.tx || !tk.topk || tk.rs.rows <= 0 || tk.rs.rows > g.M || tk.rs.ld < tk.rs.rows)
-                return mm_fail("gemm/rowtopk: record buffers missing");
-            return launch_t<EPI_ROWTOPK>(g, sw, s);
-        case EPI_ROWSAMPLE:
-            if (const RowSampleArgs sa = rowsample_args(g); !sa.rs.part || !sa.rs.tx || !sa.samp || !sa.counter || sa.rs.rows <= 0 ||
-                                                            sa.rs.rows > g.M || sa.rs.ld < sa.rs.rows || !(sa.temperature >= 0.f) ||
-                                                            __builtin_isinf(sa.temperature))
-                return mm_fail("gemm/rowsample: record buffers or counter missing, or a temperature that is not finite and >= 0");
-            return launch_t<EPI_ROWSAMPLE>(g, sw, s);
+        case EPI_ROWSTAT: return launch_t<EPI_ROWSTAT>(g, sw, s);
+        case EPI_ROWTOPK: return launch_t<EPI_ROWTOPK>(g, sw, s);
+        case EPI_ROWSAMPLE: return launch_t<EPI_ROWSAMPLE>(g, sw, s);
     }
     return mm_fail("gemm: bad epilogue %d", epi);
-}
-
-// ---- the scoring head: D = A · lm_head[col0 : col0 + N]^T reduced to row statistics (gemm_epilogue.h: EPI_ROWSTAT) ----------
-// Record buffer: [ceil(N / 256)][ceil8(R)] records of 16 bytes, then ceil8(R) target logits (fp32): 1/32 of the bytes of the
-// bf16 logits it stands for, plus 4 bytes per row.
-static inline int rowstat_tiles(int N) { return (N + BN - 1) / BN; }
-size_t head_rowstat_bytes(int R, int N) {
-    const size_t rp = (size_t)((R + 7) / 8 * 8);
-    return rp * rowstat_tiles(N) * sizeof(float4) + rp * sizeof(float);
-}
-
-// Joins the column-tile records of a row in the fixed order of rowstat_fold.h (shared with the tensor-parallel join of
-// tp_comm.hip): neither the tile order of the GEMM nor its configuration shows in the result.
-__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void rowstat_combine_kernel(const float4* part, const float* tx, const int64_t* targets,
-                                                                               int R, int ld, int ntn, float* logprob, float* lse_out,
-                                                                               int32_t* argmax_out, float* max_out) {
-    const int row = blockIdx.x * RS_ROWS + threadIdx.x % RS_ROWS;
-    float m, sum;
-    int arg;
-    if (!rowstat_fold([&](int t, int r) { return part[(size_t)t * ld + r]; }, row, R, ntn, m, sum, arg)) return;
-    rowstat_finish(row, m, sum, arg, targets[row], tx[row], logprob, lse_out, argmax_out, max_out);
-}
-
-int launch_head_rowstat(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, const int64_t* targets, void* part,
-                        float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s) {
-    if (R <= 0 || N <= 0) return 0;
-    const int rp = (R + 7) / 8 * 8, ntn = rowstat_tiles(N);
-    GemmArgs g = gemm_bt_args(A, W, nullptr, rp, N, K, 8);
-    const RowStatArgs rs{(float4*)part, (float*)((float4*)part + (size_t)rp * ntn), targets, R, rp, col0};
-    set_rowstat_args(g, rs);
-    // a target outside the column range leaves -inf behind (no lane holds it)
-    MM_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)rs.tx, 0xff800000u, rp, s));
-    if (launch_gemm(EPI_ROWSTAT, g, s)) return 1;
-    hipLaunchKernelGGL(rowstat_combine_kernel, dim3((R + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, rs.part, rs.tx,
-                       targets, R, rp, ntn, logprob, lse, argmax, vmax);
-    MM_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- the top-k head: the same launch with EPI_ROWTOPK (gemm_epilogue.h), which also leaves every tile's eight best keys ------
-// Record buffer: the row-statistics records and ceil8(R) floats as above, then [ceil(N / 256)][ceil8(R)] key records of 32 bytes:
-// 3/32 of the bytes of the bf16 logits it stands for, plus 4 bytes per row.
-size_t head_rowtopk_bytes(int R, int N) {
-    const size_t rp = (size_t)((R + 7) / 8 * 8);
-    return head_rowstat_bytes(R, N) + rp * rowstat_tiles(N) * (TOPK_MAX * sizeof(uint32_t));
-}
-
-// A candidate of the join: {order value of the logit, ~column inside the launch} as one 64-bit number — logit descending, then
-// tile ascending, then column ascending is ONE unsigned compare, and candidates of a row are distinct.  0: no candidate.
-MM_DEVICE unsigned long long topk_cand(uint32_t key, int tile) {
-    if (key == 0u) return 0ull;
-    const uint32_t col = (uint32_t)tile * (uint32_t)BN + (255u - (key & 255u));
-    return ((unsigned long long)(key >> 16) << 32) | (unsigned long long)(~col);
-}
-// best[] stays sorted in descending order; c replaces the last entry and moves up to its place
-MM_DEVICE void topk_insert(unsigned long long (&best)[TOPK_MAX], unsigned long long c) {
-    best[TOPK_MAX - 1] = c;
-#pragma unroll
-    for (int i = TOPK_MAX - 1; i > 0; --i) {
-        const unsigned long long lo = best[i], hi = best[i - 1];
-        best[i - 1] = lo > hi ? lo : hi;
-        best[i] = lo > hi ? hi : lo;
-    }
-}
-
-// Thread (row, group j) walks the key records of tiles j, j + 16, ... and keeps the best eight candidates sorted in registers (a
-// record is sorted: its entries are taken until one does not beat the thread's eighth — most tiles end at their first); thread
-// (row, 0) merges the 16 lists of the row through LDS the same way and writes the first k.  The candidates are totally ordered, so
-// the walk's order does not show in the result.  lse: the fold and the expression of rowstat_combine_kernel on the same records.
-__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void rowtopk_combine_kernel(const float4* part, const uint32_t* topk, int R, int ld, int ntn,
-                                                                               int col0, int k, int32_t* ids, float* logits, float* lse_out,
-                                                                               float* spare /* [ld] */) {
-    __shared__ unsigned long long sk[RS_GROUPS][TOPK_MAX][RS_ROWS];
-    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
-    const int row = blockIdx.x * RS_ROWS + rl;
-    unsigned long long best[TOPK_MAX];
-#pragma unroll
-    for (int e = 0; e < TOPK_MAX; ++e) best[e] = 0ull;
-    if (row < R)
-        for (int t = j; t < ntn; t += RS_GROUPS) {
-            const u32x4* rec = (const u32x4*)(topk + ((size_t)t * ld + row) * TOPK_MAX);
-            const u32x4 lo = rec[0], hi = rec[1];
-            const uint32_t key[TOPK_MAX] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-            for (int e = 0; e < TOPK_MAX; ++e) {
-                const unsigned long long c = topk_cand(key[e], t);
-                if (c <= best[TOPK_MAX - 1]) break;
-                topk_insert(best, c);
-            }
-        }
-#pragma unroll
-    for (int e = 0; e < TOPK_MAX; ++e) sk[j][e][rl] = best[e];
-    float m, sum;
-    int arg;
-    // (its barrier also orders the candidate lists above)
-    if (!rowstat_fold([&](int t, int r) { return part[(size_t)t * ld + r]; }, row, R, ntn, m, sum, arg)) return;
-    for (int q = 1; q < RS_GROUPS; ++q)
-#pragma unroll
-        for (int e = 0; e < TOPK_MAX; ++e) {
-            const unsigned long long c = sk[q][e][rl];
-            if (c <= best[TOPK_MAX - 1]) break;
-            topk_insert(best, c);
-        }
-#pragma unroll
-    for (int e = 0; e < TOPK_MAX; ++e)
-        if (e < k) {
-            ids[(size_t)row * k + e] = col0 + (int)~(uint32_t)best[e];
-            logits[(size_t)row * k + e] = topk_key_logit((uint32_t)(best[e] >> 32) << 16);
-        }
-    rowstat_finish(row, m, sum, arg, -1, 0.f, spare, lse_out, nullptr, nullptr);
-}
-
-int launch_head_rowtopk(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, int k, void* part, int32_t* ids,
-                        float* logits, float* lse, hipStream_t s) {
-    if (R <= 0 || N <= 0) return 0;
-    if (k < 1 || k > TOPK_MAX || k > N) return mm_fail("head top-k: k=%d outside [1, min(%d, N=%d)]", k, TOPK_MAX, N);
-    const int rp = (R + 7) / 8 * 8, ntn = rowstat_tiles(N);
-    GemmArgs g = gemm_bt_args(A, W, nullptr, rp, N, K, 8);
-    RowTopkArgs tk;
-    tk.rs = RowStatArgs{(float4*)part, (float*)((float4*)part + (size_t)rp * ntn), nullptr, R, rp, col0};
-    tk.topk = (uint32_t*)(tk.rs.tx + rp);
-    set_rowtopk_args(g, tk);
-    if (launch_gemm(EPI_ROWTOPK, g, s)) return 1;
-    hipLaunchKernelGGL(rowtopk_combine_kernel, dim3((R + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, tk.rs.part, tk.topk,
-                       R, rp, ntn, col0, k, ids, logits, lse, tk.rs.tx);
-    MM_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- the sampling head: the same launch with EPI_ROWSAMPLE (gemm_epilogue.h), which also leaves every tile's best key ---------
-// Record buffer: the row-statistics records and ceil8(R) floats as above, then [ceil(N / 256)][ceil8(R)] key records of 16 bytes:
-// 1/16 of the bytes of the bf16 logits it stands for, plus 4 bytes per row.
-size_t head_rowsample_bytes(int R, int N) {
-    const size_t rp = (size_t)((R + 7) / 8 * 8);
-    return head_rowstat_bytes(R, N) + rp * rowstat_tiles(N) * sizeof(float4);
-}
-
-// Thread (row, group j) walks the key records of tiles j, j + 16, ... in ascending order (a later equal key lies further right and
-// does not replace); thread (row, 0) folds the 16 groups through LDS, where the groups interleave the tiles and the lowest column
-// wins on equal keys.  The order of keys is total (key, then column), so neither the GEMM's tile order nor its configuration shows.
-// lse / argmax / max: the fold and the expression of rowstat_combine_kernel on the same records, with the drawn column's logit as
-// the target logit: logprob = x_drawn - lse.  The kernel is the last of the call: every workgroup of the GEMM has read *counter.
-__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void rowsample_combine_kernel(const float4* part, const float4* samp, int R, int ld, int ntn,
-                                                                                 int32_t* ids, float* logprob, float* lse_out, int32_t* argmax_out,
-                                                                                 float* max_out, uint64_t* counter) {
-    __shared__ float sk[RS_GROUPS][RS_ROWS], sx[RS_GROUPS][RS_ROWS];
-    __shared__ int sc[RS_GROUPS][RS_ROWS];
-    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
-    const int row = blockIdx.x * RS_ROWS + rl;
-    float bk = -__builtin_inff(), bx = -__builtin_inff();
-    int bc = 0x7fffffff;
-    if (row < R)
-        for (int t = j; t < ntn; t += RS_GROUPS) {
-            const float4 p = samp[(size_t)t * ld + row];
-            gemm_detail::rowsample_take(bk, bc, bx, p.x, __float_as_int(p.y), p.z);
-        }
-    sk[j][rl] = bk; sc[j][rl] = bc; sx[j][rl] = bx;
-    float m, sum;
-    int arg;
-    // (its barrier also orders the key triples above)
-    const bool mine = rowstat_fold([&](int t, int r) { return part[(size_t)t * ld + r]; }, row, R, ntn, m, sum, arg);
-    if (mine) {
-        for (int q = 1; q < RS_GROUPS; ++q) gemm_detail::rowsample_take(bk, bc, bx, sk[q][rl], sc[q][rl], sx[q][rl]);
-        ids[row] = bc;
-        rowstat_finish(row, m, sum, arg, bc, bx, logprob, lse_out, argmax_out, max_out);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *counter += 1;
-}
-
-int launch_head_rowsample(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, float temperature, uint64_t seed,
-                          uint64_t* counter, void* part, int32_t* ids, float* logprob, float* lse, int32_t* argmax, float* vmax,
-                          hipStream_t s) {
-    if (R <= 0 || N <= 0) return 0;
-    if (!(temperature >= 0.f) || __builtin_isinf(temperature))
-        return mm_fail("head sample: temperature %g is not a finite value >= 0", (double)temperature);
-    const int rp = (R + 7) / 8 * 8, ntn = rowstat_tiles(N);
-    GemmArgs g = gemm_bt_args(A, W, nullptr, rp, N, K, 8);
-    RowSampleArgs sa;
-    sa.rs = RowStatArgs{(float4*)part, (float*)((float4*)part + (size_t)rp * ntn), nullptr, R, rp, col0};
-    sa.samp = (float4*)(sa.rs.tx + rp);
-    sa.counter = counter;
-    sa.seed = seed;
-    sa.temperature = temperature;
-    set_rowsample_args(g, sa);
-    if (launch_gemm(EPI_ROWSAMPLE, g, s)) return 1;
-    hipLaunchKernelGGL(rowsample_combine_kernel, dim3((R + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, sa.rs.part, sa.samp, R,
-                       rp, ntn, ids, logprob, lse, argmax, vmax, counter);
-    MM_CHECK_HIP(hipGetLastError());
-    return 0;
 }

@@ -103,7 +103,7 @@ struct Gemm8 {
     static constexpr int SHORT_BM = BM - 16;
     static_assert(NPB % 8 == 0 && (RA0 == 0 || RA1 == 0 || RA0 == RA1) && NPA0 <= 24 && NPA1 <= 24, "piece split");
     static_assert(LDS + SiluLut::BYTES <= 160 * 1024, "LDS (K-tile buffers + the SwiGLU epilogue's SiLU table)");
-    static_assert(BN != 256 || LDS >= RowTopkLds::BYTES, "the row-statistics / top-k epilogues reuse the K-tile buffers");
+    static_assert(BN != 256 || LDS >= RowTopkLds::BYTES, "the row heads' epilogue reuses the K-tile buffers");
 
     const char* Ab;  // wave-uniform byte bases of the A / W panels of this output tile
     const char* Wb;
@@ -446,7 +446,7 @@ int launch_cfg8(const GemmArgs& g, const Switches& sw, hipStream_t s) {
 template <int EPI>
 int launch_epi8(int cfg, const GemmArgs& g, const Switches& sw, hipStream_t s) {
     constexpr int SW = EPI == EPI_QKV ? 2 : 1;
-    if constexpr (EPI == EPI_ROWSTAT || EPI == EPI_ROWTOPK || EPI == EPI_ROWSAMPLE) {   // 256-column tiles only (gemm_epilogue.h: one record per row and 256 columns)
+    if constexpr (is_row_head(EPI)) {   // 256-column tiles only (row_heads.h: one record per row and 256 columns)
         switch (cfg) {
             case GEMM8_320x256: return launch_cfg8<EPI, Gemm8<320, 256, 2, 4, SW, 2>>(g, sw, s);
             case GEMM8_256x256: return launch_cfg8<EPI, Gemm8<256, 256, 2, 4, SW, 2>>(g, sw, s);

@@ -5,7 +5,7 @@
 // anything else touches it (model/modeling_llada.py:925-927, 741-744, 962-970).
 #pragma once
 #include "kernels.h"
-#include "sample_noise.h"
+#include "row_head_epilogue.h"
 
 namespace gemm_detail {
 
@@ -73,367 +73,14 @@ MM_DEVICE void tile_coords_g(int t, int ntm, int ntn, int GM, int GN, int& mt, i
 template <int GN = 4>
 MM_DEVICE void tile_coords(int t, int ntm, int ntn, int& mt, int& nt) { tile_coords_g(t, ntm, ntn, 0, GN, mt, nt); }
 
-// ---- EPI_ROWSTAT: the scoring head (round 7).  Nothing of D is stored: a workgroup reduces its BM x 256 logits to one record per
-// row, {max, sum exp(x - max), first column of the max}, and hands the one logit at the row's target column out.  x is the
-// accumulator ROUNDED TO BF16 first — the logits nn.Linear would have written (the rounding point every other epilogue keeps).
-// Three steps, two workgroup barriers, through 15 KiB of the LDS the main loop has finished with (RowStatLds):
-//   1. every wave: max / first arg-max over its 64 columns of each of its rows — in registers over the lane's values, then
-//      across the lanes that share the row (__shfl_xor: lane ^ 16, ^ 32 in the transposed layout, ^ 1 ... ^ 8 in the other);
-//   2. with the TILE's max of the row (the 4 waves' maxima from LDS): sum of exp2((x - max) * log2 e), one v_exp_f32 per logit;
-//   3. thread r of the workgroup joins the 4 waves' records of tile row r and writes the record (one 16-byte store, 256 B per 16
-//      lanes).
-// The sum is evaluated in ONE fixed tree whatever kernel, tile height or operand order ran: groups of 4 consecutive columns
-// (e0 + e1) + (e2 + e3); the 4 fragments of a wave's 64 columns in order; the 4 column groups of a fragment (g0 + g1) + (g2 + g3);
-// the 4 waves (w0 + w1) + (w2 + w3).  fp32 addition commutes, so both layouts produce the same bits; max, arg-max and the target
-// logit are functions of the bf16 logits alone.
-struct RowStatLds {
-    static constexpr int ROWS = 320, WAVES = 4;   // tallest row tile, wave columns of a 256-column tile of 64-column waves
-    static constexpr int MAX = 0, ARG = ROWS * WAVES * 4, SUM = 2 * ROWS * WAVES * 4, BYTES = 3 * ROWS * WAVES * 4;
-};
-typedef __attribute__((address_space(3))) float* lds_f32_ptr;
-typedef __attribute__((address_space(3))) int* lds_i32_ptr;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wint-to-pointer-cast"
-MM_DEVICE float lds_ldf(int byte_off) { return *(lds_f32_ptr)(uint32_t)byte_off; }
-MM_DEVICE void lds_stf(int byte_off, float v) { *(lds_f32_ptr)(uint32_t)byte_off = v; }
-MM_DEVICE int lds_ldi(int byte_off) { return *(lds_i32_ptr)(uint32_t)byte_off; }
-MM_DEVICE void lds_sti(int byte_off, int v) { *(lds_i32_ptr)(uint32_t)byte_off = v; }
-#pragma clang diagnostic pop
-
-// ---- EPI_ROWTOPK: EPI_ROWSTAT plus the tile's eight best logits per row (kernels.h: RowTopkArgs, topk_key).  The same three steps:
-//   1. also, per slot: the lane's keys (16 in the transposed layout, 4 in the other), then eight rounds of { the lane's best
-//      remaining key ; the best of the lanes that share the row (__shfl_xor, as for the maximum) ; the lane that holds the winner
-//      retires it — keys are distinct, an equality compare finds it }.  The writer lane stores the wave column's eight keys (two
-//      16-byte LDS stores) behind the RowStatLds arrays: 4 wave columns x 320 rows x 32 B;
-//   3. the thread that joins tile row r merges the four sorted lists (eight rounds over the four list heads) and writes the
-//      32-byte record as two 16-byte stores.
-// Columns beyond N carry key 0, below every real key (the order value of -inf is 0x007f); a retired key is 0 too.
-struct RowTopkLds {
-    static constexpr int KEYS = RowStatLds::BYTES, BYTES = KEYS + RowStatLds::ROWS * RowStatLds::WAVES * TOPK_MAX * 4;
-};
-typedef __attribute__((address_space(3))) u32x4* lds_u32x4_ptr;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wint-to-pointer-cast"
-MM_DEVICE void lds_st128(int byte_off, u32x4 v) { *(lds_u32x4_ptr)(uint32_t)byte_off = v; }
-#pragma clang diagnostic pop
-MM_DEVICE uint32_t umax32(uint32_t a, uint32_t b) { return a > b ? a : b; }
-
-// ---- EPI_ROWSAMPLE: EPI_ROWSTAT plus a Gumbel-max draw per row (kernels.h: RowSampleArgs; sample_noise.h: the noise).  The same
-// three steps:
-//   1. also, per slot: key = x + T * g of the lane's values, the lane's best {key, column, x} (the first column on equal keys),
-//      then the best of the lanes that share the row (__shfl_xor, as for the maximum).  In the transposed layout a lane's four
-//      consecutive columns cost one Philox evaluation (two when the launch's first column is no multiple of 4), in the other
-//      layout every value costs one.  The writer lane stores the wave column's triple behind the RowStatLds arrays;
-//   3. the thread that joins tile row r takes the best of the four wave columns (they ascend: a later equal key does not replace)
-//      and writes the second 16-byte record.
-struct RowSampleLds {
-    static constexpr int N1 = RowStatLds::ROWS * RowStatLds::WAVES * 4;
-    static constexpr int KEY = RowStatLds::BYTES, COL = KEY + N1, X = COL + N1, BYTES = X + N1;
-};
-static_assert(RowSampleLds::BYTES <= RowTopkLds::BYTES, "the sampling head fits the LDS the top-k head reserves");
-MM_DEVICE void rowsample_take(float& k, int& c, float& x, float ok, int oc, float ox) {   // highest key, then lowest column
-    if (ok > k || (ok == k && oc < c)) { k = ok; c = oc; x = ox; }
-}
-
-MM_DEVICE void rowstat_take(float& m, int& a, float om, int oa) {   // torch's arg-max tie rule: the first index wins
-    if (om > m || (om == m && oa < a)) { m = om; a = oa; }
-}
-MM_DEVICE float rowstat_exp(float x, float m) {
-#pragma clang fp contract(off)
-    return __builtin_amdgcn_exp2f((x - m) * 1.44269504088896340736f);
-}
-// column (inside the launch) of row m's target, or -1: none in this launch
-MM_DEVICE int rowstat_target(const GemmArgs& g, const RowStatArgs& rs, int m) {
-    const long long t = rs.target[m] - (long long)rs.col0;
-    return t >= 0 && t < (long long)g.N ? (int)t : -1;
-}
-
-// TR: transposed accumulator layout (gemm_epilogue_t) or not (gemm_epilogue); lds: byte address of RowStatLds::BYTES free bytes
-// (TOPK, the EPI_ROWTOPK form: RowTopkLds::BYTES; SAMPLE, the EPI_ROWSAMPLE form: RowSampleLds::BYTES)
-template <bool TR, int TM, int TN, int WN, bool TOPK = false, bool SAMPLE = false>
-MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim, int lds,
-                                 int bm /* rows of the workgroup's tile, <= RowStatLds::ROWS */) {
-#pragma clang fp contract(off)
-    constexpr int FM = TM / 16, FN = TN / 16;
-    static_assert(TN == 64 && WN == RowStatLds::WAVES, "row statistics: 256-column tiles of four 64-column waves");
-    const int wm = wave / WN, wn = wave % WN;
-    const int l15 = lane & 15, lq = lane >> 4;
-    const int wcol0 = n0 + wn * TN;
-    const RowStatArgs rs = rowstat_args(g);
-    const int rows = min(m_lim, rs.rows);
-    const float NEG = -__builtin_inff();
-    // slots: the rows a lane takes part in.  TR: FM (row mi*16 + l15, 16 values: 4 fragments x 4 consecutive columns lq*4 + r);
-    // else FM * 4 (row mi*16 + lq*4 + r, 4 values: column l15 of 4 fragments)
-    constexpr int NS = TR ? FM : FM * 4;
-    const bool writer = TR ? lq == 0 : l15 == 0;
-    RowSampleArgs sa{};
-    uint64_t ctr = 0;
-    if constexpr (SAMPLE) {
-        sa = rowsample_args(g);
-        ctr = *sa.counter;   // the same address in every lane: one scalar load per wave
-    }
-    // SAMPLE in the untransposed layout (the 16-wave kernel: 128 VGPRs per lane): the logits are needed as bf16 values only, so
-    // they are rounded once and kept two to a register — 40 registers instead of 80 at 320 rows — which is what lets the draw's
-    // Philox state and logarithms fit beside them without scratch.  Unpacking a value is one shift or mask, exact.
-    constexpr bool PACKED = SAMPLE && !TR;
-    uint32_t pk[PACKED ? FM : 1][PACKED ? FN : 1][2];
-    if constexpr (PACKED) {
-#pragma unroll
-        for (int mi = 0; mi < FM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < FN; ++ni) {
-                pk[mi][ni][0] = pack_bf2(acc[mi][ni][0], acc[mi][ni][1]);
-                pk[mi][ni][1] = pack_bf2(acc[mi][ni][2], acc[mi][ni][3]);
-            }
-    }
-    // between two steps: the unpacked values of one step are not kept in registers for the next (the compiler would otherwise
-    // reuse them — all 80 again); every step unpacks what it needs, when it needs it
-    auto repack = [&]() {
-        if constexpr (PACKED) {
-#pragma unroll
-            for (int mi = 0; mi < FM; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < FN; ++ni) asm volatile("" : "+v"(pk[mi][ni][0]), "+v"(pk[mi][ni][1]));
-        }
-    };
-    repack();   // ... and the packing itself happens HERE, not where a value is first used (the fp32 accumulators die now)
-    auto slot_row = [&](int sl) { return TR ? wm * TM + sl * 16 + l15 : wm * TM + (sl >> 2) * 16 + lq * 4 + (sl & 3); };
-    auto val = [&](int sl, int ni, int r) {   // bf16-rounded logit; columns beyond N never win and add nothing
-        const int n = wcol0 + ni * 16 + (TR ? lq * 4 + r : l15);
-        float a;
-        if constexpr (PACKED) {
-            const uint32_t p = pk[sl >> 2][ni][(sl & 3) >> 1];
-            return n < g.N ? __uint_as_float((sl & 1) ? p & 0xffff0000u : p << 16) : NEG;
-        } else if constexpr (TR) a = acc[sl][ni][r];
-        else a = acc[sl >> 2][ni][sl & 3];
-        return n < g.N ? bfround(a) : NEG;
-    };
-    // ---- 1: wave maxima; the target logit ----
-#pragma unroll
-    for (int sl = 0; sl < NS; ++sl) {
-        const int rt = slot_row(sl), m = m0 + rt;
-        int tc;
-        if constexpr (SAMPLE) tc = -1;
-        else if constexpr (TOPK) tc = m < rows && rs.target ? rowstat_target(g, rs, m) : -1;
-        else tc = m < rows ? rowstat_target(g, rs, m) : -1;
-        const int c0 = wcol0 + (TR ? lq * 4 : l15);
-        float bm = NEG;
-        int ba = c0;
-#pragma unroll
-        for (int ni = 0; ni < FN; ++ni)
-#pragma unroll
-            for (int r = 0; r < (TR ? 4 : 1); ++r) {
-                const float x = val(sl, ni, r);
-                if (x > bm) { bm = x; ba = c0 + ni * 16 + r; }
-            }
-        const int d = tc - c0;   // this lane holds the target column if d = ni*16 + r
-        if (tc >= 0 && d >= 0 && d < TN && (d & 15) < (TR ? 4 : 1)) {
-            float x = NEG;
-#pragma unroll
-            for (int ni = 0; ni < FN; ++ni)
-#pragma unroll
-                for (int r = 0; r < (TR ? 4 : 1); ++r)
-                    if (d == ni * 16 + r) x = val(sl, ni, r);
-            rs.tx[m] = x;
-        }
-        if constexpr (TR) {
-            rowstat_take(bm, ba, __shfl_xor(bm, 16, 64), __shfl_xor(ba, 16, 64));
-            rowstat_take(bm, ba, __shfl_xor(bm, 32, 64), __shfl_xor(ba, 32, 64));
-        } else {
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) rowstat_take(bm, ba, __shfl_xor(bm, o, 64), __shfl_xor(ba, o, 64));
-        }
-        if (writer) {
-            lds_stf(lds + RowStatLds::MAX + (wn * RowStatLds::ROWS + rt) * 4, bm);
-            lds_sti(lds + RowStatLds::ARG + (wn * RowStatLds::ROWS + rt) * 4, ba);
-        }
-        if constexpr (TOPK) {
-            constexpr int NR = TR ? 4 : 1, NV = FN * NR;
-            uint32_t key[NV], win[TOPK_MAX];
-#pragma unroll
-            for (int ni = 0; ni < FN; ++ni)
-#pragma unroll
-                for (int r = 0; r < NR; ++r) {
-                    const int ct = wn * TN + ni * 16 + (TR ? lq * 4 + r : l15);   // column inside the 256-column tile
-                    float a;
-                    if constexpr (TR) a = acc[sl][ni][r];
-                    else a = acc[sl >> 2][ni][sl & 3];
-                    key[ni * NR + r] = n0 + ct < g.N ? topk_key(bfround(a), ct) : 0u;
-                }
-#pragma unroll
-            for (int e = 0; e < TOPK_MAX; ++e) {
-                uint32_t b = key[0];
-#pragma unroll
-                for (int i = 1; i < NV; ++i) b = umax32(b, key[i]);
-                if constexpr (TR) {
-                    b = umax32(b, __shfl_xor(b, 16, 64));
-                    b = umax32(b, __shfl_xor(b, 32, 64));
-                } else {
-#pragma unroll
-                    for (int o = 1; o < 16; o <<= 1) b = umax32(b, __shfl_xor(b, o, 64));
-                }
-                win[e] = b;
-#pragma unroll
-                for (int i = 0; i < NV; ++i) key[i] = key[i] == b ? 0u : key[i];
-            }
-            if (writer) {
-                const int at = lds + RowTopkLds::KEYS + (wn * RowStatLds::ROWS + rt) * (TOPK_MAX * 4);
-                lds_st128(at, u32x4{win[0], win[1], win[2], win[3]});
-                lds_st128(at + 16, u32x4{win[4], win[5], win[6], win[7]});
-            }
-        }
-        if constexpr (SAMPLE) {
-            const uint32_t gc0 = (uint32_t)(rs.col0 + c0);     // column in the whole vocabulary of the lane's first value
-            const uint32_t sh = (uint32_t)rs.col0 & 3u;        // wave-uniform: c0 is a multiple of 4 in the transposed layout
-            float bk = NEG, bx = NEG;
-            int bc = c0;
-#pragma unroll
-            for (int ni = 0; ni < FN; ++ni) {
-                const uint32_t gc = gc0 + ni * 16;
-                uint32_t w0, w1 = 0u, w2 = 0u, w3 = 0u;
-                if constexpr (TR) {
-                    sample_words4(sa.seed, ctr, (uint32_t)m, gc >> 2, w0, w1, w2, w3);
-                    if (sh) {   // the lane's four columns straddle two blocks
-                        uint32_t q0, q1, q2, q3;
-                        sample_words4(sa.seed, ctr, (uint32_t)m, (gc >> 2) + 1u, q0, q1, q2, q3);
-                        const uint32_t a1 = w1, a2 = w2, a3 = w3;    // the columns are words sh .. sh + 3 of the pair
-                        w0 = sh == 1u ? a1 : sh == 2u ? a2 : a3;
-                        w1 = sh == 1u ? a2 : sh == 2u ? a3 : q0;
-                        w2 = sh == 1u ? a3 : sh == 2u ? q0 : q1;
-                        w3 = sh == 1u ? q0 : sh == 2u ? q1 : q2;
-                    }
-                } else
-                    w0 = sample_word(sa.seed, ctr, (uint32_t)m, gc);
-#pragma unroll
-                for (int r = 0; r < (TR ? 4 : 1); ++r) {
-                    const float x = val(sl, ni, r);
-                    const int n = wcol0 + ni * 16 + (TR ? lq * 4 + r : l15);
-                    const uint32_t w = r == 0 ? w0 : r == 1 ? w1 : r == 2 ? w2 : w3;
-                    const float key = n < g.N ? sample_key(x, sa.temperature, sample_gumbel(w)) : NEG;
-                    if (key > bk) { bk = key; bc = c0 + ni * 16 + r; bx = x; }
-                }
-            }
-            if constexpr (TR) {
-                rowsample_take(bk, bc, bx, __shfl_xor(bk, 16, 64), __shfl_xor(bc, 16, 64), __shfl_xor(bx, 16, 64));
-                rowsample_take(bk, bc, bx, __shfl_xor(bk, 32, 64), __shfl_xor(bc, 32, 64), __shfl_xor(bx, 32, 64));
-            } else {
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1)
-                    rowsample_take(bk, bc, bx, __shfl_xor(bk, o, 64), __shfl_xor(bc, o, 64), __shfl_xor(bx, o, 64));
-            }
-            if (writer) {
-                const int at = (wn * RowStatLds::ROWS + rt) * 4;
-                lds_stf(lds + RowSampleLds::KEY + at, bk);
-                lds_sti(lds + RowSampleLds::COL + at, bc);
-                lds_stf(lds + RowSampleLds::X + at, bx);
-            }
-        }
-    }
-    repack();
-    __syncthreads();
-    // ---- 2: sums of exponentials against the tile's row max ----
-#pragma unroll
-    for (int sl = 0; sl < NS; ++sl) {
-        const int rt = slot_row(sl);
-        float mt = lds_ldf(lds + RowStatLds::MAX + rt * 4);
-#pragma unroll
-        for (int w = 1; w < WN; ++w) mt = fmaxf(mt, lds_ldf(lds + RowStatLds::MAX + (w * RowStatLds::ROWS + rt) * 4));
-        float s = 0.f;
-#pragma unroll
-        for (int ni = 0; ni < FN; ++ni) {
-            float gsum;
-            if constexpr (TR) {
-                gsum = (rowstat_exp(val(sl, ni, 0), mt) + rowstat_exp(val(sl, ni, 1), mt)) +
-                       (rowstat_exp(val(sl, ni, 2), mt) + rowstat_exp(val(sl, ni, 3), mt));
-            } else {
-                gsum = rowstat_exp(val(sl, ni, 0), mt);
-                gsum += __shfl_xor(gsum, 1, 64);
-                gsum += __shfl_xor(gsum, 2, 64);
-            }
-            s = ni == 0 ? gsum : s + gsum;
-        }
-        if constexpr (TR) {
-            s += __shfl_xor(s, 16, 64);
-            s += __shfl_xor(s, 32, 64);
-        } else {
-            s += __shfl_xor(s, 4, 64);
-            s += __shfl_xor(s, 8, 64);
-        }
-        if (writer) lds_stf(lds + RowStatLds::SUM + (wn * RowStatLds::ROWS + rt) * 4, s);
-    }
-    __syncthreads();
-    // ---- 3: one record per tile row ----
-    const int rt = wave * 64 + lane, m = m0 + rt;
-    if (rt < bm && m < rows) {
-        float mw[WN], sw[WN];
-        int aw[WN];
-#pragma unroll
-        for (int w = 0; w < WN; ++w) {
-            mw[w] = lds_ldf(lds + RowStatLds::MAX + (w * RowStatLds::ROWS + rt) * 4);
-            aw[w] = lds_ldi(lds + RowStatLds::ARG + (w * RowStatLds::ROWS + rt) * 4);
-            sw[w] = lds_ldf(lds + RowStatLds::SUM + (w * RowStatLds::ROWS + rt) * 4);
-        }
-        float mt = mw[0];
-        int at = aw[0];
-#pragma unroll
-        for (int w = 1; w < WN; ++w)
-            if (mw[w] > mt) { mt = mw[w]; at = aw[w]; }   // wave columns ascend: a later equal maximum does not replace
-        const float st = (sw[0] + sw[1]) + (sw[2] + sw[3]);
-        rs.part[(size_t)(n0 / (TN * WN)) * rs.ld + m] = float4{mt, st, __int_as_float(at + rs.col0), 0.f};
-        if constexpr (TOPK) {
-            int at4[WN];
-            uint32_t head[WN], best[TOPK_MAX];
-#pragma unroll
-            for (int w = 0; w < WN; ++w) {
-                at4[w] = lds + RowTopkLds::KEYS + (w * RowStatLds::ROWS + rt) * (TOPK_MAX * 4);
-                head[w] = (uint32_t)lds_ldi(at4[w]);
-            }
-#pragma unroll
-            for (int e = 0; e < TOPK_MAX; ++e) {
-                const uint32_t b = umax32(umax32(head[0], head[1]), umax32(head[2], head[3]));
-                best[e] = b;
-                if (e + 1 < TOPK_MAX) {   // the list that held the winner moves on (b = 0: every list is exhausted, zeros follow)
-#pragma unroll
-                    for (int w = 0; w < WN; ++w) {
-                        at4[w] += head[w] == b ? 4 : 0;
-                        head[w] = (uint32_t)lds_ldi(at4[w]);
-                    }
-                }
-            }
-            u32x4* dst = (u32x4*)(rowtopk_args(g).topk + ((size_t)(n0 / (TN * WN)) * rs.ld + m) * TOPK_MAX);
-            dst[0] = u32x4{best[0], best[1], best[2], best[3]};
-            dst[1] = u32x4{best[4], best[5], best[6], best[7]};
-        }
-        if constexpr (SAMPLE) {
-            float bk = lds_ldf(lds + RowSampleLds::KEY + rt * 4), bx = lds_ldf(lds + RowSampleLds::X + rt * 4);
-            int bc = lds_ldi(lds + RowSampleLds::COL + rt * 4);
-#pragma unroll
-            for (int w = 1; w < WN; ++w) {
-                const int at = (w * RowStatLds::ROWS + rt) * 4;
-                const float ok = lds_ldf(lds + RowSampleLds::KEY + at);
-                if (ok > bk) { bk = ok; bc = lds_ldi(lds + RowSampleLds::COL + at); bx = lds_ldf(lds + RowSampleLds::X + at); }
-            }
-            sa.samp[(size_t)(n0 / (TN * WN)) * rs.ld + m] = float4{bk, __int_as_float(bc + rs.col0), bx, 0.f};
-        }
-    }
-}
-
 // m_lim: first row this tile does NOT write (g.M, or the end of a short row tile of gemm8.hip).
 // Wave grid WM x WN over the block tile, a wave owns TM x TN outputs = FM x FN fragments of 16 x 16:
 //     acc[mi][ni][r] = D[m][n],  m = m0 + wm*TM + mi*16 + (lane>>4)*4 + r,  n = n0 + wn*TN + ni*16 + (lane&15)
 template <int EPI, int TM, int TN, int WN>
 MM_DEVICE void gemm_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim,
-                             int lds = 0, int bm = 0 /* EPI_ROWSTAT, EPI_ROWTOPK, EPI_ROWSAMPLE: free LDS (byte address), rows of the tile */) {
-    if constexpr (EPI == EPI_ROWSTAT) {
-        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<false, TM, TN, WN>(g, m0, n0, acc, wave, lane, m_lim, lds, bm);
-        return;
-    }
-    if constexpr (EPI == EPI_ROWTOPK) {
-        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<false, TM, TN, WN, true>(g, m0, n0, acc, wave, lane, m_lim, lds, bm);
-        return;
-    }
-    if constexpr (EPI == EPI_ROWSAMPLE) {
-        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<false, TM, TN, WN, false, true>(g, m0, n0, acc, wave, lane, m_lim, lds, bm);
+                             int lds = 0, int bm = 0 /* the row heads: free LDS (byte address), rows of the tile */) {
+    if constexpr (is_row_head(EPI)) {   // row_head_epilogue.h
+        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<EPI, false, TM, TN, WN>(g, m0, n0, acc, wave, lane, m_lim, lds, bm);
         return;
     }
     constexpr int FM = TM / 16, FN = TN / 16;
@@ -596,16 +243,8 @@ MM_DEVICE int run8_col(int lq) { return (lq & 1) * 16 + (lq >> 1) * 8; }
 template <int EPI, int TM, int TN, int WN>
 MM_DEVICE void gemm_epilogue_t(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[TM / 16][TN / 16], int wave, int lane, int m_lim,
                                 int lut_lds = -1 /* LDS byte address of the SiLU table, or -1 */) {
-    if constexpr (EPI == EPI_ROWSTAT) {   // the 8-phase kernel owns the LDS from address 0; its main loop is behind a barrier
-        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<true, TM, TN, WN>(g, m0, n0, acc, wave, lane, m_lim, 0, TM * (8 / WN));
-        return;
-    }
-    if constexpr (EPI == EPI_ROWTOPK) {
-        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<true, TM, TN, WN, true>(g, m0, n0, acc, wave, lane, m_lim, 0, TM * (8 / WN));
-        return;
-    }
-    if constexpr (EPI == EPI_ROWSAMPLE) {
-        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<true, TM, TN, WN, false, true>(g, m0, n0, acc, wave, lane, m_lim, 0, TM * (8 / WN));
+    if constexpr (is_row_head(EPI)) {   // row_head_epilogue.h; the 8-phase kernel owns the LDS from address 0; its main loop is behind a barrier
+        if constexpr (TN == 64 && WN == RowStatLds::WAVES) rowstat_epilogue<EPI, true, TM, TN, WN>(g, m0, n0, acc, wave, lane, m_lim, 0, TM * (8 / WN));
         return;
     }
     constexpr int FM = TM / 16, FN = TN / 16;
@@ -827,11 +466,3 @@ MM_DEVICE void gemm_publish(const GemmArgs& g, int wave) {
 }
 
 }  // namespace gemm_detail
-
-// gemm8.hip: the 8-phase kernel.  cfg = one of the GEMM8_* configurations; returns nonzero on a launch error.
-enum Gemm8Cfg { GEMM8_320x256 = 0, GEMM8_256x256 = 1, GEMM8_160x256 = 2, GEMM8_320x128 = 3, GEMM8_NCFG = 4 };
-bool gemm8_supports(const GemmArgs& g);  // shape contract of the 8-phase kernel (K % 128 == 0, K >= 256, M, N % 8 == 0, ...)
-int launch_gemm8(int epi, int cfg, const GemmArgs& g, const Switches& sw, hipStream_t s);  // sw: short row tiles, tile order
-int gemm_plan_code(int M, int N, int K);  // the planner's pick for a plain product: 0..3 or 1000 + BM; -1: unsupported shape
-// allocate + fill the per-device constants of the GEMM launchers now (zero rows, SiLU table) instead of at the first launch
-int gemm_prepare_device();

@@ -81,7 +81,7 @@ struct mmada_handle {
     std::vector<ProfRec> prof;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
     TpComm* tp = nullptr;  // tensor-parallel collective engine (tp_comm.hip; mmada_comm_*)
-    // record buffer of mmada_head_logprobs / mmada_head_topk / mmada_head_sample (kernels.h: head_rowstat_bytes, head_rowtopk_bytes,
+    // record buffer of mmada_head_logprobs / mmada_head_topk / mmada_head_sample (row_heads.h: row_head_layout; head_rowstat_bytes, head_rowtopk_bytes,
     // head_rowsample_bytes), grown at first use, freed with the handle
     void* score_buf = nullptr;
     size_t score_bytes = 0;

@@ -3,6 +3,7 @@
 // (mmada_head_sample, mmada_text_select_sampled; the noise: sample_noise.h).  Host code only.
 #include "../../include/mmada_mi355x.h"
 #include "handle.h"
+#include "row_heads.h"
 #include "sample_noise.h"
 
 int check_head_range(const mmada_handle* h, const char* who, int R, int limit, int col_begin, int col_end) {
@@ -26,17 +27,38 @@ static int store_logits(const mmada_handle* h, const bf16_t* xg, int R, int col_
     return launch_gemm(EPI_STORE, gemm_bt_args(xg, h->lm_head + (size_t)col_begin * d, (bf16_t*)out, R, N, d, N), s);
 }
 
-// the record buffer of mmada_head_logprobs / mmada_head_topk / mmada_head_sample holds at least `need` bytes
-static int grow_score_buffer(mmada_handle* h, size_t need, hipStream_t s) {
+// the record buffer of mmada_head_logprobs / mmada_head_topk / mmada_head_sample (`who`) holds at least `need` bytes
+static int grow_score_buffer(mmada_handle* h, const char* who, size_t need, hipStream_t s) {
     if (need <= h->score_bytes) return 0;
     if (stream_capturing(s))
-        return mm_fail("mmada_head_logprobs: the record buffer must grow (%zu bytes): run the call once outside the capture", need);
+        return mm_fail("%s: the record buffer must grow (%zu bytes): run the call once outside the capture", who, need);
     MM_CHECK_HIP(hipStreamSynchronize(s));   // an earlier call on this stream may still read the old buffer
     (void)hipFree(h->score_buf);
     h->score_buf = nullptr; h->score_bytes = 0;
     MM_CHECK_HIP(hipMalloc(&h->score_buf, need));
     h->score_bytes = need;
     return 0;
+}
+
+// What the three fused heads share.  First: a forward is resident and no required pointer is null ...
+static int fused_head_entry(const mmada_handle* h, const char* who, bool null_argument) {
+    if (!h || !resident(h)) return mm_fail("%s: no forward resident", who);
+    if (null_argument) return mm_fail("%s: null argument", who);
+    return 0;
+}
+// ... then, behind the entry point's own checks: one rank only (`refusal`: the entry point's words for a handle that is not), the
+// range, the record buffer (`bytes`: the head's size function, kernels.h), the same gather as mmada_head_rows (compact stream of a
+// windowed forward; rows outside the window are an error there), and launch(A rows, W rows, N, K), the head's launcher.
+template <class Launch>
+static int fused_head_on_one_rank(mmada_handle* h, const char* who, bool one_rank, const char* refusal, const int32_t* rows, int R,
+                                  int col_begin, int col_end, size_t (*bytes)(int, int), hipStream_t s, Launch launch) {
+    if (!one_rank) return mm_fail("%s", refusal);
+    if (R <= 0) return 0;
+    if (check_head_range(h, who, R, h->res.B * h->res.L, col_begin, col_end)) return 1;
+    const int d = h->cfg.d_model, N = col_end - col_begin;
+    if (grow_score_buffer(h, who, bytes(R, N), s)) return 1;
+    if (gather_resident_rows(h, rows, R, s)) return 1;
+    return launch(h->xg, h->lm_head + (size_t)col_begin * d, N, d);
 }
 
 extern "C" {
@@ -85,23 +107,17 @@ int mmada_head_rows(mmada_handle* h, const int32_t* rows, int R, int col_begin, 
 
 int mmada_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
                         float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out, void* stream) {
-    if (!h || !resident(h)) return mm_fail("mmada_head_logprobs: no forward resident");
-    if (!rows || !targets || !logprob_out) return mm_fail("mmada_head_logprobs: null argument");
-    // a connected handle (also a one-rank group): the vocabulary-parallel head, same records, same fold (tp_heads.hip)
-    if (tp_comm_connected(h))
-        return tp_head_logprobs(h, rows, R, col_begin, col_end, targets, logprob_out, lse_out, argmax_out, max_out, (hipStream_t)stream);
-    if (h->res.xn_is_final || h->cfg.tp_size != 1)
-        return mm_fail("mmada_head_logprobs: a tensor-parallel handle scores through the library's exchange only (mmada_comm_create + "
-                       "mmada_comm_connect_*): a vocabulary-parallel score exchanges the same records as mmada_text_select_tp");
-    if (R <= 0) return 0;
-    if (check_head_range(h, "mmada_head_logprobs", R, h->res.B * h->res.L, col_begin, col_end)) return 1;
+    if (fused_head_entry(h, "mmada_head_logprobs", !rows || !targets || !logprob_out)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    const int d = h->cfg.d_model, N = col_end - col_begin;
-    if (grow_score_buffer(h, head_rowstat_bytes(R, N), s)) return 1;
-    // the same gather as mmada_head_rows (compact stream of a windowed forward; rows outside the window are an error there)
-    if (gather_resident_rows(h, rows, R, s)) return 1;
-    return launch_head_rowstat(h->xg, h->lm_head + (size_t)col_begin * d, R, N, d, col_begin, targets, h->score_buf, logprob_out,
-                               lse_out, argmax_out, max_out, s);
+    // a connected handle (also a one-rank group): the vocabulary-parallel head, same records, same fold (tp_heads.hip)
+    if (tp_comm_connected(h)) return tp_head_logprobs(h, rows, R, col_begin, col_end, targets, logprob_out, lse_out, argmax_out, max_out, s);
+    return fused_head_on_one_rank(
+        h, "mmada_head_logprobs", !h->res.xn_is_final && h->cfg.tp_size == 1,
+        "mmada_head_logprobs: a tensor-parallel handle scores through the library's exchange only (mmada_comm_create + "
+        "mmada_comm_connect_*): a vocabulary-parallel score exchanges the same records as mmada_text_select_tp",
+        rows, R, col_begin, col_end, head_rowstat_bytes, s, [&](const bf16_t* A, const bf16_t* W, int N, int K) {
+            return launch_head_rowstat(A, W, R, N, K, col_begin, targets, h->score_buf, logprob_out, lse_out, argmax_out, max_out, s);
+        });
 }
 
 int mmada_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, int k, int32_t* ids_out,
@@ -109,19 +125,15 @@ int mmada_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, 
     if (k < 1 || k > MMADA_TOPK_MAX) return mm_fail("mmada_head_topk: k=%d outside [1, MMADA_TOPK_MAX=%d]", k, MMADA_TOPK_MAX);
     if ((long long)k > (long long)col_end - col_begin)
         return mm_fail("mmada_head_topk: k=%d exceeds the column range [%d, %d)", k, col_begin, col_end);
-    if (!h || !resident(h)) return mm_fail("mmada_head_topk: no forward resident");
-    if (!rows || !ids_out || !logit_out) return mm_fail("mmada_head_topk: null argument");
-    if (runs_tensor_parallel(h) || h->res.xn_is_final)
-        return mm_fail("mmada_head_topk: top-k runs on one rank (a handle without a tensor-parallel exchange): the vocabulary-parallel "
-                       "top-k, whose key records would ride the score exchange of mmada_head_logprobs, is a follow-up");
-    if (R <= 0) return 0;
-    if (check_head_range(h, "mmada_head_topk", R, h->res.B * h->res.L, col_begin, col_end)) return 1;
+    if (fused_head_entry(h, "mmada_head_topk", !rows || !ids_out || !logit_out)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    const int d = h->cfg.d_model, N = col_end - col_begin;
-    if (grow_score_buffer(h, head_rowtopk_bytes(R, N), s)) return 1;
-    if (gather_resident_rows(h, rows, R, s)) return 1;
-    return launch_head_rowtopk(h->xg, h->lm_head + (size_t)col_begin * d, R, N, d, col_begin, k, h->score_buf, ids_out, logit_out,
-                               lse_out, s);
+    return fused_head_on_one_rank(
+        h, "mmada_head_topk", !runs_tensor_parallel(h) && !h->res.xn_is_final,
+        "mmada_head_topk: top-k runs on one rank (a handle without a tensor-parallel exchange): the vocabulary-parallel "
+        "top-k, whose key records would ride the score exchange of mmada_head_logprobs, is a follow-up",
+        rows, R, col_begin, col_end, head_rowtopk_bytes, s, [&](const bf16_t* A, const bf16_t* W, int N, int K) {
+            return launch_head_rowtopk(A, W, R, N, K, col_begin, k, h->score_buf, ids_out, logit_out, lse_out, s);
+        });
 }
 
 unsigned mmada_topk_order_key(unsigned bf16_bits) { return topk_order(__builtin_bit_cast(float, (uint32_t)(bf16_bits & 0xffffu) << 16)) >> 16; }
@@ -129,21 +141,18 @@ unsigned mmada_topk_order_key(unsigned bf16_bits) { return topk_order(__builtin_
 int mmada_head_sample(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, float temperature, uint64_t seed,
                       uint64_t* counter, int32_t* ids_out, float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out,
                       void* stream) {
-    if (!h || !resident(h)) return mm_fail("mmada_head_sample: no forward resident");
-    if (!rows || !counter || !ids_out || !logprob_out) return mm_fail("mmada_head_sample: null argument");
+    if (fused_head_entry(h, "mmada_head_sample", !rows || !counter || !ids_out || !logprob_out)) return 1;
     if (!(temperature >= 0.f) || __builtin_isinf(temperature))
         return mm_fail("mmada_head_sample: temperature %g is not a finite value >= 0", (double)temperature);
-    if (runs_tensor_parallel(h) || h->res.xn_is_final)
-        return mm_fail("mmada_head_sample: the draw runs on one rank (a handle without a tensor-parallel exchange): the "
-                       "vocabulary-parallel draw, whose key records would ride the score exchange of mmada_head_logprobs, is a follow-up");
-    if (R <= 0) return 0;
-    if (check_head_range(h, "mmada_head_sample", R, h->res.B * h->res.L, col_begin, col_end)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    const int d = h->cfg.d_model, N = col_end - col_begin;
-    if (grow_score_buffer(h, head_rowsample_bytes(R, N), s)) return 1;
-    if (gather_resident_rows(h, rows, R, s)) return 1;
-    return launch_head_rowsample(h->xg, h->lm_head + (size_t)col_begin * d, R, N, d, col_begin, temperature, seed, counter, h->score_buf,
-                                 ids_out, logprob_out, lse_out, argmax_out, max_out, s);
+    return fused_head_on_one_rank(
+        h, "mmada_head_sample", !runs_tensor_parallel(h) && !h->res.xn_is_final,
+        "mmada_head_sample: the draw runs on one rank (a handle without a tensor-parallel exchange): the "
+        "vocabulary-parallel draw, whose key records would ride the score exchange of mmada_head_logprobs, is a follow-up",
+        rows, R, col_begin, col_end, head_rowsample_bytes, s, [&](const bf16_t* A, const bf16_t* W, int N, int K) {
+            return launch_head_rowsample(A, W, R, N, K, col_begin, temperature, seed, counter, h->score_buf, ids_out, logprob_out, lse_out,
+                                         argmax_out, max_out, s);
+        });
 }
 
 // The text step with the draw above (generators/parallel_generator.py:181-217, low-confidence re-masking).  scratch is the layout

@@ -47,88 +47,6 @@ struct GemmArgs {
     int tile_gm, tile_gn;  // set by gemm8's launcher only: tile-order groups of tile_gm row tiles (0: all) x tile_gn column tiles
 };
 
-int launch_gemm(int epi, const GemmArgs& g, hipStream_t s);
-
-// EPI_ROWSTAT (the scoring head, launch_head_rowstat).  Nothing of C is stored.  Per row m < rows and 256-column tile nt ONE
-// record part[nt * ld + m] = {max, sum exp(x - max), first column of the max in the whole vocabulary (int bits), 0} over the
-// bf16-rounded logits x of that tile, and the logit at column target[m] - col0 (if that is a column of this launch) to tx[m].
-// M may be `rows` rounded up to 8 (pad rows of A hold anything; their results are dropped).
-// Its arguments travel in GemmArgs fields the epilogue has no other use for (C, resid, pos_map; rwin, rlp, rbeg), so that the
-// argument block every GEMM kernel takes keeps its layout and no other kernel's compiled code changes.
-struct RowStatArgs {
-    float4* part;            // [ceil(N / 256)][ld] records
-    float* tx;               // [ld] target logits, preset to -inf by the launcher
-    const int64_t* target;   // [rows] column in the whole vocabulary, or negative: none
-    int rows, ld, col0;
-};
-static inline __host__ __device__ RowStatArgs rowstat_args(const GemmArgs& g) {
-    return RowStatArgs{(float4*)g.C, (float*)g.resid, (const int64_t*)g.pos_map, g.rwin, g.rlp, g.rbeg};
-}
-static inline void set_rowstat_args(GemmArgs& g, const RowStatArgs& r) {
-    g.C = (bf16_t*)r.part; g.resid = (const bf16_t*)r.tx; g.pos_map = (const int32_t*)r.target;
-    g.ldc = 8; g.ldr = 8;   // (the 8-phase kernel's shape contract looks at them)
-    g.rwin = r.rows; g.rlp = r.ld; g.rbeg = r.col0;
-}
-
-// EPI_ROWTOPK (the top-k head, launch_head_rowtopk): a superset of EPI_ROWSTAT.  The same 16-byte record with the same bits (and
-// the target logit, where `target` is not null — null: no row has one), plus per row and 256-column tile ONE 32-byte record
-// topk[(nt * ld + m) * 8 .. + 8): the tile's eight best logits as 32-bit keys in descending order (= logit descending, then
-// column ascending).  A key (topk_key below): high half = the bf16 bits of the logit mapped to an unsigned value of the same order,
-// low byte = 255 - column inside the tile; an unsigned compare is the whole order and the keys of a tile are distinct.  Places
-// beyond the tile's columns (N - 256 * nt < 8) hold 0, below every real key.  The extra pointer travels in GemmArgs::q.
-struct RowTopkArgs {
-    RowStatArgs rs;
-    uint32_t* topk;          // [ceil(N / 256)][ld][8] keys
-};
-static inline __host__ __device__ RowTopkArgs rowtopk_args(const GemmArgs& g) { return RowTopkArgs{rowstat_args(g), (uint32_t*)g.q}; }
-static inline void set_rowtopk_args(GemmArgs& g, const RowTopkArgs& r) {
-    set_rowstat_args(g, r.rs);
-    g.q = (bf16_t*)r.topk;
-}
-constexpr int TOPK_MAX = 8;   // = MMADA_TOPK_MAX (include/mmada_mi355x.h); entries of a tile's record
-// Order value of a bf16-rounded logit x (an fp32 whose low 16 bits are zero), in the HIGH half of the result: negatives with all
-// bits flipped, the rest with the sign bit flipped, so that an unsigned compare orders as the floats do.  -0.0 is taken as +0.0
-// first (x + 0.0f): torch's sort compares floats, for which the two are equal and the lower column wins.  NaN: outside the contract.
-static inline __host__ __device__ uint32_t topk_order(float x) {
-    const float c = x + 0.0f;
-    uint32_t u;
-    __builtin_memcpy(&u, &c, 4);
-    return u ^ ((uint32_t)((int32_t)u >> 31) & 0x7fff0000u) ^ 0x80000000u;
-}
-static inline __host__ __device__ uint32_t topk_key(float x, int col_in_tile) { return (topk_order(x) & 0xffff0000u) | (uint32_t)(255 - col_in_tile); }
-static inline __host__ __device__ float topk_key_logit(uint32_t key) {   // inverse of topk_order on the key's high half
-    const uint32_t o = key & 0xffff0000u, u = (o & 0x80000000u) ? o ^ 0x80000000u : o ^ 0xffff0000u;
-    float x;
-    __builtin_memcpy(&x, &u, 4);
-    return x;
-}
-
-// EPI_ROWSAMPLE (the sampling head, launch_head_rowsample): a superset of EPI_ROWSTAT, built like EPI_ROWTOPK.  The same 16-byte
-// record with the same bits (no row has a target), plus per row and 256-column tile ONE 16-byte record
-// samp[nt * ld + m] = {max key, its column in the whole vocabulary (int bits), the bf16 logit at that column as fp32, 0} —
-// key = x + T * g(seed, *counter, row m, column in the whole vocabulary) (sample_noise.h); highest key, then lowest column.
-// Columns beyond N carry the key -inf.  The extra arguments travel in GemmArgs fields of the QKV epilogue: q (records),
-// k (counter: one scalar load per wave), Hq / Hkv (seed, low / high half), Lq (bits of T).
-struct RowSampleArgs {
-    RowStatArgs rs;
-    float4* samp;              // [ceil(N / 256)][ld] records
-    const uint64_t* counter;   // device [1]
-    uint64_t seed;
-    float temperature;         // finite, T >= 0
-};
-static inline __host__ __device__ RowSampleArgs rowsample_args(const GemmArgs& g) {
-    float t;
-    __builtin_memcpy(&t, &g.Lq, 4);
-    return RowSampleArgs{rowstat_args(g), (float4*)g.q, (const uint64_t*)g.k, (uint64_t)(uint32_t)g.Hq | ((uint64_t)(uint32_t)g.Hkv << 32), t};
-}
-static inline void set_rowsample_args(GemmArgs& g, const RowSampleArgs& r) {
-    set_rowstat_args(g, r.rs);
-    g.q = (bf16_t*)r.samp;
-    g.k = (bf16_t*)r.counter;
-    g.Hq = (int)(uint32_t)r.seed; g.Hkv = (int)(uint32_t)(r.seed >> 32);
-    __builtin_memcpy(&g.Lq, &r.temperature, 4);
-}
-
 // A plain C[M, ldc] = A[M, K] · W[N, K]^T on K-contiguous operands (lda = ldw = K), epilogue fields left zero.
 static inline GemmArgs gemm_bt_args(const bf16_t* A, const bf16_t* W, bf16_t* C, int M, int N, int K, int ldc) {
     GemmArgs g{};
@@ -146,24 +64,36 @@ struct Switches {
 };
 Switches switches();
 
-// gemm.hip: the scoring head.  A [ceil8(R), K] (rows >= R: anything), W = lm_head rows [col0, col0 + N).  `part` holds
-// head_rowstat_bytes(R, N) bytes.  Outputs [R] (lse / argmax / max may be null): logprob = x_target - lse (0 for a negative
-// target, -inf for a target outside [col0, col0 + N)), argmax = column index in the WHOLE vocabulary (first maximum).
+// gemm.hip: the launcher of every epilogue (it picks the kernel and the tile), the planner and the per-device constants.
+// EPI_ROWSTAT, EPI_ROWTOPK, EPI_ROWSAMPLE are the row heads of the LM head: nothing of C is stored, and their arguments travel in
+// GemmArgs fields these epilogues have no other use for (row_heads.h: RowHeadArgs, the records, the record buffer's layout).
+// gemm8.hip: the 8-phase kernel, cfg = one of the GEMM8_* configurations; returns nonzero on a launch error.
+int launch_gemm(int epi, const GemmArgs& g, hipStream_t s);
+enum Gemm8Cfg { GEMM8_320x256 = 0, GEMM8_256x256 = 1, GEMM8_160x256 = 2, GEMM8_320x128 = 3, GEMM8_NCFG = 4 };
+bool gemm8_supports(const GemmArgs& g);  // shape contract of the 8-phase kernel (K % 128 == 0, K >= 256, M, N % 8 == 0, ...)
+int launch_gemm8(int epi, int cfg, const GemmArgs& g, const Switches& sw, hipStream_t s);  // sw: short row tiles, tile order
+int gemm_plan_code(int M, int N, int K);  // the planner's pick for a plain product: 0..3 or 1000 + BM; -1: unsupported shape
+// allocate + fill the per-device constants of the GEMM launchers now (zero rows, SiLU table) instead of at the first launch
+int gemm_prepare_device();
+
+// row_heads.hip: the scoring head.  A [ceil8(R), K] (rows >= R: anything), W = lm_head rows [col0, col0 + N).  `part` holds
+// head_rowstat_bytes(R, N) bytes (row_heads.h: row_head_layout).  Outputs [R] (lse / argmax / max may be null): logprob =
+// x_target - lse (0 for a negative target, -inf for a target outside [col0, col0 + N)), argmax = column index in the WHOLE
+// vocabulary (first maximum).
 size_t head_rowstat_bytes(int R, int N);
 int launch_head_rowstat(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, const int64_t* targets, void* part,
                         float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s);
 
-// gemm.hip: the top-k head.  Same operands; `part` holds head_rowtopk_bytes(R, N) bytes: the row-statistics records, ceil8(R)
-// floats, then the 32-byte key records (kernels.h: RowTopkArgs).  ids [R, k] (column in the whole vocabulary) and logits [R, k] in
-// the order logit descending, column ascending; lse [R] or null: the bits launch_head_rowstat returns.  1 <= k <= TOPK_MAX, k <= N.
+// row_heads.hip: the top-k head.  Same operands; `part` holds head_rowtopk_bytes(R, N) bytes.  ids [R, k] (column in the whole
+// vocabulary) and logits [R, k] in the order logit descending, column ascending; lse [R] or null: the bits launch_head_rowstat
+// returns.  1 <= k <= TOPK_MAX, k <= N.
 size_t head_rowtopk_bytes(int R, int N);
 int launch_head_rowtopk(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, int k, void* part, int32_t* ids,
                         float* logits, float* lse, hipStream_t s);
 
-// gemm.hip: the sampling head.  Same operands; `part` holds head_rowsample_bytes(R, N) bytes: the row-statistics records, ceil8(R)
-// floats, then the 16-byte key records (kernels.h: RowSampleArgs).  ids [R]: arg-max of the key, column in the whole vocabulary;
-// logprob [R] = x_drawn - lse; lse / argmax / vmax [R] or null: the bits launch_head_rowstat returns.  *counter is read by the
-// GEMM's workgroups and incremented by the joining kernel, the last of the call.
+// row_heads.hip: the sampling head.  Same operands; `part` holds head_rowsample_bytes(R, N) bytes.  ids [R]: arg-max of the key,
+// column in the whole vocabulary; logprob [R] = x_drawn - lse; lse / argmax / vmax [R] or null: the bits launch_head_rowstat
+// returns.  *counter is read by the GEMM's workgroups and incremented by the joining kernel, the last of the call.
 size_t head_rowsample_bytes(int R, int N);
 int launch_head_rowsample(const bf16_t* A, const bf16_t* W, int R, int N, int K, int col0, float temperature, uint64_t seed,
                           uint64_t* counter, void* part, int32_t* ids, float* logprob, float* lse, int32_t* argmax, float* vmax,

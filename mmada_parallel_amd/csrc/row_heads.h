@@ -1,0 +1,163 @@
+// row_heads.h — the contract of the LM head's row heads (host and device): what the launchers (row_heads.hip, tp_heads.hip), the
+// GEMM epilogue (row_head_epilogue.h) and the joining kernels must agree on.  Nothing of D = A · lm_head[col0 : col0 + N]^T is
+// stored: per row m < rows and 256-column tile nt the GEMM leaves records over the bf16-rounded logits x of that tile.
+//   EPI_ROWSTAT   (scoring, mmada_head_logprobs)  part[nt * ld + m] = {max, sum exp(x - max), first column of the max in the whole
+//                 vocabulary (int bits), 0}, and the logit at column target[m] - col0 (if that is a column of the launch) to tx[m].
+//   EPI_ROWTOPK   (top-k, mmada_head_topk)        the same record with the same bits (and the target logit where `target` is not
+//                 null — null: no row has one), plus extra[(nt * ld + m) * 8 .. + 8): the tile's eight best logits as 32-bit keys
+//                 (topk_key below) in descending order = logit descending, then column ascending.  Places beyond the tile's columns
+//                 (N - 256 * nt < 8) hold 0, below every real key.
+//   EPI_ROWSAMPLE (Gumbel-max draw, mmada_head_sample)  the same record with the same bits (no row has a target), plus
+//                 extra[nt * ld + m] = {max key, its column in the whole vocabulary (int bits), the bf16 logit at that column as
+//                 fp32, 0} — key = x + T * g(seed, *counter, row m, column in the whole vocabulary) (sample_noise.h); highest key,
+//                 then lowest column.  Columns beyond N carry the key -inf.
+// M may be `rows` rounded up to 8 (pad rows of A hold anything; their results are dropped).
+#pragma once
+#include "kernels.h"
+
+constexpr bool is_row_head(int epi) { return epi == EPI_ROWSTAT || epi == EPI_ROWTOPK || epi == EPI_ROWSAMPLE; }
+
+constexpr int ROW_HEAD_BN = 256;   // columns per record: one column tile of either GEMM kernel
+constexpr int TOPK_MAX = 8;        // = MMADA_TOPK_MAX (include/mmada_mi355x.h); entries of a tile's key record
+
+// ---- the argument block.  It travels in GemmArgs fields the row-head epilogue has no other use for, so that the argument block
+// every GEMM kernel takes keeps its layout and no other kernel's compiled code changes.  THE aliasing, the only statement of it:
+//     part -> C        tx -> resid      target -> pos_map      rows -> rwin      ld -> rlp      col0 -> rbeg
+//     extra -> q       counter -> k     seed -> Hq (low half), Hkv (high half)   temperature -> Lq (its bits)
+// (ldc = ldr = 8: the 8-phase kernel's shape contract looks at them.)  A head that has no use for a field leaves it zero.
+struct RowHeadArgs {
+    float4* part;              // [ceil(N / 256)][ld] records
+    float* tx;                 // [ld] target logits; -inf where no lane holds the target (preset by the launcher)
+    const int64_t* target;     // [rows] column in the whole vocabulary, or negative: none.  Null (top-k, sample): no row has one
+    int rows, ld, col0;
+    void* extra;               // EPI_ROWTOPK: uint32_t [ceil(N / 256)][ld][8] keys; EPI_ROWSAMPLE: float4 [ceil(N / 256)][ld]
+    const uint64_t* counter;   // EPI_ROWSAMPLE: device [1], one scalar load per wave
+    uint64_t seed;             // EPI_ROWSAMPLE
+    float temperature;         // EPI_ROWSAMPLE: finite, T >= 0
+};
+static inline __host__ __device__ RowHeadArgs row_head_args(const GemmArgs& g) {
+    float t;
+    __builtin_memcpy(&t, &g.Lq, 4);
+    return RowHeadArgs{(float4*)g.C, (float*)g.resid, (const int64_t*)g.pos_map, g.rwin, g.rlp, g.rbeg, (void*)g.q, (const uint64_t*)g.k,
+                       (uint64_t)(uint32_t)g.Hq | ((uint64_t)(uint32_t)g.Hkv << 32), t};
+}
+static inline void set_row_head_args(GemmArgs& g, const RowHeadArgs& a) {
+    g.C = (bf16_t*)a.part; g.resid = (const bf16_t*)a.tx; g.pos_map = (const int32_t*)a.target;
+    g.ldc = 8; g.ldr = 8;
+    g.rwin = a.rows; g.rlp = a.ld; g.rbeg = a.col0;
+    g.q = (bf16_t*)a.extra;
+    g.k = (bf16_t*)a.counter;
+    g.Hq = (int)(uint32_t)a.seed; g.Hkv = (int)(uint32_t)(a.seed >> 32);
+    __builtin_memcpy(&g.Lq, &a.temperature, 4);
+}
+// What launch_gemm refuses: the message, or null when the block is complete for `head` (M: rows of the GEMM)
+static inline const char* row_head_args_fault(int head, const RowHeadArgs& a, int M) {
+    const bool sample = head == EPI_ROWSAMPLE;
+    const bool missing = !a.part || !a.tx || (head == EPI_ROWSTAT ? !a.target : !a.extra) || (sample && !a.counter);
+    const bool bad_t = sample && (!(a.temperature >= 0.f) || __builtin_isinf(a.temperature));
+    if (!missing && a.rows > 0 && a.rows <= M && a.ld >= a.rows && !bad_t) return nullptr;
+    return head == EPI_ROWSTAT   ? "gemm/rowstat: record buffers missing"
+           : head == EPI_ROWTOPK ? "gemm/rowtopk: record buffers missing"
+                                 : "gemm/rowsample: record buffers or counter missing, or a temperature that is not finite and >= 0";
+}
+
+// ---- the record buffer of a one-rank launch: records | target logits | extra records.  Per row 1/32 (scoring), 3/32 (top-k) or
+// 1/16 (sample) of the bytes of the bf16 logits it stands for, plus 4 bytes.  (The tensor-parallel score exchange publishes its
+// records in a layout of its own: tp_comm.h, ScoreLayout.)
+struct RowHeadLayout {
+    int rp, ntn;                   // rows rounded up to 8 (the records' leading dimension), 256-column tiles
+    size_t part, tx, extra, bytes; // byte offsets of the three sub-buffers, total size
+};
+static inline RowHeadLayout row_head_layout(int R, int N, int head) {
+    RowHeadLayout l;
+    l.rp = (R + 7) / 8 * 8;
+    l.ntn = (N + ROW_HEAD_BN - 1) / ROW_HEAD_BN;
+    const size_t recs = (size_t)l.rp * l.ntn;
+    const size_t extra_rec = head == EPI_ROWTOPK ? TOPK_MAX * sizeof(uint32_t) : head == EPI_ROWSAMPLE ? sizeof(float4) : 0;
+    l.part = 0;
+    l.tx = recs * sizeof(float4);
+    l.extra = l.tx + (size_t)l.rp * sizeof(float);
+    l.bytes = l.extra + recs * extra_rec;
+    return l;
+}
+
+// ---- the key of the top-k head: high half = the bf16 bits of the logit mapped to an unsigned value of the same order, low byte =
+// 255 - column inside the tile; an unsigned compare is the whole order and the keys of a tile are distinct.
+// Order value of a bf16-rounded logit x (an fp32 whose low 16 bits are zero), in the HIGH half of the result: negatives with all
+// bits flipped, the rest with the sign bit flipped, so that an unsigned compare orders as the floats do.  -0.0 is taken as +0.0
+// first (x + 0.0f): torch's sort compares floats, for which the two are equal and the lower column wins.  NaN: outside the contract.
+static inline __host__ __device__ uint32_t topk_order(float x) {
+    const float c = x + 0.0f;
+    uint32_t u;
+    __builtin_memcpy(&u, &c, 4);
+    return u ^ ((uint32_t)((int32_t)u >> 31) & 0x7fff0000u) ^ 0x80000000u;
+}
+static inline __host__ __device__ uint32_t topk_key(float x, int col_in_tile) { return (topk_order(x) & 0xffff0000u) | (uint32_t)(255 - col_in_tile); }
+static inline __host__ __device__ float topk_key_logit(uint32_t key) {   // inverse of topk_order on the key's high half
+    const uint32_t o = key & 0xffff0000u, u = (o & 0x80000000u) ? o ^ 0x80000000u : o ^ 0xffff0000u;
+    float x;
+    __builtin_memcpy(&x, &u, 4);
+    return x;
+}
+
+// ---- the order of the sampling head's triples {key, column, logit}: highest key, then lowest column
+MM_DEVICE void rowsample_take(float& k, int& c, float& x, float ok, int oc, float ox) {
+    if (ok > k || (ok == k && oc < c)) { k = ok; c = oc; x = ox; }
+}
+
+// ---- the one fold of a row's column-tile records into {max, sum exp(x - max), first arg-max}, shared by the one-rank joins
+// (row_heads.hip) and the tensor-parallel join (tp_heads.hip: tp_score_join_kernel), so that they cannot drift apart: the order
+// below IS the result's definition.
+// Joins the column-tile records of a row in a FIXED order (so that neither the tile order of the GEMM nor its configuration
+// nor the rank that produced a tile shows in the result): 16 rows x 16 tile groups per workgroup; group j folds tiles j, j + 16,
+// ... in ascending order (online soft-max: rescale by exp(m_tile - m_row)), then thread (row, 0) folds the 16 groups in ascending
+// order.
+constexpr int RS_ROWS = 16, RS_GROUPS = 16;
+
+// Called by every thread of a workgroup of RS_ROWS * RS_GROUPS threads (thread = (row rl, group j), row = blockIdx.x * RS_ROWS + rl).
+// fetch(t, row) -> float4 record of tile t.  Returns true on the one thread per row (< R) that holds the row's result.
+template <class Fetch>
+MM_DEVICE bool rowstat_fold(Fetch fetch, int row, int R, int ntn, float& m, float& sum, int& arg) {
+    __shared__ float sm[RS_GROUPS][RS_ROWS], ss[RS_GROUPS][RS_ROWS];
+    __shared__ int sa[RS_GROUPS][RS_ROWS];
+    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
+    m = -__builtin_inff(); sum = 0.f;
+    arg = 0x7fffffff;
+    if (row < R)
+        for (int t = j; t < ntn; t += RS_GROUPS) {
+            const float4 p = fetch(t, row);
+            const int a = __float_as_int(p.z);
+            if (p.x > m) {   // tiles ascend inside a group: an equal maximum further right does not replace
+                sum = sum * expf(m - p.x) + p.y;
+                m = p.x;
+                arg = a;
+            } else
+                sum += p.y * expf(p.x - m);
+        }
+    sm[j][rl] = m; ss[j][rl] = sum; sa[j][rl] = arg;
+    __syncthreads();
+    if (j != 0 || row >= R) return false;
+    for (int q = 1; q < RS_GROUPS; ++q) {
+        const float mq = sm[q][rl], sq = ss[q][rl];
+        const int aq = sa[q][rl];
+        if (mq > m) {
+            sum = sum * expf(m - mq) + sq;
+            m = mq;
+            arg = aq;
+        } else if (mq > -__builtin_inff()) {
+            sum += sq * expf(mq - m);
+            if (mq == m && aq < arg) arg = aq;   // groups interleave the tiles: the leftmost column wins
+        }
+    }
+    return true;
+}
+
+// The row's outputs from its fold and its target logit tx (-inf: the target is no column of the range)
+MM_DEVICE void rowstat_finish(int row, float m, float sum, int arg, long long target, float tx, float* logprob, float* lse_out,
+                              int32_t* argmax_out, float* max_out) {
+    const float lse = m + logf(sum);
+    logprob[row] = target < 0 ? 0.f : tx - lse;
+    if (lse_out) lse_out[row] = lse;
+    if (argmax_out) argmax_out[row] = arg;
+    if (max_out) max_out[row] = m;
+}

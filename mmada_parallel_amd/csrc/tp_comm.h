@@ -9,7 +9,7 @@
 constexpr int TP_MAX = 8;
 constexpr int STAT_ROWS = 16384;   // text rows (B*T) a vocabulary-parallel select can take
 constexpr int SCORE_ROUND = 1280;  // rows per round of the vocabulary-parallel scoring head: whole 320 / 256 / 160 / 128-row GEMM tiles
-constexpr int SCORE_BN = 256;      // columns per record of EPI_ROWSTAT (kernels.h)
+constexpr int SCORE_BN = 256;      // columns per record of EPI_ROWSTAT (row_heads.h: ROW_HEAD_BN)
 
 // The values of the public header (mmada_comm_status / mmada_comm_set_mode) and of tp_link.py.
 enum TpMode {

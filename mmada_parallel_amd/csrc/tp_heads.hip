@@ -1,7 +1,9 @@
 // tp_heads.hip — the LM head under tensor parallelism, on the transports of tp_comm.hip: the row gather in front of every head,
 // the vocabulary-parallel text head (mmada_text_select_tp) and the vocabulary-parallel scoring head (tp_head_logprobs).
-#include "rowstat_fold.h"
+#include "row_heads.h"
 #include "tp_comm.h"
+
+static_assert(SCORE_BN == ROW_HEAD_BN, "the published score records are the one-rank launch's, tile for tile");
 
 namespace {
 
@@ -73,8 +75,8 @@ struct ScoreJoinArgs {
     float* vmax;
 };
 
-// The join of rowstat_combine_kernel (gemm.hip) with tile t's record taken from the rank that owns t: the same fold
-// (rowstat_fold.h), so every rank — and a one-rank handle — ends with the same bits.  Every rank joins every row.
+// The join of rowstat_combine_kernel (row_heads.hip) with tile t's record taken from the rank that owns t: the same fold
+// (row_heads.h: rowstat_fold), so every rank — and a one-rank handle — ends with the same bits.  Every rank joins every row.
 __global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_score_join_kernel(ScoreJoinArgs a) {
     if (a.sys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // see tp_reduce_norm_kernel
     const int row = blockIdx.x * RS_ROWS + threadIdx.x % RS_ROWS;
@@ -216,7 +218,10 @@ int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin,
         MM_CHECK_HIP(hipGetLastError());
         if (n_own > 0) {
             GemmArgs g = gemm_bt_args(h->xg + (size_t)r0 * d, h->lm_head + (size_t)c0 * d, nullptr, rp, n_own, d, 8);
-            set_rowstat_args(g, RowStatArgs{(float4*)(buf + lay.rec_off), tx, targets + r0, rr, rp, c0});
+            RowHeadArgs ra{};
+            ra.part = (float4*)(buf + lay.rec_off); ra.tx = tx; ra.target = targets + r0;
+            ra.rows = rr; ra.ld = rp; ra.col0 = c0;
+            set_row_head_args(g, ra);
             g.publish = mapped;
             if (launch_gemm(EPI_ROWSTAT, g, s)) return 1;
         }
