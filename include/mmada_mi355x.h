@@ -187,6 +187,18 @@ float mmada_sample_uniform(uint32_t word);
  * [R * N] output takes the word (col0 + i) << 9, so col0 = 0 and R * N = 2^23 enumerate every value of u in ascending order. */
 int mmada_probe_gumbel(uint64_t seed, uint64_t counter, int row0, int R, int col0, int N, uint32_t* words_out, float* g_out,
                        void* stream);
+/* The re-mask noise of the image step (mmada_image_commit_sampled; replaces torch.randn, generators/parallel_generator.py:30-33):
+ * a standard-normal value per image position r = b*N + n, a pure function of (seed, counter, r).
+ *   (word0, word1) = words 0 and 1 of Philox4x32-10 on the counter block (0, r, counter low, counter high) with the key
+ *   seed ^ 0x5851F42D4C957F2D (low, high) — a different key from the token draw's, so the two streams never share a block;
+ *   z = sqrtf(-2 logf(u(word0))) * cosf(2 pi u(word1)) in fp32 without FMA, u as above; |z| <= sqrt(48 ln 2) ~ 5.77.
+ * The commit uses z rounded to bf16 (the reference's randn is bf16, :30-36).  mmada_sample_normal: the fp32 z on the host (no
+ * device is touched; the code the kernels compile, with the host's logf / cosf).  mmada_probe_normal, tests only: the device's
+ * values of rows row0 .. row0 + R - 1: words01_out device [R, 2], z_out device fp32 [R], z_bf16_out device bf16 [R], each or
+ * NULL (not all three). */
+float mmada_sample_normal(uint64_t seed, uint64_t counter, uint32_t r);
+int mmada_probe_normal(uint64_t seed, uint64_t counter, int row0, int R, uint32_t* words01_out, float* z_out, uint16_t* z_bf16_out,
+                       void* stream);
 
 /* Declare which residual-stream rows the caller will read after the forwards that follow: only l in
  * [row_begin, row_end) of every sequence (e.g. the image + text span of generate_ti2ti; the prompt and the input image
@@ -301,6 +313,33 @@ int mmada_image_probs(mmada_handle* h, const void* cond, const void* unc_text, c
 int mmada_image_commit(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
                        const int32_t* sampled_in, const void* p_in, const void* noise, float remask_temp,
                        const int32_t* mask_len_sched, int text_vocab_size, int codebook_size, void* stream);
+
+/* Image step with both draws on the device: no probabilities, no torch random tensor, no by-value argument that changes from step
+ * to step — a captured step replays (generate_ti2ti(image_sampler="device")).
+ *
+ * mmada_image_sample replaces part 1 at temperature > 0, generators/parallel_generator.py:282-302,311 (CFG combine, softmax,
+ * torch.multinomial, gather): the combine and soft-max statistics of mmada_image_probs bit for bit, and
+ *   sampled_out[b,n] = first-index arg-max over i < CB of  fadd_rn(l_i, g(seed, *counter, r, col0 + i)),  r = b*N + n,
+ * l_i the combined bf16 logit as fp32, g the Gumbel value of mmada_head_sample at temperature 1 (highest key wins, lowest column on
+ * equal keys).  col0: the column of codebook entry 0 in the WHOLE vocabulary (text_vocab_size; any value >= 0), so the draw is the
+ * one mmada_head_sample makes on the same logits.  The draw samples softmax(l) evaluated in fp32; the reference's multinomial
+ * samples the bf16-ROUNDED probabilities, a slightly different law (and another RNG stream).  As in the reference (:292-302) the
+ * image logits are not divided by the temperature.
+ * p_sel_out: bf16 device [B,N] = bf16(e_sampled / sum), exactly what mmada_image_probs writes to probs[b,n,sampled].
+ * argmax_out / pmax_out: NULL or the outputs of mmada_image_probs, same bits.  counter: device uint64 [1], read, never written.
+ * CB % 8 == 0, CB <= 16384, col0 >= 0; B*N <= 0 returns 0.
+ *
+ * mmada_image_commit_sampled replaces part 2, :221-233,304-344 + mask_by_random_topk :23-70 with its torch.randn (:30-33):
+ * mmada_image_commit with noise[b,n] = bf16(z(seed, *counter, b*N + n)) (mmada_sample_normal) computed in the kernel and the
+ * re-mask temperature read from remask_temp (device fp32 [1]).  *counter is read by every workgroup and incremented by 1 by the
+ * call's last kernel, so the next step — or the next replay — draws fresh noise. */
+int mmada_image_sample(mmada_handle* h, const void* cond, const void* unc_text, const void* unc_img, int B, int N, int CB,
+                       float cfg_scale, float cfg_img, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out,
+                       void* p_sel_out, int32_t* argmax_out, void* pmax_out, void* stream);
+int mmada_image_commit_sampled(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
+                               const int32_t* sampled_in, const void* p_in, const float* remask_temp, uint64_t seed,
+                               uint64_t* counter, const int32_t* mask_len_sched, int text_vocab_size, int codebook_size,
+                               void* stream);
 
 /* ---- (M variant) sampler math of MMadaModelLM.interleave_generate, MMaDA-Parallel-M/models/modeling_mmada.py:117-248 --
  * Text step (:179-207): logits = cond + text_cfg * (uncond - cond) with bf16 rounding per op, then exactly

@@ -51,6 +51,8 @@ SIGNATURES = {
     "mmada_sample_word": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
     "mmada_sample_uniform": (c_float, [C.c_uint32]),
     "mmada_probe_gumbel": (c_int, [C.c_uint64, C.c_uint64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "mmada_sample_normal": (c_float, [C.c_uint64, C.c_uint64, C.c_uint32]),
+    "mmada_probe_normal": (c_int, [C.c_uint64, C.c_uint64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mmada_cache_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "mmada_cache_bind": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "mmada_forward_cached": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -71,6 +73,10 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "mmada_image_commit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                    c_float, c_void_p, c_int, c_int, c_void_p]),
+    "mmada_image_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int,
+                                   C.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mmada_image_commit_sampled": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           C.c_uint64, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "mmada_text_select_cfg": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                       c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mmada_image_probs_m": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,

@@ -299,6 +299,25 @@ int mmada_image_commit(mmada_handle* h, int64_t* ids, int B, int L, const int32_
                                mask_len_sched, h->cfg.mask_token_id, text_vocab_size, codebook_size, 0, (hipStream_t)stream);
 }
 
+int mmada_image_sample(mmada_handle* h, const void* cond, const void* unc_text, const void* unc_img, int B, int N, int CB,
+                       float cfg_scale, float cfg_img, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out,
+                       void* p_sel_out, int32_t* argmax_out, void* pmax_out, void* stream) {
+    if (!h || !cond || !counter || !sampled_out || !p_sel_out) return mm_fail("mmada_image_sample: null argument");
+    return launch_image_sample((const bf16_t*)cond, (const bf16_t*)unc_text, (const bf16_t*)unc_img, B, N, CB, cfg_scale, cfg_img,
+                               col0, seed, counter, sampled_out, (bf16_t*)p_sel_out, argmax_out, (bf16_t*)pmax_out,
+                               (hipStream_t)stream);
+}
+
+int mmada_image_commit_sampled(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
+                               const int32_t* sampled_in, const void* p_in, const float* remask_temp, uint64_t seed,
+                               uint64_t* counter, const int32_t* mask_len_sched, int text_vocab_size, int codebook_size,
+                               void* stream) {
+    if (!h || !ids || !pos_map || !sampled_in || !p_in || !remask_temp || !counter || !mask_len_sched)
+        return mm_fail("mmada_image_commit_sampled: null argument");
+    return launch_image_commit_sampled(ids, B, L, pos_map, N, sampled_in, (const bf16_t*)p_in, remask_temp, seed, counter,
+                                       mask_len_sched, h->cfg.mask_token_id, text_vocab_size, codebook_size, (hipStream_t)stream);
+}
+
 int mmada_lfq_gather(mmada_handle* h, const int64_t* idx, int B, int N, int nbits, int dtype_f32, void* out,
                      void* stream) {
     (void)h;

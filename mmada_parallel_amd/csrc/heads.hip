@@ -183,6 +183,14 @@ int mmada_probe_gumbel(uint64_t seed, uint64_t counter, int row0, int R, int col
     return launch_gumbel_probe(seed, counter, row0, R, col0, N, words_out, g_out, (hipStream_t)stream);
 }
 
+float mmada_sample_normal(uint64_t seed, uint64_t counter, uint32_t r) { return sample_normal(seed, counter, r); }
+
+int mmada_probe_normal(uint64_t seed, uint64_t counter, int row0, int R, uint32_t* words01_out, float* z_out, uint16_t* z_bf16_out,
+                       void* stream) {
+    if (R <= 0 || row0 < 0 || (!words01_out && !z_out && !z_bf16_out)) return mm_fail("mmada_probe_normal: bad argument");
+    return launch_normal_probe(seed, counter, row0, R, words01_out, z_out, z_bf16_out, (hipStream_t)stream);
+}
+
 size_t mmada_score_buffer_bytes(const mmada_handle* h) { return h ? h->score_bytes : 0; }
 
 }  // extern "C"

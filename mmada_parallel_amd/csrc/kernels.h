@@ -150,8 +150,19 @@ int launch_image_probs(const bf16_t* cond, const bf16_t* ut, const bf16_t* ui, i
 int launch_image_commit(int64_t* ids, int B, int L, const int32_t* pos_map, int N, const int32_t* sampled_in,
                         const bf16_t* p_in, const bf16_t* noise, float remask_temp, const int32_t* mask_len_sched,
                         int mask_id, int text_vocab, int codebook, int mvar, hipStream_t s);
+// the image step with both draws on the device (sample_noise.h).  launch_image_sample: launch_image_probs' A variant without the
+// probabilities, the token a Gumbel-max draw at (seed, *counter), col0 = the column of codebook entry 0 in the whole vocabulary;
+// argmax_out / pmax_out may be null.  launch_image_commit_sampled: launch_image_commit's A variant with the noise of (seed,
+// *counter) and the temperature in device memory; its last launch adds 1 to *counter.
+int launch_image_sample(const bf16_t* cond, const bf16_t* ut, const bf16_t* ui, int B, int N, int CB, float cfg_scale,
+                        float cfg_img, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out,
+                        bf16_t* p_sel_out, int32_t* argmax_out, bf16_t* pmax_out, hipStream_t s);
+int launch_image_commit_sampled(int64_t* ids, int B, int L, const int32_t* pos_map, int N, const int32_t* sampled_in,
+                                const bf16_t* p_in, const float* remask_temp, uint64_t seed, uint64_t* counter,
+                                const int32_t* mask_len_sched, int mask_id, int text_vocab, int codebook, hipStream_t s);
 
 // probe.hip: MFMA-only diagnostic (attainable roof at the sustained clock on random data)
 int launch_f2bf_probe(const float* in, bf16_t* out, long long n, hipStream_t s);
 int launch_gumbel_probe(uint64_t seed, uint64_t counter, int row0, int R, int col0, int N, uint32_t* words, float* g, hipStream_t s);
+int launch_normal_probe(uint64_t seed, uint64_t counter, int row0, int R, uint32_t* words01, float* z, bf16_t* z_bf16, hipStream_t s);
 int launch_mfma_probe(const bf16_t* data, float* sink, int iters, int launches, hipStream_t s, double* tflops_out, double* ms_out);

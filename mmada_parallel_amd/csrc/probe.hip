@@ -197,6 +197,27 @@ int launch_gumbel_probe(uint64_t seed, uint64_t counter, int row0, int R, int co
     return 0;
 }
 
+// the re-mask noise of rows row0 .. row0 + R - 1: the two words, z in fp32 and the bf16 rounding the commit uses
+namespace {
+__global__ __launch_bounds__(256) void normal_probe_kernel(uint64_t seed, uint64_t counter, int row0, int R, uint32_t* __restrict__ words01,
+                                                           float* __restrict__ z, bf16_t* __restrict__ z_bf16) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= R) return;
+    uint32_t w0, w1;
+    sample_normal_words(seed, counter, (uint32_t)(row0 + i), w0, w1);
+    const float v = sample_normal_of(w0, w1);
+    if (words01) { words01[2 * (size_t)i] = w0; words01[2 * (size_t)i + 1] = w1; }
+    if (z) z[i] = v;
+    if (z_bf16) z_bf16[i] = f2bf(v);
+}
+}  // namespace
+int launch_normal_probe(uint64_t seed, uint64_t counter, int row0, int R, uint32_t* words01, float* z, bf16_t* z_bf16, hipStream_t s) {
+    if (R <= 0) return 0;
+    hipLaunchKernelGGL(normal_probe_kernel, dim3((R + 255) / 256), dim3(256), 0, s, seed, counter, row0, R, words01, z, z_bf16);
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- which CUs a stream's CU mask selects (round 5: the tensor-parallel exchange's CU partition, tp_comm.hip) -------------------
 // Every workgroup records where it ran: out[b] = XCC_ID | HW_ID << 8 (HW_REG_XCC_ID bits 3:0; HW_REG_HW_ID: cu_id 11:8, sh_id 12,
 // se_id 15:13).  Launched on a stream created with the given mask; tools/cu_mask_probe.py walks the mask bits.

@@ -10,6 +10,13 @@
 //   key = x + T * g                        two roundings, no FMA: x the bf16-rounded logit as fp32
 // row: index of the row inside the call; col: column in the WHOLE vocabulary.  Four consecutive columns from a multiple of 4
 // share one Philox evaluation.
+//
+// The image step (mmada_image_sample, mmada_image_commit_sampled) draws its tokens with the same g at T = 1 and adds the re-mask
+// noise, a standard-normal value per image position r = b * N + n:
+//   (word0, word1) = words 0, 1 of Philox4x32-10, counter block (0, r, counter_lo32, counter_hi32), key seed ^ SAMPLE_NORMAL_KEY_XOR
+//                    — another key than the token draw's, so the two streams never share a block
+//   z = sqrtf(-2 logf(u(word0))) * cosf(2 pi u(word1))      fp32 Box-Muller, no FMA; |z| <= sqrt(48 ln 2) ~ 5.77
+// and the commit uses z rounded to bf16 (the reference's randn is bf16: generators/parallel_generator.py:30-36).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -68,4 +75,22 @@ SN_FN float sample_key(float x, float T, float g) {
 #pragma clang fp contract(off)
     const float tg = T * g;
     return x + tg;
+}
+
+// the re-mask noise of image position r: its two words, and z from them
+constexpr uint64_t SAMPLE_NORMAL_KEY_XOR = 0x5851F42D4C957F2Dull;
+SN_FN void sample_normal_words(uint64_t seed, uint64_t counter, uint32_t r, uint32_t& w0, uint32_t& w1) {
+    uint32_t w2, w3;
+    sample_words4(seed ^ SAMPLE_NORMAL_KEY_XOR, counter, r, 0u, w0, w1, w2, w3);
+}
+SN_FN float sample_normal_of(uint32_t w0, uint32_t w1) {
+#pragma clang fp contract(off)
+    const float radius = sqrtf(-2.0f * logf(sample_uniform(w0)));
+    const float angle = 6.28318530717958647692f * sample_uniform(w1);
+    return radius * cosf(angle);
+}
+SN_FN float sample_normal(uint64_t seed, uint64_t counter, uint32_t r) {
+    uint32_t w0, w1;
+    sample_normal_words(seed, counter, r, w0, w1);
+    return sample_normal_of(w0, w1);
 }

@@ -8,6 +8,7 @@
 // Transcendentals are evaluated in fp64 and rounded once to the precision the reference computes in, which makes
 // the device result independent of libm flavour (the CPU oracle in oracle/sampler_oracle.c does the same).
 #include "kernels.h"
+#include "sample_noise.h"
 
 namespace {
 
@@ -329,6 +330,132 @@ __global__ __launch_bounds__(TB) void image_probs_kernel(const bf16_t* __restric
     }
 }
 
+// first-index arg-max over the workgroup: value descending, index ascending.  s_v / s_x: TB / 64 entries each; every thread
+// returns the winner (index 0 when no thread offered a candidate).  Ends with a barrier, so s_v / s_x may be reused.
+MM_DEVICE int block_argmax(float best, int bidx, float* s_v, int* s_x, float* best_out = nullptr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bidx, o, 64);
+        if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+    }
+    if (lane == 0) { s_v[wave] = best; s_x[wave] = bidx; }
+    __syncthreads();
+    best = s_v[0]; bidx = s_x[0];
+#pragma unroll
+    for (int w = 1; w < TB / 64; ++w)
+        if (s_v[w] > best || (s_v[w] == best && s_x[w] < bidx)) { best = s_v[w]; bidx = s_x[w]; }
+    __syncthreads();
+    if (best_out) *best_out = best;
+    return bidx == 0x7fffffff ? 0 : bidx;
+}
+
+// The same step with the token drawn here (image_sampler="device": replaces torch.multinomial + gather, :297-302, :311): the
+// sibling of image_probs_kernel<false> that never writes the probabilities.  CFG combine, maximum, e_i = (float)exp((double)(l_i -
+// max)), the fp64 row sum in the same order and fsum are image_probs_kernel's, bit for bit.  The draw is a Gumbel-max at T = 1:
+//   sampled = first-index arg-max over i < CB of sample_key(l_i, 1, g(seed, *counter, row, col0 + i))        (sample_noise.h)
+// l_i: the combined bf16-rounded logit as fp32; col0: the column of codebook entry 0 in the whole vocabulary (any value >= 0).
+// It samples softmax(l) evaluated in fp32, NOT its bf16 rounding: the reference's multinomial samples the bf16-rounded
+// probabilities.  Like the reference (:292-302) the image logits are not divided by a temperature.
+// p_sel = f2bf(e_sampled / fsum): what image_probs_kernel writes to probs[row, sampled].  argmax_out / pmax_out: null = skip,
+// else the bits of image_probs_kernel.  *counter is read, never written.
+__global__ __launch_bounds__(TB) void image_sample_kernel(const bf16_t* __restrict__ cond, const bf16_t* __restrict__ ut,
+                                                          const bf16_t* __restrict__ ui, int CB, float cfg_scale,
+                                                          float cfg_img, uint32_t col0, uint64_t seed,
+                                                          const uint64_t* __restrict__ counter,
+                                                          int32_t* __restrict__ sampled_out, bf16_t* __restrict__ p_sel_out,
+                                                          int32_t* __restrict__ argmax_out, bf16_t* __restrict__ pmax_out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* e = (float*)smem;  // [CB]: l_i, then e_i
+    __shared__ float s_f[TB / 64];
+    __shared__ double s_d[TB / 64];
+    __shared__ int s_i[TB / 64];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool use_t = cfg_scale != 0.0f && ut != nullptr, use_i = cfg_img != 0.0f && ui != nullptr;
+    const bf16_t* crow = cond + (size_t)row * CB;
+    const bf16_t* trow = use_t ? ut + (size_t)row * CB : crow;
+    const bf16_t* irow = use_i ? ui + (size_t)row * CB : crow;
+    const int nchunk = CB >> 3;
+
+    float mx = -INFINITY;
+    for (int c = tid; c < nchunk; c += TB) {
+        const u32x4 cv = ((const u32x4*)crow)[c];
+        u32x4 tv = cv, iv = cv;
+        if (use_t) tv = ((const u32x4*)trow)[c];
+        if (use_i) iv = ((const u32x4*)irow)[c];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float l0 = cfg_combine(__uint_as_float(cv[j] << 16), __uint_as_float(tv[j] << 16),
+                                         __uint_as_float(iv[j] << 16), use_t, use_i, cfg_scale, cfg_img);
+            const float l1 = cfg_combine(__uint_as_float(cv[j] & 0xffff0000u), __uint_as_float(tv[j] & 0xffff0000u),
+                                         __uint_as_float(iv[j] & 0xffff0000u), use_t, use_i, cfg_scale, cfg_img);
+            e[c * 8 + 2 * j] = l0;
+            e[c * 8 + 2 * j + 1] = l1;
+            mx = fmaxf(mx, fmaxf(l0, l1));
+        }
+    }
+    mx = wave_max(mx);
+    if (lane == 0) s_f[wave] = mx;
+    __syncthreads();
+    mx = s_f[0];
+#pragma unroll
+    for (int w = 1; w < TB / 64; ++w) mx = fmaxf(mx, s_f[w]);
+    __syncthreads();  // s_f is free again
+
+    // the draw, while e still holds the logits: one Philox block per four columns of the whole vocabulary, whatever col0 & 3 is
+    const uint64_t ctr = *counter;
+    const uint32_t blk0 = col0 >> 2, nblk = ((col0 + (uint32_t)CB - 1u) >> 2) - blk0 + 1u;
+    float kbest = -INFINITY;
+    int kidx = 0x7fffffff;
+    for (uint32_t q = tid; q < nblk; q += TB) {
+        uint32_t w0, w1, w2, w3;
+        sample_words4(seed, ctr, (uint32_t)row, blk0 + q, w0, w1, w2, w3);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const int i = (int)(((blk0 + q) << 2) + j - col0);  // ascends per thread -> first index kept
+            if (i < 0 || i >= CB) continue;
+            const float key = sample_key(e[i], 1.0f, sample_gumbel(sample_pick(w0, w1, w2, w3, j)));
+            if (key > kbest) { kbest = key; kidx = i; }
+        }
+    }
+    const int sampled = block_argmax(kbest, kidx, s_f, s_i);  // its barriers also end every read of the logits in e
+
+    // e_i = exp(l_i - max) rounded to fp32; the row sum is accumulated in fp64 (image_probs_kernel's order)
+    double sum = 0.0;
+    for (int i = tid; i < CB; i += TB) {
+        const float ev = (float)exp((double)(e[i] - mx));
+        e[i] = ev;
+        sum += (double)ev;
+    }
+    sum = wave_sum_d(sum);
+    if (lane == 0) s_d[wave] = sum;
+    __syncthreads();
+    double tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < TB / 64; ++w) tot += s_d[w];
+    const float fsum = (float)tot;
+
+    if (tid == 0) {
+        sampled_out[row] = sampled;
+        p_sel_out[row] = f2bf(e[sampled] / fsum);
+    }
+    if (!argmax_out && !pmax_out) return;
+
+    // p_i = bf16(e_i / sum); argmax over the bf16 values, lowest index wins
+    float best = -1.0f;
+    int bidx = 0x7fffffff;
+    for (int i = tid; i < CB; i += TB) {
+        const float p = bfround(e[i] / fsum);
+        if (p > best) { best = p; bidx = i; }
+    }
+    bidx = block_argmax(best, bidx, s_f, s_i, &best);
+    if (tid == 0) {
+        if (argmax_out) argmax_out[row] = bidx;
+        if (pmax_out) pmax_out[row] = f2bf(best < 0.f ? 0.f : best);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Image step part 2: keep known tokens, confidence, stable lowest-k re-mask, write back
 // (generators/parallel_generator.py:221-233, 304-344; mask_by_random_topk :23-70).
@@ -401,6 +528,63 @@ __global__ __launch_bounds__(1024) void image_commit_kernel(int64_t* __restrict_
     }
 }
 
+// The A-variant commit (image_commit_kernel<false>, keep_rule 0) for a step whose draws are all on the device: the noise of
+// position (b, n) is the bf16 rounding of sample_normal(seed, *counter, b * N + n) (sample_noise.h) instead of a randn tensor
+// (:30-33), and the re-mask temperature is read from device memory — nothing that changes from step to step is a by-value
+// argument, so a captured step replays.  Known-token clamp, bf16 log-confidence, stable lowest-k order and the mask_len rule are
+// image_commit_kernel's.  Every workgroup reads *counter: counter_bump_kernel, the launch after this one, advances it.
+__global__ __launch_bounds__(1024) void image_commit_sampled_kernel(int64_t* __restrict__ ids, int L,
+                                                                    const int32_t* __restrict__ pos_map, int N,
+                                                                    const int32_t* __restrict__ sampled_in,
+                                                                    const bf16_t* __restrict__ p_in,
+                                                                    const float* __restrict__ remask_temp, uint64_t seed,
+                                                                    const uint64_t* __restrict__ counter,
+                                                                    const int32_t* __restrict__ mask_len_sched, int mask_id,
+                                                                    int text_vocab, int codebook) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* conf = (float*)smem;          // [N] bf16-valued
+    int* samp = (int*)(conf + N);        // [N]
+    __shared__ int s_unknown;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) s_unknown = 0;
+    __syncthreads();
+    const float temp = remask_temp[0];
+    const uint64_t ctr = *counter;
+    int64_t* row = ids + (size_t)b * L;
+    int my_unknown = 0;
+    for (int n = tid; n < N; n += blockDim.x) {
+        const long long tok = row[pos_map[n]];
+        const bool unknown = tok == (long long)mask_id;
+        long long vq = tok - text_vocab;
+        vq = vq < 0 ? 0 : (vq > codebook - 1 ? codebook - 1 : vq);
+        int sidx = unknown ? sampled_in[(size_t)b * N + n] : (int)vq;
+        sidx = sidx < 0 ? 0 : (sidx > codebook - 1 ? codebook - 1 : sidx);
+        const float p = unknown ? bf2f(p_in[(size_t)b * N + n]) : bf2f((bf16_t)0x7f7f);
+        const float z = bfround(sample_normal(seed, ctr, (uint32_t)(b * N + n)));
+        float c = bfround((float)log((double)bfround(p + bfround(1e-10f))));
+        c = bfround(c + bfround(temp * z));
+        conf[n] = c;
+        samp[n] = sidx;
+        my_unknown += unknown;
+    }
+    if (my_unknown) atomicAdd(&s_unknown, my_unknown);
+    __syncthreads();
+    int k = max(1, min(s_unknown - 1, mask_len_sched[0]));
+    k = max(0, min(k, N - 1));
+    for (int n = tid; n < N; n += blockDim.x) {
+        const float c = conf[n];
+        int rank = 0;
+        for (int j = 0; j < N; ++j) {
+            const float cj = conf[j];
+            rank += (cj < c) || (cj == c && j < n);
+        }
+        row[pos_map[n]] = (rank < k) ? (int64_t)mask_id : (int64_t)(samp[n] + text_vocab);
+    }
+}
+
+// *counter += 1 once every workgroup of the kernel in front has read it (one thread: the stream orders it)
+__global__ void counter_bump_kernel(uint64_t* __restrict__ counter) { *counter += 1; }
+
 }  // namespace
 
 // remasking == 'random' (generators/parallel_generator.py:194-198): the confidence of a masked position is a uniform draw
@@ -472,6 +656,39 @@ int launch_image_commit(int64_t* ids, int B, int L, const int32_t* pos_map, int 
     } else
         hipLaunchKernelGGL(image_commit_kernel<false>, dim3(B), dim3(1024), (size_t)N * 8, s, ids, L, pos_map, N, sampled_in,
                            p_in, noise, remask_temp, mask_len_sched, mask_id, text_vocab, codebook, 0);
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_image_sample(const bf16_t* cond, const bf16_t* ut, const bf16_t* ui, int B, int N, int CB, float cfg_scale,
+                        float cfg_img, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out,
+                        bf16_t* p_sel_out, int32_t* argmax_out, bf16_t* pmax_out, hipStream_t s) {
+    if (CB <= 0 || CB % 8 || CB > 16384) return mm_fail("image_sample: codebook=%d must be a multiple of 8 and <= 16384", CB);
+    if (col0 < 0 || col0 > INT32_MAX - CB) return mm_fail("image_sample: col0=%d is not a column of the vocabulary", col0);
+    if (B * N <= 0) return 0;
+    static MmOncePerDevice attr_set;
+    MM_ONCE_PER_DEVICE(attr_set,
+        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         16384 * 4)));
+    hipLaunchKernelGGL(image_sample_kernel, dim3(B * N), dim3(TB), (size_t)CB * 4, s, cond, ut, ui, CB, cfg_scale, cfg_img,
+                       (uint32_t)col0, seed, counter, sampled_out, p_sel_out, argmax_out, pmax_out);
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_image_commit_sampled(int64_t* ids, int B, int L, const int32_t* pos_map, int N, const int32_t* sampled_in,
+                                const bf16_t* p_in, const float* remask_temp, uint64_t seed, uint64_t* counter,
+                                const int32_t* mask_len_sched, int mask_id, int text_vocab, int codebook, hipStream_t s) {
+    if (B <= 0 || N <= 0) return 0;
+    if (N > 8192) return mm_fail("image_commit_sampled: N=%d too large", N);
+    static MmOncePerDevice attr_set;  // as launch_image_commit: above the 64 KiB default near N = 8192
+    MM_ONCE_PER_DEVICE(attr_set,
+        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_commit_sampled_kernel,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8)));
+    hipLaunchKernelGGL(image_commit_sampled_kernel, dim3(B), dim3(1024), (size_t)N * 8, s, ids, L, pos_map, N, sampled_in, p_in,
+                       remask_temp, seed, counter, mask_len_sched, mask_id, text_vocab, codebook);
+    MM_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(counter_bump_kernel, dim3(1), dim3(1), 0, s, counter);
     MM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -8,6 +8,8 @@ the reference's, line for line in meaning; what changed is *where* the math runs
     inside the LM head's GEMM (mmada_text_select_sampled) and the logits are never materialised
   * VQ gather + CFG + softmax + argmax -> mmada_head_rows + mmada_image_probs   (:236-295)
   * keep-known / confidence / re-mask / write-back -> mmada_image_commit        (:221-233, :304-344, :23-70)
+    opt-in image_sampler="device": the token draw (torch.multinomial) and the re-mask noise (torch.randn) run inside
+    mmada_image_sample / mmada_image_commit_sampled, and the probabilities are never materialised
 All per-step counts (text k, image mask_len) are schedule-determined and precomputed on the host.
 """
 from __future__ import annotations
@@ -138,6 +140,7 @@ def _ti2ti_steps(
     graph=None,
     text_sampler="torch",
     sampler_seed=None,
+    image_sampler="torch",
 ):
     """Generator core shared by generate_ti2ti and generate_ti2ti_stepwise: runs the reference loop and yields
     (step, ids, info) after every step; `info` carries the image step's sampled ids (before re-masking) when one ran.
@@ -146,15 +149,30 @@ def _ti2ti_steps(
     `graph` (None = env MMADA_GRAPH=1): replay each kind of step — text-only, image step — as ONE hipGraph
     (mmada_graph_*): the launches of a step are a fixed sequence over fixed buffers because k, mask_len and the set of
     forwards are schedule-determined.  The first step of each kind runs eagerly, the second is captured,
-    the rest replay.  Only at temperature == text_temperature == 0 (the image re-mask temperature is a by-value kernel
-    argument that changes every step otherwise) and when the forward issues no host-side collective.
+    the rest replay.  Only when every draw of a step is device-side or absent — (temperature == 0 or image_sampler == "device")
+    and (text_temperature == 0 or text_sampler == "device"): a replayed step would otherwise replay torch's draws, and the torch
+    path's image re-mask temperature is a by-value kernel argument that changes every step — with remasking == 'low_confidence',
+    and when the forward issues no host-side collective.  At the README settings (temperature 1.0, text_temperature 0.7) with both
+    samplers "device" a step draws nothing on the host and replays bit-identically to the eager run.
 
     `text_sampler="device"` (opt-in; the default "torch" is the reference's path, draw for draw): the text step is ONE
     mmada_text_select_sampled call — a Gumbel-max draw inside the LM head's GEMM with a counter-based generator keyed by
     `sampler_seed` (required) and a counter that starts at 0 per call and advances by 1 per text step.  Neither the [B*T, V] logits
     nor the noise tensor exists.  The draws do not reproduce torch's RNG stream.  Only with text_temperature > 0,
-    remasking == 'low_confidence', on one rank and without micro-batched lanes: anything else raises ValueError.  The image step
-    (torch.multinomial included) is unchanged."""
+    remasking == 'low_confidence', on one rank and without micro-batched lanes: anything else raises ValueError.  With
+    temperature == 0 the one randn the reference still draws in an image step (it is multiplied by 0) is drawn ahead of the step's
+    launches, outside a capture; torch's stream sees the same values in the same order.
+
+    `image_sampler="device"` (opt-in; the default "torch" is the reference's path, draw for draw): an image step is
+    mmada_head_rows, mmada_image_sample (col0 = text_vocab_size) and mmada_image_commit_sampled.  Neither the [B*N, codebook]
+    probabilities nor any torch random tensor exists and `rng` is never called for it.  The token is a Gumbel-max draw at
+    temperature 1 over the CFG-combined bf16 logits — it samples their soft-max evaluated in fp32, where the reference's multinomial
+    samples the bf16-rounded probabilities — and the re-mask noise is a counter-based normal value per image position, both keyed by
+    `sampler_seed` (shared with the text sampler) and a counter of its own that starts at 1 << 62 per call — far from the text
+    counter, so a text row and an image row of one step never share (seed, counter, row) — and advances by 1 per image step.  The
+    re-mask temperature temperature * (1 - (step + 1) / text_steps) is a device value copied per step outside the captured region,
+    as mask_len is.  Only with temperature > 0 and on one rank: anything else raises ValueError.  The draws do not reproduce torch's
+    RNG stream."""
     if not isinstance(model, LLaDAForMultiModalGeneration):
         raise TypeError("generate_ti2ti (MI355X) needs mmada_parallel_amd.LLaDAForMultiModalGeneration; "
                         "there is no PyTorch fallback path")
@@ -181,6 +199,19 @@ def _ti2ti_steps(
             why = "sampler_seed"
         if why:
             raise ValueError(f"text_sampler='device' needs {why}")
+    if image_sampler not in ("torch", "device"):
+        raise ValueError(f"image_sampler={image_sampler!r}: 'torch' or 'device'")
+    dev_img = image_sampler == "device"
+    if dev_img:
+        why = None
+        if not temperature > 0:
+            why = "temperature > 0 (at 0 the image step is an arg-max: nothing is drawn)"
+        elif model.tp_size != 1 or model._comm_in_library:
+            why = "one rank (tensor parallelism is out of scope)"
+        elif sampler_seed is None:
+            why = "sampler_seed"
+        if why:
+            raise ValueError(f"image_sampler='device' needs {why}")
     lib, h = model._lib, model._handle
     device = model.device
     rng = rng or TorchRng()
@@ -242,7 +273,18 @@ def _ti2ti_steps(
     if not need_uncond and (cfg_scale != 0.0 or cfg_img != 0.0) and img_steps:
         zeros_vq = torch.zeros((B * N, CBs), dtype=torch.bfloat16, device=device)  # reference :275-278
     noise_buf = torch.zeros((B, N), dtype=torch.bfloat16, device=device)
-    probs = torch.empty((B * N, CBs), dtype=torch.bfloat16, device=device) if temperature != 0 and img_steps else None
+    probs = None
+    if temperature != 0 and img_steps and not dev_img:
+        probs = torch.empty((B * N, CBs), dtype=torch.bfloat16, device=device)
+    if dev_img:
+        img_counter = torch.full((1,), 1 << 62, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_sampled
+        # the re-mask temperature per step: host double arithmetic as on the torch path, then the same cast to fp32
+        temp_dev = torch.tensor([temperature * (1.0 - 1.0 * (step + 1) / text_steps) for step in range(text_steps)],
+                                dtype=torch.float32, device=device)
+        temp_cur = torch.zeros(1, dtype=torch.float32, device=device)
+        sampled_dev = torch.empty((B, N), dtype=torch.int32, device=device)
+        p_sel_dev = torch.empty((B, N), dtype=torch.bfloat16, device=device)
+        seed64 = int(sampler_seed) & 0xFFFFFFFFFFFFFFFF
 
     masked_left = remaining_text.clone()
     # rows of the residual stream each forward is read at (host-side): the last block only computes those
@@ -284,7 +326,8 @@ def _ti2ti_steps(
                           "mmada_text_select")
 
     def image_forwards():
-        """Unconditional forwards of an image step (reference :243-274) + dual-CFG soft-max / arg-max (:282-295)."""
+        """Unconditional forwards of an image step (reference :243-274) + dual-CFG soft-max / arg-max (:282-295), or with
+        image_sampler="device" the draw itself (:297-302)."""
         st = abi.stream_ptr()
         ut = ui = None
         if need_uncond:
@@ -301,6 +344,12 @@ def _ti2ti_steps(
             ut, ui = unc_vq[:B * N], unc_vq[B * N:]
         elif zeros_vq is not None:
             ut = ui = zeros_vq  # reference :275-278: uncond logits are zeros when no uncond input exists
+        if dev_img:
+            abi.check(lib.mmada_image_sample(h, cond_vq.data_ptr(), abi.ptr(ut), abi.ptr(ui), B, N, codebook_size,
+                                             float(cfg_scale), float(cfg_img), int(text_vocab_size), seed64,
+                                             img_counter.data_ptr(), sampled_dev.data_ptr(), p_sel_dev.data_ptr(), None, None, st),
+                      "mmada_image_sample")
+            return
         abi.check(lib.mmada_image_probs(h, cond_vq.data_ptr(), abi.ptr(ut), abi.ptr(ui), B, N, codebook_size,
                                         float(cfg_scale), float(cfg_img), abi.ptr(probs), argmax.data_ptr(),
                                         pmax.data_ptr(), st), "mmada_image_probs")
@@ -311,10 +360,16 @@ def _ti2ti_steps(
                                          mlen_cur.data_ptr(), int(text_vocab_size),
                                          int(codebook_size), abi.stream_ptr()), "mmada_image_commit")
 
+    def image_commit_sampled():
+        abi.check(lib.mmada_image_commit_sampled(h, ids.data_ptr(), B, L, pos_map.data_ptr(), N, sampled_dev.data_ptr(),
+                                                 p_sel_dev.data_ptr(), temp_cur.data_ptr(), seed64, img_counter.data_ptr(),
+                                                 mlen_cur.data_ptr(), int(text_vocab_size), int(codebook_size),
+                                                 abi.stream_ptr()), "mmada_image_commit_sampled")
+
     if graph is None:
         graph = os.environ.get("MMADA_GRAPH") == "1"
-    graph = (bool(graph) and temperature == 0 and text_temperature == 0 and remasking == 'low_confidence'
-             and model.graph_capturable())  # a replayed step would replay its random draws
+    graph = (bool(graph) and (temperature == 0 or dev_img) and (text_temperature == 0 or dev_text)
+             and remasking == 'low_confidence' and model.graph_capturable())  # a replayed step would replay torch's draws
     graphs, seen = {}, set()
     ws_epoch = model._ws_epoch
     side = torch.cuda.Stream(device=device) if graph else None
@@ -328,11 +383,14 @@ def _ti2ti_steps(
             with torch.cuda.stream(side) if graph else contextlib.nullcontext():
                 k_cur.copy_(k_dev[step])
                 mlen_cur.copy_(mlen_dev[step:step + 1])
-                early_noise = is_img and temperature == 0 and text_temperature == 0 and remasking == 'low_confidence'
+                if dev_img:
+                    temp_cur.copy_(temp_dev[step:step + 1])
+                early_noise = (is_img and temperature == 0 and (text_temperature == 0 or dev_text)
+                               and remasking == 'low_confidence')
                 if early_noise:
                     # randn is drawn even at temperature 0 (reference :30-33, A.2) so the RNG stream advances identically;
-                    # nothing else draws in such a step (no Gumbel noise, no random re-mask ranks), so it can be drawn
-                    # ahead of the step's launches
+                    # nothing else draws from torch in such a step (no Gumbel noise or a device-side one, no random re-mask
+                    # ranks), so it can be drawn ahead of the step's launches
                     noise_buf.copy_(rng.randn((B, N), torch.bfloat16, device, generator))
                 key = (is_img, need_text)
                 if graph and graphs and model._ws_epoch != ws_epoch:
@@ -353,7 +411,9 @@ def _ti2ti_steps(
                         text_part(is_img, need_text)
                         if is_img:
                             image_forwards()
-                            if temperature == 0:
+                            if dev_img:
+                                image_commit_sampled()
+                            elif temperature == 0:
                                 if not early_noise:  # the reference's draw order: text Gumbel noise first (:13-16, :30-33)
                                     noise_buf.copy_(rng.randn((B, N), torch.bfloat16, device, generator))
                                 image_commit(argmax, pmax, 0.0)
@@ -372,7 +432,9 @@ def _ti2ti_steps(
                 if need_text:
                     masked_left = masked_left - num_transfer[:, step]
                 if is_img:
-                    if temperature == 0:
+                    if dev_img:
+                        info["sampled"] = sampled_dev
+                    elif temperature == 0:
                         info["sampled"] = argmax
                     else:
                         s64 = rng.multinomial(probs, generator)
@@ -423,20 +485,26 @@ def generate_ti2ti(
     graph=None,
     text_sampler="torch",
     sampler_seed=None,
+    image_sampler="torch",
 ):
     """Joint text+image generation; returns (List[int] vq ids, str | List[int] text) like the reference
     (generators/parallel_generator.py:102-368).
 
-    `graph=True` (or MMADA_GRAPH=1) replays every step as one hipGraph (see _ti2ti_steps; BASELINE configs[4]).
+    `graph=True` (or MMADA_GRAPH=1) replays every step as one hipGraph when every draw of a step is device-side or absent
+    (see _ti2ti_steps; BASELINE configs[4]).
     `return_state=True` additionally returns the final `combined_input_ids` *before* the random fill of
     still-masked image tokens (reference :360-362) — the quantity parity tests compare.
-    `text_sampler="device"` with `sampler_seed`: draw the text tokens inside the LM head's GEMM (see _ti2ti_steps)."""
+    `text_sampler="device"` with `sampler_seed`: draw the text tokens inside the LM head's GEMM (see _ti2ti_steps).
+    `image_sampler="device"` with `sampler_seed` (temperature > 0, one rank): draw the image tokens and the re-mask noise in the
+    image kernels — no probabilities, no torch.multinomial / randn; with both samplers "device" a temperature > 0 run can replay as
+    hipGraphs, bit-identical to the eager run (see _ti2ti_steps)."""
     ids = pos_list = None
     for _step, ids, info in _ti2ti_steps(model, input_ids, text_start, text_end, image_start, seq_len, newline_every,
                                          text_steps, text_gen_length, text_block_length, timesteps, temperature,
                                          text_temperature, cfg_scale, cfg_img, uncon_text, uncon_image, tokenizer,
                                          remasking, noise_schedule, generator, text_vocab_size, codebook_size, rng=rng,
-                                         graph=graph, text_sampler=text_sampler, sampler_seed=sampler_seed):
+                                         graph=graph, text_sampler=text_sampler, sampler_seed=sampler_seed,
+                                         image_sampler=image_sampler):
         pos_list = info.get("pos_list", pos_list)
 
     # ===== final read-out (reference :346-368) =====
@@ -468,6 +536,7 @@ def generate_ti2ti_stepwise(
     uncon_text=None, uncon_image=None, tokenizer=None, remasking='low_confidence',
     noise_schedule=cosine_schedule, generator=None, text_vocab_size=126356,
     codebook_size=8192, vqvae=None, image_height=512, image_width=512, text_sampler="torch", sampler_seed=None,
+    image_sampler="torch",
 ):
     """Token-level mirror of the reference's streaming sampler `generate_ti2ti_stepwise` (app.py:143-398): the same
     loop as generate_ti2ti with the Gradio schedule of image steps, yielding after every step
@@ -485,7 +554,7 @@ def generate_ti2ti_stepwise(
                                             text_steps, 256, 64, 0, temperature, text_temperature, cfg_scale, cfg_img,
                                             uncon_text, uncon_image, tokenizer, remasking, noise_schedule, generator,
                                             text_vocab_size, codebook_size, image_step_list=sched, text_sampler=text_sampler,
-                                            sampler_seed=sampler_seed):
+                                            sampler_seed=sampler_seed, image_sampler=image_sampler):
             if step >= text_steps:
                 return
             show = step % 5 == 0 or info["image_step"] or step == text_steps - 1
