@@ -508,6 +508,34 @@ int mmada_probe_cu_mask(const uint32_t* mask, int words, uint32_t* out_host, int
  * in[i]; tests/test_gpu_kernels.py sweeps all 2^32 bit patterns against torch's conversion. */
 int mmada_probe_f2bf(const float* in, uint16_t* out, int64_t n, void* stream);
 
+/* ---- GEMM launcher probe (tests only) ------------------------------------------------------------------------------------
+ * One launch of the library's GEMM launcher with the STORE (epi 0), RESID (1) or SWIGLU (2) epilogue and every argument the
+ * forward sets for them; lda = ldw = K.  The launcher runs unchanged (planner, "gemm_config" and the other switches, zero rows,
+ * SiLU table), and `ran` receives the configuration it launched: 0..3 = the 8-phase configurations in the order of
+ * "gemm_config", 1000 + BM = the 16-wave kernel, -1 = nothing launched.
+ *   epi 0: C[M, ldc] = bf16(A·W^T).
+ *   epi 1: C = bf16(resid + bf16(A·W^T)) on the rows this rank owns — row m belongs to rank (m >> 4) % resid_mod — else
+ *          bf16(A·W^T); resid [., ldr] is never read on the other rows.  rwin > 0: C / A rows are compact [b * rwin + i] and the
+ *          residual of row m is read from row b * rlp + rbeg + i (M % rwin == 0); rwin == 0: from row m.
+ *   epi 2: C[M, ldc] holds N / 2 columns, W in the packed gate/up row order (mmada_gemm_swiglu_bt); N % 64 == 0.
+ *   publish != 0: every workgroup ends with the system-scope release of the tensor-parallel partial sums (same values).
+ * Refused, with nothing launched: a null operand, epi outside 0..2, epi 1 without resid, resid_mod < 1, resid_rank outside
+ * [0, resid_mod), rwin < 0, M % rwin != 0, a window outside its sequence (rbeg < 0 or rbeg + rwin > rlp), SwiGLU with
+ * N % 64 != 0, ldc (ldr) below the row length.  tests/test_gpu_gemm_exact.py holds every epilogue to exact expected bits with it. */
+typedef struct mmada_gemm_probe {
+    const void* A;      /* [M, K] bf16 */
+    const void* W;      /* [N, K] bf16 */
+    void* C;            /* [M, ldc] bf16 */
+    const void* resid;  /* epi 1: [rows, ldr] bf16 */
+    int32_t epi, M, N, K, ldc;
+    int32_t ldr, resid_mod, resid_rank;
+    int32_t rwin, rlp, rbeg;
+    int32_t publish;
+    int32_t ran;        /* out */
+    int32_t reserved;
+} mmada_gemm_probe;
+int mmada_probe_gemm(mmada_gemm_probe* p, void* stream);
+
 /* ---- tensor-parallel exchange inside the library (SURVEY.md §8b mmada_allreduce_init, §8e) ----------------------------
  * New design; the reference runs one replica (inference.py:83-85).  With tp_size > 1 the two row-parallel GEMMs of a block
  * (attn_out, ff_out; model/modeling_llada.py:741-744, 968-970) leave a partial [B*Lp, d] sum on every rank.  One exchange

@@ -26,6 +26,18 @@ class MmadaCfg(C.Structure):
     ]
 
 
+class MmadaGemmProbe(C.Structure):
+    """struct mmada_gemm_probe (include/mmada_mi355x.h): one launch of the GEMM launcher; `ran` is written by the library."""
+
+    _fields_ = [
+        ("A", c_void_p), ("W", c_void_p), ("C", c_void_p), ("resid", c_void_p),
+        ("epi", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ldc", C.c_int32),
+        ("ldr", C.c_int32), ("resid_mod", C.c_int32), ("resid_rank", C.c_int32),
+        ("rwin", C.c_int32), ("rlp", C.c_int32), ("rbeg", C.c_int32),
+        ("publish", C.c_int32), ("ran", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol the header declares (checked by tests/test_abi.py)
 SIGNATURES = {
     "mmada_create": (c_int, [C.POINTER(MmadaCfg), C.POINTER(C.c_float), C.POINTER(c_void_p)]),
@@ -93,6 +105,7 @@ SIGNATURES = {
     "mmada_gemm_plan": (c_int, [c_int, c_int, c_int]),
     "mmada_attention_plan": (c_int, [c_int, c_int, c_int]),
     "mmada_probe_f2bf": (c_int, [c_void_p, c_void_p, C.c_int64, c_void_p]),
+    "mmada_probe_gemm": (c_int, [C.POINTER(MmadaGemmProbe), c_void_p]),
     "mmada_mfma_probe_bytes": (c_size_t, []),
     "mmada_mfma_probe": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mmada_gemm_bt": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -213,6 +213,35 @@ int mmada_gemm_swiglu_bt(const void* A, const void* W, void* C, int M, int N, in
     return launch_gemm(EPI_SWIGLU, gemm_bt_args((const bf16_t*)A, (const bf16_t*)W, (bf16_t*)C, M, N, K, N / 2), (hipStream_t)stream);
 }
 
+// The launcher itself on caller data (tests): the three epilogues of the block's plain projections with what forward.hip sets for them.
+int mmada_probe_gemm(mmada_gemm_probe* p, void* stream) {
+    if (!p) return mm_fail("mmada_probe_gemm: null argument");
+    p->ran = -1;
+    if (!p->A || !p->W || !p->C) return mm_fail("mmada_probe_gemm: null operand");
+    if (p->epi < EPI_STORE || p->epi > EPI_SWIGLU) return mm_fail("mmada_probe_gemm: epi=%d is not 0 (store), 1 (resid) or 2 (swiglu)", p->epi);
+    if (p->epi == EPI_RESID && !p->resid) return mm_fail("mmada_probe_gemm: the residual epilogue needs resid");
+    if (p->resid_mod < 1 || p->resid_rank < 0 || p->resid_rank >= p->resid_mod)
+        return mm_fail("mmada_probe_gemm: resid_mod=%d must be >= 1 and resid_rank=%d inside [0, resid_mod)", p->resid_mod, p->resid_rank);
+    if (p->rwin < 0) return mm_fail("mmada_probe_gemm: rwin=%d is negative", p->rwin);
+    if (p->rwin > 0 && p->M % p->rwin != 0) return mm_fail("mmada_probe_gemm: M=%d is not a multiple of rwin=%d", p->M, p->rwin);
+    if (p->rwin > 0 && (p->rbeg < 0 || p->rbeg + p->rwin > p->rlp))
+        return mm_fail("mmada_probe_gemm: rows [%d, %d) lie outside a sequence of rlp=%d rows", p->rbeg, p->rbeg + p->rwin, p->rlp);
+    if (p->epi == EPI_SWIGLU && p->N % 64 != 0) return mm_fail("mmada_probe_gemm: SwiGLU needs N=%d to be a multiple of 64", p->N);
+    const int ncol = p->epi == EPI_SWIGLU ? p->N / 2 : p->N;
+    if (p->ldc < ncol || (p->epi == EPI_RESID && p->ldr < ncol))
+        return mm_fail("mmada_probe_gemm: ldc=%d (ldr=%d) is shorter than a row of %d columns", p->ldc, p->ldr, ncol);
+    GemmArgs g = gemm_bt_args((const bf16_t*)p->A, (const bf16_t*)p->W, (bf16_t*)p->C, p->M, p->N, p->K, p->ldc);
+    if (p->epi == EPI_RESID) {   // (forward.hip: add_residual and the consumed-row window)
+        g.resid = (const bf16_t*)p->resid; g.ldr = p->ldr; g.resid_mod = p->resid_mod; g.resid_rank = p->resid_rank;
+        g.rwin = p->rwin; g.rlp = p->rlp; g.rbeg = p->rbeg;
+    }
+    g.publish = p->publish;
+    int ran = -1;
+    const int rc = launch_gemm(p->epi, g, (hipStream_t)stream, &ran);
+    p->ran = ran;
+    return rc;
+}
+
 int mmada_gemm_plan(int M, int N, int K) { return gemm_plan_code(M, N, K); }
 int mmada_attention_plan(int pairs, int groups, int keys) {
     if (pairs <= 0 || groups <= 0 || keys <= 0) return mm_fail("mmada_attention_plan: bad argument"), -1;

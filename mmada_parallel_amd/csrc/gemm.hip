@@ -228,8 +228,9 @@ Plan plan(const GemmArgs& g, int force) {
     return best;
 }
 
+// ran (or null): receives what is launched, 0..3 = GEMM8_* configuration, 1000 + BM = the 16-wave kernel (mmada_probe_gemm)
 template <int EPI>
-int launch_t(const GemmArgs& g, const Switches& sw, hipStream_t s) {
+int launch_t(const GemmArgs& g, const Switches& sw, hipStream_t s, int* ran) {
     Plan p = plan(g, sw.gemm_config);
     if constexpr (is_row_head(EPI)) {
         // the row-statistics epilogue (and its top-k and sampling forms) exists for 256-column tiles of four 64-column waves: a pinned configuration without one
@@ -238,6 +239,7 @@ int launch_t(const GemmArgs& g, const Switches& sw, hipStream_t s) {
         if (p.p8 && p.code == GEMM8_320x128) p = {true, GEMM8_320x256};
         if (!p.p8 && p.code == 160) p.code = 192;
         if (!p.p8 && p.code == 224) p.code = 256;
+        if (ran) *ran = p.p8 ? p.code : 1000 + p.code;
         if (p.p8) return launch_gemm8(EPI, p.code, g, sw, s);
         switch (p.code) {
             case 320: return launch_cfg<EPI, 320, 4, 4>(g, s);
@@ -246,6 +248,7 @@ int launch_t(const GemmArgs& g, const Switches& sw, hipStream_t s) {
             default: return launch_cfg<EPI, 128, 4, 4>(g, s);
         }
     } else {
+    if (ran) *ran = p.p8 ? p.code : 1000 + p.code;   // plan() only returns a BM the switch below has a case for
     if (p.p8) return launch_gemm8(EPI, p.code, g, sw, s);
     switch (p.code) {
         case 320: return launch_cfg<EPI, 320, 4, 4>(g, s);
@@ -324,7 +327,7 @@ int gemm_prepare_device() {
     return device_consts(&dc, (hipStream_t)0);
 }
 
-int launch_gemm(int epi, const GemmArgs& g_in, hipStream_t s) {
+int launch_gemm(int epi, const GemmArgs& g_in, hipStream_t s, int* ran) {
     const Switches sw = switches();   // one snapshot decides the whole launch
     DeviceConsts dc;
     if (device_consts(&dc, s)) return 1;
@@ -338,18 +341,18 @@ int launch_gemm(int epi, const GemmArgs& g_in, hipStream_t s) {
     if (is_row_head(epi))   // (row_heads.h: what each head needs; a null target is allowed for top-k and sample only)
         if (const char* fault = row_head_args_fault(epi, row_head_args(g), g.M)) return mm_fail("%s", fault);
     switch (epi) {
-        case EPI_STORE: return launch_t<EPI_STORE>(g, sw, s);
-        case EPI_RESID: return launch_t<EPI_RESID>(g, sw, s);
+        case EPI_STORE: return launch_t<EPI_STORE>(g, sw, s, ran);
+        case EPI_RESID: return launch_t<EPI_RESID>(g, sw, s, ran);
         case EPI_SWIGLU:
             if (g.N % 64) return mm_fail("gemm/swiglu: N must be a multiple of 64");
-            return launch_t<EPI_SWIGLU>(g, sw, s);
+            return launch_t<EPI_SWIGLU>(g, sw, s, ran);
         case EPI_QKV:
             if (g.N != (g.Hq + 2 * g.Hkv) * 128) return mm_fail("gemm/qkv: N mismatch");
             if (g.Lp % 8 || g.m_base % 8) return mm_fail("gemm/qkv: Lp and m_base must be multiples of 8");
-            return launch_t<EPI_QKV>(g, sw, s);
-        case EPI_ROWSTAT: return launch_t<EPI_ROWSTAT>(g, sw, s);
-        case EPI_ROWTOPK: return launch_t<EPI_ROWTOPK>(g, sw, s);
-        case EPI_ROWSAMPLE: return launch_t<EPI_ROWSAMPLE>(g, sw, s);
+            return launch_t<EPI_QKV>(g, sw, s, ran);
+        case EPI_ROWSTAT: return launch_t<EPI_ROWSTAT>(g, sw, s, ran);
+        case EPI_ROWTOPK: return launch_t<EPI_ROWTOPK>(g, sw, s, ran);
+        case EPI_ROWSAMPLE: return launch_t<EPI_ROWSAMPLE>(g, sw, s, ran);
     }
     return mm_fail("gemm: bad epilogue %d", epi);
 }

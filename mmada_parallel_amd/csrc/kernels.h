@@ -68,7 +68,9 @@ Switches switches();
 // EPI_ROWSTAT, EPI_ROWTOPK, EPI_ROWSAMPLE are the row heads of the LM head: nothing of C is stored, and their arguments travel in
 // GemmArgs fields these epilogues have no other use for (row_heads.h: RowHeadArgs, the records, the record buffer's layout).
 // gemm8.hip: the 8-phase kernel, cfg = one of the GEMM8_* configurations; returns nonzero on a launch error.
-int launch_gemm(int epi, const GemmArgs& g, hipStream_t s);
+// ran (or null): receives the configuration launch_gemm launched — 0..3 = GEMM8_*, 1000 + BM = the 16-wave kernel; left alone when
+// nothing is launched
+int launch_gemm(int epi, const GemmArgs& g, hipStream_t s, int* ran = nullptr);
 enum Gemm8Cfg { GEMM8_320x256 = 0, GEMM8_256x256 = 1, GEMM8_160x256 = 2, GEMM8_320x128 = 3, GEMM8_NCFG = 4 };
 bool gemm8_supports(const GemmArgs& g);  // shape contract of the 8-phase kernel (K % 128 == 0, K >= 256, M, N % 8 == 0, ...)
 int launch_gemm8(int epi, int cfg, const GemmArgs& g, const Switches& sw, hipStream_t s);  // sw: short row tiles, tile order

@@ -681,3 +681,179 @@ def att_general_verdict(got, ref, A, E):
     bound = (ATT_U + 2.0 * E) * (A + r)
     ratio = (got.double() - ref).abs() / bound.clamp_min(1e-300)
     return float(torch.nan_to_num(ratio, nan=float("inf")).max())
+
+
+# ---- the GEMM epilogues STORE / RESID / SWIGLU, exactly (tests/test_gpu_gemm_exact.py, tests/test_gemm_exact_host.py) ----
+# Every expected value is integer arithmetic or ONE IEEE operation plus torch's fp32 -> bf16 cast (which
+# test_f2bf_matches_torch_on_every_bit_pattern ties to the device's conversion): independent of libm and of accumulation order.
+GEMM_CONFIGS = (-1, 0, 1, 2, 3, 1128, 1160, 1192, 1224, 1256, 1320)     # "gemm_config": automatic, the 8-phase tiles, 1000 + BM
+GEMM_BM16 = (128, 160, 192, 224, 256, 320)
+GEMM_CANARY = 0x7FA5                                                    # a bf16 NaN whose payload no kernel produces
+
+
+def gemm8_admits(M, N, K, ldc, ldr=None, c_byte_offset=0):
+    """csrc/gemm8.hip gemm8_supports restated for K-contiguous operands and 16-byte aligned allocations: may the 8-phase kernel run?"""
+    return (K % 128 == 0 and K >= 256 and M % 8 == 0 and N % 8 == 0 and M >= 8 and N >= 8 and ldc % 8 == 0
+            and (ldr is None or ldr % 8 == 0) and c_byte_offset % 16 == 0)
+
+
+def gemm_int_operands(M, N, K, seed=0):
+    """A [M, K], W [N, K] (bf16, CPU): seeded random integers of [-7, 7], or [-15, 15] at K = 64 (so that a single K-tile's sums still leave
+    bf16's 8 bits).  Every product and partial sum is an integer below K * 225 < 2^24: the fp32 accumulator is exact in any order."""
+    amp = 15 if K <= 64 else 7
+    assert K * amp * amp < 2 ** 24
+    g = torch.Generator().manual_seed(1000003 * seed + 7919 * M + 31 * N + K)
+    A = torch.randint(-amp, amp + 1, (M, K), generator=g).to(torch.bfloat16)
+    W = torch.randint(-amp, amp + 1, (N, K), generator=g).to(torch.bfloat16)
+    return A, W
+
+
+def gemm_pre(A, W, k_tiles=None):
+    """The exact pre-activation A @ W.T of integer operands as int64 (float64 products and sums of integers below 2^53: exact).
+    k_tiles: weights per 64-wide K-tile (the mutations: 0 drops a tile, 2 counts it twice); None: every tile once."""
+    a, w = A.double(), W.double()
+    if k_tiles is not None:
+        a = a * torch.tensor(k_tiles, dtype=torch.float64).repeat_interleave(64)[None, :]
+    return (a @ w.t()).to(torch.int64)
+
+
+def gemm_expected_store(pre):
+    """bf16(acc): the integer as fp32 (exact below 2^24), then torch's cast."""
+    assert int(pre.abs().max()) < 2 ** 24
+    return pre.float().to(torch.bfloat16)
+
+
+def gemm_resid_rows(M, rwin=0, rlp=0, rbeg=0):
+    """Residual row of output row m: m, or with a row window b * rlp + rbeg + i for the compact row m = b * rwin + i."""
+    m = torch.arange(M)
+    if not rwin:
+        return m
+    b = m // rwin
+    return b * rlp + rbeg + (m - b * rwin)
+
+
+def gemm_owner(M, mod, rank, shift=0):
+    """[M] bool: does rank `rank` of `mod` add the residual of row m?  Fragment row m >> 4 belongs to rank (m >> 4) % mod.
+    shift != 0 is the mutation 'the wrong owner's fragment rows'."""
+    return (((torch.arange(M) >> 4) + shift) % mod) == rank
+
+
+def gemm_resid(pre, rows, ldr, seed=0):
+    """[rows, ldr] random bf16 ~ N(0, std(acc)): arbitrary mantissas at the magnitude of the accumulator."""
+    g = torch.Generator().manual_seed(seed + 17)
+    return (torch.randn(rows, ldr, generator=g) * float(pre.double().std())).to(torch.bfloat16)
+
+
+def gemm_poison_resid(resid, keep_rows):
+    """A copy of resid with every row NOT in keep_rows filled with NaN: what a rank must never read."""
+    out = torch.full_like(resid, float("nan"))
+    out[keep_rows] = resid[keep_rows]
+    return out
+
+
+def gemm_expected_resid(pre, resid, mod=1, rank=0, rwin=0, rlp=0, rbeg=0, owner_shift=0, every_rank=False, single_rounding=False):
+    """bf16(resid + bf16(acc)) on the rows the rank owns, bf16(acc) elsewhere: one IEEE fp32 add and one rounding per element.
+    The keyword mutations restate the defects the tests must catch."""
+    M, N = pre.shape
+    acc = gemm_expected_store(pre)
+    own = torch.ones(M, dtype=torch.bool) if every_rank else gemm_owner(M, mod, rank, owner_shift)
+    r = resid[gemm_resid_rows(M, rwin, rlp, rbeg), :N].float()
+    summed = (r + (pre.float() if single_rounding else acc.float())).to(torch.bfloat16)
+    return torch.where(own[:, None], summed, acc)
+
+
+def gemm_onehot(M, K, stride, shift):
+    """A [M, K] bf16 with A[m, pi(m)] = 1, pi(m) = (m * stride + shift) % K, stride odd: the pre-activation is W[n, pi(m)] exactly, for
+    arbitrary mantissas of W — which k and which n every output reads.  Returns (A, pi)."""
+    assert stride % 2 == 1
+    pi = (torch.arange(M) * stride + shift) % K
+    A = torch.zeros(M, K, dtype=torch.bfloat16)
+    A[torch.arange(M), pi] = 1.0
+    return A, pi
+
+
+def gemm_random_w(N, K, seed=0):
+    """[N, K] random normal bf16, finite and nonzero (0 * Inf would poison a whole output row)."""
+    g = torch.Generator().manual_seed(seed + 29)
+    W = torch.randn(N, K, generator=g).to(torch.bfloat16)
+    assert bool(torch.isfinite(W.float()).all()) and bool((W.float() != 0).all())
+    return W
+
+
+def silu_margin_ok(vals):
+    """For bf16 gate values: (ok, silu) — silu = the bf16 nearest to the float64 g / (1 + exp(-g)); ok where that float64 value lies
+    further than 2^-16 (relative) from a bf16 rounding midpoint.  The device evaluates g / (1.0f + expf(-g)): a few-ulp expf, one
+    add, one IEEE division, about 2^-21 relative in all — 1/32 of the margin, so bf16(silu) is the same for ANY correct fp32
+    evaluation (and for the table, which silu_lut_kernel fills with that function)."""
+    g = vals.double()
+    s = g / (1.0 + torch.exp(-g))
+    mant, _ = torch.frexp(s.abs())                 # [0.5, 1)
+    scaled = mant * 256.0                          # [128, 256): bf16's 8 significant bits are the integer part
+    frac = scaled - torch.floor(scaled)
+    ok = ((frac - 0.5).abs() / scaled > 2.0 ** -16) | (s == 0)
+    return ok, bf16_nearest(s).to(torch.bfloat16)
+
+
+_SILU_SAFE = {}
+
+
+def silu_safe_set():
+    """(gates, silu, n_domain): the bf16 values with |g| in [2^-14, 2^5) — the whole domain of the SwiGLU epilogue's table
+    (gemm_epilogue.h: SiluLut), 4 864 values — that pass silu_margin_ok, and their bf16 SiLU."""
+    if not _SILU_SAFE:
+        key = torch.arange(19 * 128, dtype=torch.int32) + (113 << 7)
+        dom = torch.cat([key, key | 0x8000]).to(torch.int16).view(torch.bfloat16)
+        ok, s = silu_margin_ok(dom)
+        _SILU_SAFE["v"] = (dom[ok], s[ok], dom.numel())
+    return _SILU_SAFE["v"]
+
+
+def silu_bf16_torch(x):
+    """F.silu on a bf16 tensor the way the reference runs it: fp32 inside, rounded to bf16."""
+    return torch.nn.functional.silu(x.float()).to(torch.bfloat16)
+
+
+def swiglu_weights(N, K, seed=0, extras=None):
+    """Gate rows G [N / 2, K] drawn from the safe set and up rows U [N / 2, K] ~ N(0, 1) (bf16).  extras: gate values outside the table's
+    domain mixed into half of the entries of every 24th gate column (two whole 16-row fragments at least, so some waves of every
+    tile configuration take the evaluating path while the others read the table)."""
+    g = torch.Generator().manual_seed(1000003 * seed + 31 * N + K + 41)
+    safe = silu_safe_set()[0]
+    G = safe[torch.randint(0, safe.numel(), (N // 2, K), generator=g)]
+    U = torch.randn(N // 2, K, generator=g).to(torch.bfloat16)
+    if extras is not None:
+        cols = torch.arange(5, N // 2, 24)
+        pick = extras[torch.randint(0, extras.numel(), (cols.numel(), K), generator=g)]
+        mix = torch.rand(cols.numel(), K, generator=g) < 0.5
+        G[cols] = torch.where(mix, pick, G[cols])
+    return G, U
+
+
+def swiglu_pack(G, U):
+    """W [N, K] in the library's packed gate/up row order (pack_gate_up): groups of 32 rows = [16 gate rows | the matching 16 up rows]."""
+    n2, K = G.shape
+    W = torch.empty(2 * n2, K, dtype=torch.bfloat16)
+    Wv = W.view(n2 // 16, 2, 16, K)
+    Wv[:, 0] = G.view(n2 // 16, 16, K)
+    Wv[:, 1] = U.view(n2 // 16, 16, K)
+    return W
+
+
+def swiglu_expected(G, U, pi, swapped=False):
+    """[M, N / 2]: bf16(silu_bf16(gate) * up) with gate = G[c, pi(m)], up = U[c, pi(m)] — the one-hot operand's pre-activations: one
+    exact fp32 product of two bf16 values and one rounding.  swapped: the mutation 'gate and up halves exchanged'."""
+    gate, up = G[:, pi].t(), U[:, pi].t()
+    if swapped:
+        gate, up = up, gate
+    return (silu_bf16_torch(gate).float() * up.float()).to(torch.bfloat16)
+
+
+def gemm_exact_verdict(got, exp):
+    """None if got and exp (bf16, same shape) hold the same BITS; else the first wrong element, both bit patterns and the count."""
+    g, e = bits(got), bits(exp)
+    bad = g != e
+    count = int(bad.sum())
+    if count == 0:
+        return None
+    m, n = (int(i) for i in bad.nonzero()[0])
+    return dict(count=count, first=(m, n), got=int(g[m, n]) & 0xFFFF, expected=int(e[m, n]) & 0xFFFF)

@@ -67,6 +67,8 @@ def test_gemm_every_row_tile_height():
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (300, 384, 256), (77, 200, 128), (1000, 8192, 256),
                                    (2438, 4096, 4096), (2440, 12288, 4096), (4876, 4096, 12288)])
 def test_gemm_bt(M, N, K):
+    """The random-data sanity check of the plain product at production sizes; exactness (expected bits under every configuration,
+    for the store, residual and SwiGLU epilogues) lives in tests/test_gpu_gemm_exact.py."""
     torch.manual_seed(M + N + K)
     A = torch.randn(M, K, device=DEV).to(torch.bfloat16)
     W = (torch.randn(N, K, device=DEV) * 0.05).to(torch.bfloat16)  # asymmetric operands: catches transposed C
