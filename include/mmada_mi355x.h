@@ -197,6 +197,11 @@ int mmada_probe_gumbel(uint64_t seed, uint64_t counter, int row0, int R, int col
  * values of rows row0 .. row0 + R - 1: words01_out device [R, 2], z_out device fp32 [R], z_bf16_out device bf16 [R], each or
  * NULL (not all three). */
 float mmada_sample_normal(uint64_t seed, uint64_t counter, uint32_t r);
+/* The re-mask noise of the M image step (mmada_image_commit_m_sampled; replaces uniform_ and its two logs,
+ * MMaDA-Parallel-M/models/sampling.py:15-17): g_remask = -log(-log(u(word0))) on the word0 above, in fp32 — the Gumbel value
+ * g(seed ^ 0x5851F42D4C957F2D, counter, row r, column 0), so mmada_probe_gumbel with that seed, col0 = 0 and N = 1 returns the
+ * device's values.  The commit uses it rounded to bf16.  On the host, no device is touched (the host's logf). */
+float mmada_sample_remask_gumbel(uint64_t seed, uint64_t counter, uint32_t r);
 int mmada_probe_normal(uint64_t seed, uint64_t counter, int row0, int R, uint32_t* words01_out, float* z_out, uint16_t* z_bf16_out,
                        void* stream);
 
@@ -358,6 +363,42 @@ int mmada_image_probs_m(mmada_handle* h, const void* cond, const void* uncond, i
 int mmada_image_commit_m(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
                          const int32_t* sampled_in, const void* p_in, const void* gumbel, float remask_temp,
                          const int32_t* mask_len_sched, int text_vocab_size, void* stream);
+
+/* The M steps with every draw on the device (interleave_generate / t2i_generate with image_sampler="device", text_sampler="device"):
+ * no probabilities, no torch random tensor, no by-value argument that changes from step to step — a captured step replays.
+ *
+ * mmada_image_sample_m replaces mmada_image_probs_m + torch.multinomial + gather (modeling_mmada.py:216-222,229-231; t2i :314-334):
+ * the combine l_i = bf16(bf16((1 + image_cfg) * c_i) - bf16(image_cfg * u_i)), the maximum, the exponentials and the fp64 row sum of
+ * mmada_image_probs_m bit for bit, and
+ *   sampled_out[b,n] = first-index arg-max over i < CB of  fadd_rn(l_i, g(seed, *counter, r, col0 + i)),  r = b*N + n
+ * (g and the tie rule of mmada_head_sample at temperature 1; col0: the column of codebook entry 0 in the WHOLE vocabulary, the
+ * generators pass len(tokenizer)).  p_sel_out: bf16 device [B,N] = bf16(e_sampled / sum), what mmada_image_probs_m writes to
+ * probs[b,n,sampled].  argmax_out / pmax_out: NULL or mmada_image_probs_m's, same bits.  counter: read, never written.  The draw
+ * samples softmax(l) evaluated in fp32; the reference's multinomial samples the bf16-ROUNDED probabilities.  Limits of
+ * mmada_image_sample.
+ *
+ * mmada_image_commit_m_sampled replaces uniform_ + logs + mmada_image_commit_m (:224-241, sampling.py:15-17,31-36):
+ * mmada_image_commit_m with gumbel[b,n] = bf16(g_remask(seed, *counter, b*N + n)) (mmada_sample_remask_gumbel) computed in the kernel
+ * and the re-mask temperature read from remask_temp (device fp32 [1]).  sampled_out: NULL or device int32 [B,N], the id each position
+ * is committed from — unknown ? sampled_in : ids - text_vocab_size, read before ids is overwritten: the reference's sampled_ids
+ * (:224-225), which the generators return.  *counter is incremented by 1 by the call's last kernel.
+ *
+ * mmada_text_draw_cfg replaces add_gumbel_noise + argmax on the float64 copy of the combined logits (:49-60,173,182) at
+ * text_temperature > 0: cond / uncond bf16 device [B*T, ld_logits] (V columns used, ld_logits % 8 == 0),
+ *   x0_out[r] = first-index arg-max over v < V of  fadd_rn(l_v, fmul_rn(temperature, g(seed, *counter, r, v))),  r = b*T + t,
+ * l_v = bf16(c_v + bf16(text_cfg * bf16(u_v - c_v))) as mmada_text_select_cfg combines; at temperature 0 the plain first-index
+ * arg-max of l.  temperature: finite and >= 0, anything else is an error.  x0_out is the x0_in of mmada_text_select_cfg.  The
+ * reference's exp(l) / (-log u)^T in float64 has the same arg-max in exact arithmetic; this draws from softmax(l / T) evaluated in
+ * fp32, on another stream than torch's.  *counter is incremented by 1 by the call's last kernel. */
+int mmada_image_sample_m(mmada_handle* h, const void* cond, const void* uncond, int B, int N, int CB, float image_cfg, int col0,
+                         uint64_t seed, const uint64_t* counter, int32_t* sampled_out, void* p_sel_out, int32_t* argmax_out,
+                         void* pmax_out, void* stream);
+int mmada_image_commit_m_sampled(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
+                                 const int32_t* sampled_in, const void* p_in, const float* remask_temp, uint64_t seed,
+                                 uint64_t* counter, const int32_t* mask_len_sched, int text_vocab_size, int32_t* sampled_out,
+                                 void* stream);
+int mmada_text_draw_cfg(mmada_handle* h, const void* cond, const void* uncond, float text_cfg, int B, int T, int V, int ld_logits,
+                        float temperature, uint64_t seed, uint64_t* counter, int32_t* x0_out, void* stream);
 
 /* (A, text-to-image) re-mask + write-back of generate_image (generators/image_generation_generator.py:99-103,178-207,
  * utils/generation_utils.py:47-64): as mmada_image_commit_m, but the number of tokens that stay masked is

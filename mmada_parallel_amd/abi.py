@@ -95,6 +95,13 @@ SIGNATURES = {
                                     c_void_p, c_void_p]),
     "mmada_image_commit_m": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_float, c_void_p, c_int, c_void_p]),
+    "mmada_image_sample_m": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, C.c_uint64, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mmada_image_commit_m_sampled": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                             C.c_uint64, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "mmada_text_draw_cfg": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_float, C.c_uint64,
+                                    c_void_p, c_void_p, c_void_p]),
+    "mmada_sample_remask_gumbel": (c_float, [C.c_uint64, C.c_uint64, C.c_uint32]),
     "mmada_image_commit_g": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_float, c_void_p, c_int, c_void_p]),
     "mmada_lfq_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

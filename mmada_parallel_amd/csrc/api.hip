@@ -333,8 +333,37 @@ int mmada_image_sample(mmada_handle* h, const void* cond, const void* unc_text, 
                        void* p_sel_out, int32_t* argmax_out, void* pmax_out, void* stream) {
     if (!h || !cond || !counter || !sampled_out || !p_sel_out) return mm_fail("mmada_image_sample: null argument");
     return launch_image_sample((const bf16_t*)cond, (const bf16_t*)unc_text, (const bf16_t*)unc_img, B, N, CB, cfg_scale, cfg_img,
-                               col0, seed, counter, sampled_out, (bf16_t*)p_sel_out, argmax_out, (bf16_t*)pmax_out,
+                               col0, seed, counter, sampled_out, (bf16_t*)p_sel_out, argmax_out, (bf16_t*)pmax_out, 0,
                                (hipStream_t)stream);
+}
+
+int mmada_image_sample_m(mmada_handle* h, const void* cond, const void* uncond, int B, int N, int CB, float image_cfg, int col0,
+                         uint64_t seed, const uint64_t* counter, int32_t* sampled_out, void* p_sel_out, int32_t* argmax_out,
+                         void* pmax_out, void* stream) {
+    if (!h || !cond || !uncond || !counter || !sampled_out || !p_sel_out) return mm_fail("mmada_image_sample_m: null argument");
+    const float one_plus = (float)(1.0 + (double)image_cfg);  // as mmada_image_probs_m
+    return launch_image_sample((const bf16_t*)cond, (const bf16_t*)uncond, nullptr, B, N, CB, image_cfg, one_plus, col0, seed,
+                               counter, sampled_out, (bf16_t*)p_sel_out, argmax_out, (bf16_t*)pmax_out, 1, (hipStream_t)stream);
+}
+
+int mmada_image_commit_m_sampled(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
+                                 const int32_t* sampled_in, const void* p_in, const float* remask_temp, uint64_t seed,
+                                 uint64_t* counter, const int32_t* mask_len_sched, int text_vocab_size, int32_t* sampled_out,
+                                 void* stream) {
+    if (!h || !ids || !pos_map || !sampled_in || !p_in || !remask_temp || !counter || !mask_len_sched)
+        return mm_fail("mmada_image_commit_m_sampled: null argument");
+    return launch_image_commit_sampled(ids, B, L, pos_map, N, sampled_in, (const bf16_t*)p_in, remask_temp, seed, counter,
+                                       mask_len_sched, h->cfg.mask_token_id, text_vocab_size, 0, 1, sampled_out,
+                                       (hipStream_t)stream);
+}
+
+int mmada_text_draw_cfg(mmada_handle* h, const void* cond, const void* uncond, float text_cfg, int B, int T, int V, int ld_logits,
+                        float temperature, uint64_t seed, uint64_t* counter, int32_t* x0_out, void* stream) {
+    if (!h || !cond || !uncond || !counter || !x0_out) return mm_fail("mmada_text_draw_cfg: null argument");
+    if (!(temperature >= 0.f) || __builtin_isinf(temperature))
+        return mm_fail("mmada_text_draw_cfg: temperature %g is not a finite value >= 0", (double)temperature);
+    return launch_text_draw_cfg((const bf16_t*)cond, (const bf16_t*)uncond, text_cfg, B, T, V, ld_logits, temperature, seed, counter,
+                                x0_out, (hipStream_t)stream);
 }
 
 int mmada_image_commit_sampled(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
@@ -344,7 +373,8 @@ int mmada_image_commit_sampled(mmada_handle* h, int64_t* ids, int B, int L, cons
     if (!h || !ids || !pos_map || !sampled_in || !p_in || !remask_temp || !counter || !mask_len_sched)
         return mm_fail("mmada_image_commit_sampled: null argument");
     return launch_image_commit_sampled(ids, B, L, pos_map, N, sampled_in, (const bf16_t*)p_in, remask_temp, seed, counter,
-                                       mask_len_sched, h->cfg.mask_token_id, text_vocab_size, codebook_size, (hipStream_t)stream);
+                                       mask_len_sched, h->cfg.mask_token_id, text_vocab_size, codebook_size, 0, nullptr,
+                                       (hipStream_t)stream);
 }
 
 int mmada_lfq_gather(mmada_handle* h, const int64_t* idx, int B, int N, int nbits, int dtype_f32, void* out,

@@ -184,6 +184,7 @@ int mmada_probe_gumbel(uint64_t seed, uint64_t counter, int row0, int R, int col
 }
 
 float mmada_sample_normal(uint64_t seed, uint64_t counter, uint32_t r) { return sample_normal(seed, counter, r); }
+float mmada_sample_remask_gumbel(uint64_t seed, uint64_t counter, uint32_t r) { return sample_remask_gumbel(seed, counter, r); }
 
 int mmada_probe_normal(uint64_t seed, uint64_t counter, int row0, int R, uint32_t* words01_out, float* z_out, uint16_t* z_bf16_out,
                        void* stream) {

@@ -17,6 +17,12 @@
 //                    — another key than the token draw's, so the two streams never share a block
 //   z = sqrtf(-2 logf(u(word0))) * cosf(2 pi u(word1))      fp32 Box-Muller, no FMA; |z| <= sqrt(48 ln 2) ~ 5.77
 // and the commit uses z rounded to bf16 (the reference's randn is bf16: generators/parallel_generator.py:30-36).
+//
+// The M image step (mmada_image_sample_m, mmada_image_commit_m_sampled) draws its tokens the same way and re-masks with Gumbel
+// noise (MMaDA-Parallel-M/models/sampling.py:15-17), a value per image position r = b * N + n from the SAME block as z:
+//   g_remask = -log(-log(u(word0)))     word0 as above: = g(seed ^ SAMPLE_NORMAL_KEY_XOR, counter, row r, column 0)
+// and the commit uses g_remask rounded to bf16 (the reference's uniform_ and its two logs are bf16 tensors).  The M text draw
+// (mmada_text_draw_cfg) is sample_key over the CFG-combined logits with g(seed, counter, row b * T + t, column v).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -93,4 +99,10 @@ SN_FN float sample_normal(uint64_t seed, uint64_t counter, uint32_t r) {
     uint32_t w0, w1;
     sample_normal_words(seed, counter, r, w0, w1);
     return sample_normal_of(w0, w1);
+}
+// the M variant's re-mask noise of image position r: the Gumbel value of the same block's word 0
+SN_FN float sample_remask_gumbel(uint64_t seed, uint64_t counter, uint32_t r) {
+    uint32_t w0, w1;
+    sample_normal_words(seed, counter, r, w0, w1);
+    return sample_gumbel(w0);
 }

@@ -360,6 +360,10 @@ MM_DEVICE int block_argmax(float best, int bidx, float* s_v, int* s_x, float* be
 // probabilities.  Like the reference (:292-302) the image logits are not divided by a temperature.
 // p_sel = f2bf(e_sampled / fsum): what image_probs_kernel writes to probs[row, sampled].  argmax_out / pmax_out: null = skip,
 // else the bits of image_probs_kernel.  *counter is read, never written.
+// MVAR (interleave_generate / t2i_generate with image_sampler="device": replaces torch.multinomial + gather, modeling_mmada.py:220-222,
+// :229-231): the sibling of image_probs_kernel<true> — ut = the uncond branch, cfg_scale = image_cfg, cfg_img = 1 + image_cfg
+// (host-computed), l_i = cfg_combine_m; everything after the combine is the same code.
+template <bool MVAR>
 __global__ __launch_bounds__(TB) void image_sample_kernel(const bf16_t* __restrict__ cond, const bf16_t* __restrict__ ut,
                                                           const bf16_t* __restrict__ ui, int CB, float cfg_scale,
                                                           float cfg_img, uint32_t col0, uint64_t seed,
@@ -372,7 +376,7 @@ __global__ __launch_bounds__(TB) void image_sample_kernel(const bf16_t* __restri
     __shared__ double s_d[TB / 64];
     __shared__ int s_i[TB / 64];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool use_t = cfg_scale != 0.0f && ut != nullptr, use_i = cfg_img != 0.0f && ui != nullptr;
+    const bool use_t = MVAR || (cfg_scale != 0.0f && ut != nullptr), use_i = !MVAR && cfg_img != 0.0f && ui != nullptr;
     const bf16_t* crow = cond + (size_t)row * CB;
     const bf16_t* trow = use_t ? ut + (size_t)row * CB : crow;
     const bf16_t* irow = use_i ? ui + (size_t)row * CB : crow;
@@ -386,10 +390,17 @@ __global__ __launch_bounds__(TB) void image_sample_kernel(const bf16_t* __restri
         if (use_i) iv = ((const u32x4*)irow)[c];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float l0 = cfg_combine(__uint_as_float(cv[j] << 16), __uint_as_float(tv[j] << 16),
-                                         __uint_as_float(iv[j] << 16), use_t, use_i, cfg_scale, cfg_img);
-            const float l1 = cfg_combine(__uint_as_float(cv[j] & 0xffff0000u), __uint_as_float(tv[j] & 0xffff0000u),
-                                         __uint_as_float(iv[j] & 0xffff0000u), use_t, use_i, cfg_scale, cfg_img);
+            float l0, l1;
+            if constexpr (MVAR) {
+                l0 = cfg_combine_m(__uint_as_float(cv[j] << 16), __uint_as_float(tv[j] << 16), cfg_img, cfg_scale);
+                l1 = cfg_combine_m(__uint_as_float(cv[j] & 0xffff0000u), __uint_as_float(tv[j] & 0xffff0000u), cfg_img,
+                                   cfg_scale);
+            } else {
+                l0 = cfg_combine(__uint_as_float(cv[j] << 16), __uint_as_float(tv[j] << 16),
+                                 __uint_as_float(iv[j] << 16), use_t, use_i, cfg_scale, cfg_img);
+                l1 = cfg_combine(__uint_as_float(cv[j] & 0xffff0000u), __uint_as_float(tv[j] & 0xffff0000u),
+                                 __uint_as_float(iv[j] & 0xffff0000u), use_t, use_i, cfg_scale, cfg_img);
+            }
             e[c * 8 + 2 * j] = l0;
             e[c * 8 + 2 * j + 1] = l1;
             mx = fmaxf(mx, fmaxf(l0, l1));
@@ -533,6 +544,12 @@ __global__ __launch_bounds__(1024) void image_commit_kernel(int64_t* __restrict_
 // (:30-33), and the re-mask temperature is read from device memory — nothing that changes from step to step is a by-value
 // argument, so a captured step replays.  Known-token clamp, bf16 log-confidence, stable lowest-k order and the mask_len rule are
 // image_commit_kernel's.  Every workgroup reads *counter: counter_bump_kernel, the launch after this one, advances it.
+// MVAR: image_commit_kernel<true> (keep_rule 0) the same way (replaces the uniform_ + two logs of sampling.py:15-17): the noise is
+// the bf16 rounding of sample_remask_gumbel(seed, *counter, b * N + n); known ids unclamped, bf16 log(clamp(p, 1e-20)) + temp *
+// gumbel, the cut-off rule rank <= k and the mask_len rule are image_commit_kernel<true>'s.  sampled_out (null = skip): the id each
+// position is committed from, unknown ? sampled_in : vq - text_vocab (the reference's sampled_ids, :224-225), taken from the ids
+// this kernel READS — the barrier before the write-back separates the two.
+template <bool MVAR>
 __global__ __launch_bounds__(1024) void image_commit_sampled_kernel(int64_t* __restrict__ ids, int L,
                                                                     const int32_t* __restrict__ pos_map, int N,
                                                                     const int32_t* __restrict__ sampled_in,
@@ -540,7 +557,8 @@ __global__ __launch_bounds__(1024) void image_commit_sampled_kernel(int64_t* __r
                                                                     const float* __restrict__ remask_temp, uint64_t seed,
                                                                     const uint64_t* __restrict__ counter,
                                                                     const int32_t* __restrict__ mask_len_sched, int mask_id,
-                                                                    int text_vocab, int codebook) {
+                                                                    int text_vocab, int codebook,
+                                                                    int32_t* __restrict__ sampled_out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* conf = (float*)smem;          // [N] bf16-valued
     int* samp = (int*)(conf + N);        // [N]
@@ -556,13 +574,21 @@ __global__ __launch_bounds__(1024) void image_commit_sampled_kernel(int64_t* __r
         const long long tok = row[pos_map[n]];
         const bool unknown = tok == (long long)mask_id;
         long long vq = tok - text_vocab;
-        vq = vq < 0 ? 0 : (vq > codebook - 1 ? codebook - 1 : vq);
+        if constexpr (!MVAR) vq = vq < 0 ? 0 : (vq > codebook - 1 ? codebook - 1 : vq);
         int sidx = unknown ? sampled_in[(size_t)b * N + n] : (int)vq;
-        sidx = sidx < 0 ? 0 : (sidx > codebook - 1 ? codebook - 1 : sidx);
+        if constexpr (!MVAR) sidx = sidx < 0 ? 0 : (sidx > codebook - 1 ? codebook - 1 : sidx);
         const float p = unknown ? bf2f(p_in[(size_t)b * N + n]) : bf2f((bf16_t)0x7f7f);
-        const float z = bfround(sample_normal(seed, ctr, (uint32_t)(b * N + n)));
-        float c = bfround((float)log((double)bfround(p + bfround(1e-10f))));
-        c = bfround(c + bfround(temp * z));
+        float c;
+        if constexpr (MVAR) {
+            const float g = bfround(sample_remask_gumbel(seed, ctr, (uint32_t)(b * N + n)));
+            c = bfround((float)log((double)(p < 1e-20f ? bfround(1e-20f) : p)));  // log(t.clamp(min=1e-20)) in bf16
+            c = bfround(c + bfround(temp * g));
+            if (sampled_out) sampled_out[(size_t)b * N + n] = sidx;
+        } else {
+            const float z = bfround(sample_normal(seed, ctr, (uint32_t)(b * N + n)));
+            c = bfround((float)log((double)bfround(p + bfround(1e-10f))));
+            c = bfround(c + bfround(temp * z));
+        }
         conf[n] = c;
         samp[n] = sidx;
         my_unknown += unknown;
@@ -574,12 +600,66 @@ __global__ __launch_bounds__(1024) void image_commit_sampled_kernel(int64_t* __r
     for (int n = tid; n < N; n += blockDim.x) {
         const float c = conf[n];
         int rank = 0;
-        for (int j = 0; j < N; ++j) {
-            const float cj = conf[j];
-            rank += (cj < c) || (cj == c && j < n);
+        if constexpr (MVAR) {
+            // conf < sorted[k]  <=>  at most k elements are <= conf (its own tie class sits below position k)
+            for (int j = 0; j < N; ++j) rank += conf[j] <= c;
+            row[pos_map[n]] = (rank <= k) ? (int64_t)mask_id : (int64_t)((long long)samp[n] + text_vocab);
+        } else {
+            for (int j = 0; j < N; ++j) {
+                const float cj = conf[j];
+                rank += (cj < c) || (cj == c && j < n);
+            }
+            row[pos_map[n]] = (rank < k) ? (int64_t)mask_id : (int64_t)(samp[n] + text_vocab);
         }
-        row[pos_map[n]] = (rank < k) ? (int64_t)mask_id : (int64_t)(samp[n] + text_vocab);
     }
+}
+
+// The M text draw at text_temperature > 0 (replaces add_gumbel_noise + argmax on a float64 copy of the combined logits,
+// modeling_mmada.py:49-60, :182), one workgroup per (b, t) row:
+//   x0 = first-index arg-max over v < V of sample_key(text_cfg_combine(c_v, u_v, text_cfg), T, g(seed, *counter, row, v))
+// v: the column in the whole vocabulary, so a 16-byte chunk of eight logits takes two Philox blocks.  T == 0: the plain arg-max of
+// the combined logits, no generator runs.  The reference's exp(l) / (-log u)^T in float64 has the same arg-max as l + T * g in exact
+// arithmetic; this draws from softmax(comb / T) evaluated in fp32, on another stream than torch's.
+__global__ __launch_bounds__(TB) void text_draw_cfg_kernel(const bf16_t* __restrict__ cond, const bf16_t* __restrict__ unc,
+                                                           float text_cfg, int V, int ld, float temperature, uint64_t seed,
+                                                           const uint64_t* __restrict__ counter, int32_t* __restrict__ x0_out) {
+    __shared__ float s_f[TB / 64];
+    __shared__ int s_i[TB / 64];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const bf16_t* crow = cond + (size_t)row * ld;
+    const bf16_t* urow = unc + (size_t)row * ld;
+    const uint64_t ctr = *counter;
+    const bool noisy = temperature != 0.0f;
+    const int nchunk = V >> 3;
+    float best = -INFINITY;
+    int bidx = 0x7fffffff;
+    for (int c = tid; c < nchunk; c += TB) {
+        const u32x4 cv = ((const u32x4*)crow)[c];
+        const u32x4 uv = ((const u32x4*)urow)[c];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            uint32_t w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u;
+            if (noisy) sample_words4(seed, ctr, (uint32_t)row, (uint32_t)(2 * c + half), w0, w1, w2, w3);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const uint32_t cb = cv[2 * half + j], ub = uv[2 * half + j];
+                const float l0 = text_cfg_combine(__uint_as_float(cb << 16), __uint_as_float(ub << 16), text_cfg);
+                const float l1 = text_cfg_combine(__uint_as_float(cb & 0xffff0000u), __uint_as_float(ub & 0xffff0000u), text_cfg);
+                const float k0 = noisy ? sample_key(l0, temperature, sample_gumbel(j ? w2 : w0)) : l0;
+                const float k1 = noisy ? sample_key(l1, temperature, sample_gumbel(j ? w3 : w1)) : l1;
+                const int i = c * 8 + 4 * half + 2 * j;  // ascends per thread -> first index kept
+                if (k0 > best) { best = k0; bidx = i; }
+                if (k1 > best) { best = k1; bidx = i + 1; }
+            }
+        }
+    }
+    for (int i = (nchunk << 3) + tid; i < V; i += TB) {  // tail (V % 8): at most one column per thread
+        const float l = text_cfg_combine(bf2f(crow[i]), bf2f(urow[i]), text_cfg);
+        const float k = noisy ? sample_key(l, temperature, sample_gumbel(sample_word(seed, ctr, (uint32_t)row, (uint32_t)i))) : l;
+        if (k > best || (k == best && i < bidx)) { best = k; bidx = i; }
+    }
+    const int x0 = block_argmax(best, bidx, s_f, s_i);
+    if (tid == 0) x0_out[row] = x0;
 }
 
 // *counter += 1 once every workgroup of the kernel in front has read it (one thread: the stream orders it)
@@ -662,31 +742,56 @@ int launch_image_commit(int64_t* ids, int B, int L, const int32_t* pos_map, int 
 
 int launch_image_sample(const bf16_t* cond, const bf16_t* ut, const bf16_t* ui, int B, int N, int CB, float cfg_scale,
                         float cfg_img, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out,
-                        bf16_t* p_sel_out, int32_t* argmax_out, bf16_t* pmax_out, hipStream_t s) {
+                        bf16_t* p_sel_out, int32_t* argmax_out, bf16_t* pmax_out, int mvar, hipStream_t s) {
     if (CB <= 0 || CB % 8 || CB > 16384) return mm_fail("image_sample: codebook=%d must be a multiple of 8 and <= 16384", CB);
     if (col0 < 0 || col0 > INT32_MAX - CB) return mm_fail("image_sample: col0=%d is not a column of the vocabulary", col0);
     if (B * N <= 0) return 0;
     static MmOncePerDevice attr_set;
     MM_ONCE_PER_DEVICE(attr_set,
-        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_sample_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         16384 * 4));
+        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          16384 * 4)));
-    hipLaunchKernelGGL(image_sample_kernel, dim3(B * N), dim3(TB), (size_t)CB * 4, s, cond, ut, ui, CB, cfg_scale, cfg_img,
-                       (uint32_t)col0, seed, counter, sampled_out, p_sel_out, argmax_out, pmax_out);
+    if (mvar)
+        hipLaunchKernelGGL(image_sample_kernel<true>, dim3(B * N), dim3(TB), (size_t)CB * 4, s, cond, ut, ui, CB, cfg_scale,
+                           cfg_img, (uint32_t)col0, seed, counter, sampled_out, p_sel_out, argmax_out, pmax_out);
+    else
+        hipLaunchKernelGGL(image_sample_kernel<false>, dim3(B * N), dim3(TB), (size_t)CB * 4, s, cond, ut, ui, CB, cfg_scale,
+                           cfg_img, (uint32_t)col0, seed, counter, sampled_out, p_sel_out, argmax_out, pmax_out);
     MM_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_image_commit_sampled(int64_t* ids, int B, int L, const int32_t* pos_map, int N, const int32_t* sampled_in,
                                 const bf16_t* p_in, const float* remask_temp, uint64_t seed, uint64_t* counter,
-                                const int32_t* mask_len_sched, int mask_id, int text_vocab, int codebook, hipStream_t s) {
+                                const int32_t* mask_len_sched, int mask_id, int text_vocab, int codebook, int mvar,
+                                int32_t* sampled_out, hipStream_t s) {
     if (B <= 0 || N <= 0) return 0;
     if (N > 8192) return mm_fail("image_commit_sampled: N=%d too large", N);
     static MmOncePerDevice attr_set;  // as launch_image_commit: above the 64 KiB default near N = 8192
     MM_ONCE_PER_DEVICE(attr_set,
-        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_commit_sampled_kernel,
+        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_commit_sampled_kernel<false>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
+        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_commit_sampled_kernel<true>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8)));
-    hipLaunchKernelGGL(image_commit_sampled_kernel, dim3(B), dim3(1024), (size_t)N * 8, s, ids, L, pos_map, N, sampled_in, p_in,
-                       remask_temp, seed, counter, mask_len_sched, mask_id, text_vocab, codebook);
+    if (mvar)
+        hipLaunchKernelGGL(image_commit_sampled_kernel<true>, dim3(B), dim3(1024), (size_t)N * 8, s, ids, L, pos_map, N,
+                           sampled_in, p_in, remask_temp, seed, counter, mask_len_sched, mask_id, text_vocab, codebook, sampled_out);
+    else
+        hipLaunchKernelGGL(image_commit_sampled_kernel<false>, dim3(B), dim3(1024), (size_t)N * 8, s, ids, L, pos_map, N,
+                           sampled_in, p_in, remask_temp, seed, counter, mask_len_sched, mask_id, text_vocab, codebook, nullptr);
+    MM_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(counter_bump_kernel, dim3(1), dim3(1), 0, s, counter);
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_text_draw_cfg(const bf16_t* cond, const bf16_t* unc, float text_cfg, int B, int T, int V, int ld, float temperature,
+                         uint64_t seed, uint64_t* counter, int32_t* x0_out, hipStream_t s) {
+    if (V <= 0 || V > ld || ld % 8) return mm_fail("text_draw_cfg: V=%d, ld_logits=%d: 0 < V <= ld_logits, a multiple of 8", V, ld);
+    if (B <= 0 || T <= 0) return 0;
+    hipLaunchKernelGGL(text_draw_cfg_kernel, dim3(B * T), dim3(TB), 0, s, cond, unc, text_cfg, V, ld, temperature, seed, counter,
+                       x0_out);
     MM_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(counter_bump_kernel, dim3(1), dim3(1), 0, s, counter);
     MM_CHECK_HIP(hipGetLastError());

@@ -8,10 +8,17 @@ inside the image span; the returned image ids are the last image step's samples.
 
 The random draws go through an `rng` object (default: torch's own RNG calls, in the reference's order) so that parity
 tests can replay the reference's draws.
+
+Opt-in, `image_sampler="device"` / `text_sampler="device"` with `sampler_seed`: the draws run inside the kernels
+(mmada_image_sample_m, mmada_image_commit_m_sampled, mmada_text_draw_cfg) on the counter-based generator of
+csrc/sample_noise.h, and a step can then replay as one hipGraph (`graph=True`); see interleave_generate.
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes as C
 import math
+import os
 from typing import Callable, Dict, Optional
 
 import torch
@@ -60,6 +67,152 @@ def _log(t, eps=1e-20):
     return torch.log(t.clamp(min=eps))  # sampling.py:11-12
 
 
+def check_m_samplers(model, image_sampler, text_sampler="torch", sampler_seed=None, text_temperature=0.0):
+    """The refusals of the M generators' device samplers, in generate_ti2ti's wording; returns (dev_img, dev_text)."""
+    if text_sampler not in ("torch", "device"):
+        raise ValueError(f"text_sampler={text_sampler!r}: 'torch' or 'device'")
+    if image_sampler not in ("torch", "device"):
+        raise ValueError(f"image_sampler={image_sampler!r}: 'torch' or 'device'")
+    dev_img, dev_text = image_sampler == "device", text_sampler == "device"
+    if dev_text and not text_temperature > 0:
+        raise ValueError("text_sampler='device' needs text_temperature > 0 (at 0 the text step is an arg-max: nothing is drawn)")
+    for name, on in (("text_sampler", dev_text), ("image_sampler", dev_img)):
+        if on and (model.tp_size != 1 or model._comm_in_library):
+            raise ValueError(f"{name}='device' needs one rank (tensor parallelism is out of scope)")
+        if on and sampler_seed is None:
+            raise ValueError(f"{name}='device' needs sampler_seed")
+    return dev_img, dev_text
+
+
+def _device_steps(model, ids0, uncond_input_ids, P, T, N, CB, text_vocab, text_cfg, image_cfg, text_temperature, text_steps,
+                  img_steps, k_dev, mlen_dev, temps, pos_map, text_rows, img_rows, scratch, argmax, pmax, rng, generator, trace,
+                  dev_img, dev_text, seed64, graph):
+    """interleave_generate's loop with a device sampler: the same launches over buffers that all exist before the loop, so that a
+    step takes no argument that changes from step to step and can be captured and replayed (generate_ti2ti's scheme, _ti2ti_steps).
+    A sampler left at "torch" still draws from `rng` in the reference's order; such a run is not captured."""
+    lib, h, device = model._lib, model._handle, model.device
+    L, V = ids0.shape[1], model.vocab
+    text_start, img_start = L - T, P + 1
+    # cond and uncond as ONE fixed [2, L] batch: row 0 IS the running ids, row 1 = the uncond prompt + a copy of row 0's tail (:166-169)
+    both = torch.empty((2, L), dtype=torch.long, device=device)
+    both[0].copy_(ids0[0])
+    both[1, :P].copy_(uncond_input_ids[0])
+    ids = both[0:1]
+    model._ensure_ws(2, L)   # before the first step: a workspace that grew later would leave a captured graph pointing at freed memory
+    tl = torch.empty((2 * T, V), dtype=torch.bfloat16, device=device)
+    il = torch.empty((2 * N, CB), dtype=torch.bfloat16, device=device) if img_steps else None
+    x0 = torch.zeros(T, dtype=torch.int32, device=device) if text_temperature != 0 else None
+    k_cur = torch.zeros(1, dtype=torch.int32, device=device)
+    mlen_cur = torch.zeros(1, dtype=torch.int32, device=device)
+    text_counter = torch.zeros(1, dtype=torch.int64, device=device)          # advanced by mmada_text_draw_cfg
+    if dev_img:
+        img_counter = torch.full((1,), 1 << 62, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_m_sampled
+        temp_dev = torch.tensor(temps, dtype=torch.float32, device=device)
+        temp_cur = torch.zeros(1, dtype=torch.float32, device=device)
+        drawn = torch.empty((1, N), dtype=torch.int32, device=device)
+        p_sel = torch.empty((1, N), dtype=torch.bfloat16, device=device)
+        sampled = torch.empty((1, N), dtype=torch.int32, device=device)
+    mask_id = int(model.config.get("mask_token_id", 126336))
+    state = {"sampled": None}
+
+    def step_body(i, is_img):
+        both[1, P:].copy_(both[0, P:])
+        if trace is not None:
+            trace.append(both.cpu().clone())
+        model.forward_body(both, consumed=(img_start if is_img else text_start, L))   # one batch-2 forward (:171)
+        st = abi.stream_ptr()
+        model.head_rows(text_rows, 0, V, out=tl)
+        if is_img:
+            model.head_rows(img_rows, text_vocab, text_vocab + CB, out=il)
+        if text_temperature != 0 and dev_text:
+            abi.check(lib.mmada_text_draw_cfg(h, tl[:T].data_ptr(), tl[T:].data_ptr(), text_cfg, 1, T, V, V, text_temperature,
+                                              seed64, text_counter.data_ptr(), x0.data_ptr(), st), "mmada_text_draw_cfg")
+        elif text_temperature != 0:
+            comb = tl[:T] + text_cfg * (tl[T:] - tl[:T])         # :173 on the text rows, bf16 tensor ops
+            x0.copy_(rng.text_gumbel_argmax(comb.view(1, T, V), text_temperature).view(T))
+        abi.check(lib.mmada_text_select_cfg(h, tl[:T].data_ptr(), tl[T:].data_ptr(), text_cfg, abi.ptr(x0), 1, T, V, V,
+                                            ids.data_ptr(), L, text_start, k_cur.data_ptr(), scratch.data_ptr(), st),
+                  "mmada_text_select_cfg")
+        if is_img and dev_img:
+            abi.check(lib.mmada_image_sample_m(h, il[:N].data_ptr(), il[N:].data_ptr(), 1, N, CB, image_cfg, text_vocab, seed64,
+                                               img_counter.data_ptr(), drawn.data_ptr(), p_sel.data_ptr(), None, None, st),
+                      "mmada_image_sample_m")
+            abi.check(lib.mmada_image_commit_m_sampled(h, ids.data_ptr(), 1, L, pos_map.data_ptr(), N, drawn.data_ptr(),
+                                                       p_sel.data_ptr(), temp_cur.data_ptr(), seed64, img_counter.data_ptr(),
+                                                       mlen_cur.data_ptr(), text_vocab, sampled.data_ptr(), st),
+                      "mmada_image_commit_m_sampled")
+        elif is_img:   # the reference's draws (:216-241) on the fixed buffers
+            probs = torch.empty((N, CB), dtype=torch.bfloat16, device=device)
+            abi.check(lib.mmada_image_probs_m(h, il[:N].data_ptr(), il[N:].data_ptr(), 1, N, CB, image_cfg, probs.data_ptr(),
+                                              argmax.data_ptr(), pmax.data_ptr(), st), "mmada_image_probs_m")
+            cur = ids[:, img_start:img_start + N]
+            unknown = cur == mask_id
+            s64 = torch.where(unknown, rng.multinomial(probs, generator).view(1, N), cur - text_vocab)
+            p = torch.gather(probs.view(1, N, CB), -1, s64[..., None]).squeeze(-1)
+            p = torch.where(unknown, p, torch.finfo(p.dtype).max).contiguous()
+            gumbel = (-_log(-_log(rng.uniform_like(p, generator)))).contiguous()
+            s32 = s64.to(torch.int32).contiguous()
+            abi.check(lib.mmada_image_commit_m(h, ids.data_ptr(), 1, L, pos_map.data_ptr(), N, s32.data_ptr(), p.data_ptr(),
+                                               gumbel.data_ptr(), float(temps[i]), mlen_cur.data_ptr(), text_vocab, st),
+                      "mmada_image_commit_m")
+            state["sampled"] = s64
+
+    if graph is None:
+        graph = os.environ.get("MMADA_GRAPH") == "1"
+    graph = (bool(graph) and dev_img and (text_temperature == 0 or dev_text) and trace is None
+             and model.graph_capturable())   # a replayed step would otherwise replay torch's draws
+    graphs, seen = {}, set()
+    ws_epoch = model._ws_epoch
+    side = torch.cuda.Stream(device=device) if graph else None
+    if graph:  # the legacy default stream cannot be captured: the loop runs on a side stream, ordered after the caller's
+        side.wait_stream(torch.cuda.current_stream(device))
+    try:
+        with torch.cuda.stream(side) if graph else contextlib.nullcontext():
+            for i in range(text_steps):
+                is_img = i in img_steps
+                k_cur.copy_(k_dev[i])
+                mlen_cur.copy_(mlen_dev[i:i + 1])
+                if dev_img:
+                    temp_cur.copy_(temp_dev[i:i + 1])
+                if graph and graphs and model._ws_epoch != ws_epoch:
+                    # the workspace moved after all (a foreign forward in between): captured pointers are stale
+                    for g_old in graphs.values():
+                        lib.mmada_graph_destroy(g_old)
+                    graphs.clear()
+                    seen.clear()
+                ws_epoch = model._ws_epoch
+                if graph and is_img in graphs:
+                    abi.check(lib.mmada_graph_launch(graphs[is_img], abi.stream_ptr()), "mmada_graph_launch")
+                    model.graph_replays += 1
+                    continue
+                capture = graph and is_img in seen   # first step of a kind: eager (first calls set attributes / carve)
+                if capture:
+                    abi.check(lib.mmada_graph_begin(abi.stream_ptr()), "mmada_graph_begin")
+                try:
+                    step_body(i, is_img)
+                except Exception:
+                    if capture:
+                        lib.mmada_graph_abort(abi.stream_ptr())
+                    raise
+                if capture:
+                    g = C.c_void_p()
+                    abi.check(lib.mmada_graph_end(abi.stream_ptr(), C.byref(g)), "mmada_graph_end")
+                    graphs[is_img] = g
+                    model.graph_nodes[("interleave", is_img)] = lib.mmada_graph_num_nodes(g)
+                    abi.check(lib.mmada_graph_launch(g, abi.stream_ptr()), "mmada_graph_launch")
+                    model.graph_replays += 1
+                seen.add(is_img)
+        if graph:
+            torch.cuda.current_stream(device).wait_stream(side)   # whoever consumes the ids sees the finished run
+    finally:
+        for g in graphs.values():
+            lib.mmada_graph_destroy(g)
+    check_tp_exchange(model)   # tensor parallel: a timed-out hand-off raises instead of returning void tokens
+    if dev_img and img_steps:
+        state["sampled"] = sampled.long()
+    return state["sampled"], ids[:, text_start:]
+
+
 @torch.no_grad()
 def interleave_generate(
     model,
@@ -78,15 +231,39 @@ def interleave_generate(
     image_temperature: float = 1.0,
     rng=None,
     trace: Optional[list] = None,
+    image_sampler: str = "torch",
+    text_sampler: str = "torch",
+    sampler_seed: Optional[int] = None,
+    graph: Optional[bool] = None,
     **kwargs,
 ):
-    """Returns (image ids [1, num_vq_tokens], text ids [1, max_seq_length]) like the reference."""
+    """Returns (image ids [1, num_vq_tokens], text ids [1, max_seq_length]) like the reference.
+
+    `image_sampler="device"` (opt-in; the default "torch" is the reference's path, draw for draw): an image step is
+    mmada_head_rows, mmada_image_sample_m (col0 = len(tokenizer)) and mmada_image_commit_m_sampled.  Neither the [N, codebook]
+    probabilities nor any torch random tensor exists and `rng` / `generator` are never called for it.  The token is a Gumbel-max draw
+    at temperature 1 over the CFG-combined bf16 logits — it samples their soft-max evaluated in fp32, where the reference's
+    multinomial samples the bf16-rounded probabilities — and the re-mask noise is a counter-based Gumbel value per image position,
+    both keyed by `sampler_seed` (required) and a counter that starts at 1 << 62 per call and advances by 1 per image step.  The
+    re-mask temperature image_temperature * (1 - (i + 1) / text_steps) is host double arithmetic as on the torch path, cast to fp32
+    and copied per step into a device [1] buffer, as k and mask_len are.  One rank only.
+
+    `text_sampler="device"` (opt-in; needs text_temperature > 0): the text draw is mmada_text_draw_cfg on the cond / uncond halves of
+    the text logits — a Gumbel-max draw in fp32 from soft-max(combined / text_temperature) instead of the reference's float64
+    exp(l) / (-log u)^T on a [T, V] float64 copy — keyed by `sampler_seed` and a counter that starts at 0 and advances by 1 per step.
+    The draws of neither sampler reproduce torch's RNG stream.
+
+    `graph` (None = env MMADA_GRAPH=1): replay each kind of step — text-only, image step — as ONE hipGraph (mmada_graph_*), as
+    generate_ti2ti does: the first step of a kind runs eagerly, the second is captured, the rest replay, bit-identical to the eager
+    run.  Only when image_sampler == "device" and (text_temperature == 0 or text_sampler == "device") and trace is None and the
+    forward issues no host-side collective; otherwise the run is eager."""
     if not isinstance(model, LLaDAForMultiModalGeneration):
         raise TypeError("interleave_generate (MI355X) needs mmada_parallel_amd.LLaDAForMultiModalGeneration")
     if remasking != "low_confidence":
         raise NotImplementedError(remasking)
     if not (text_cfg or image_cfg):
         raise ValueError("text_cfg and image_cfg cannot be both 0")  # modeling_mmada.py:176-177
+    dev_img, dev_text = check_m_samplers(model, image_sampler, text_sampler, sampler_seed, text_temperature)
     rng = rng or TorchRng()
     lib, h, device = model._lib, model._handle, model.device
     uni_prompting = kwargs.get("uni_prompting", None)
@@ -128,6 +305,13 @@ def interleave_generate(
     argmax = torch.empty((1, N), dtype=torch.int32, device=device)
     pmax = torch.empty((1, N), dtype=torch.bfloat16, device=device)
     sampled_ids = None
+
+    if dev_img or dev_text:
+        temps = [image_temperature * (1.0 - 1.0 * (i + 1) / text_steps) for i in range(text_steps)]   # host double, as below
+        return _device_steps(model, ids, uncond_input_ids, P, T, N, CB, text_vocab, float(text_cfg), float(image_cfg),
+                             float(text_temperature), text_steps, img_steps, k_dev, mlen_dev, temps, pos_map, text_rows, img_rows,
+                             scratch, argmax, pmax, rng, generator, trace, dev_img, dev_text,
+                             int(sampler_seed) & 0xFFFFFFFFFFFFFFFF, graph)
 
     for i in range(text_steps):
         unc = torch.cat([uncond_input_ids, ids[:, P:]], dim=1)  # :166-169

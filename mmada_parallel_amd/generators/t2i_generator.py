@@ -17,7 +17,7 @@ import torch
 
 from .. import abi
 from ..model import LLaDAForMultiModalGeneration
-from .interleave_generator import TorchRng, _log, cosine_schedule
+from .interleave_generator import TorchRng, _log, check_m_samplers, cosine_schedule
 from .parallel_generator import check_tp_exchange, mask_len_schedule
 
 
@@ -39,14 +39,23 @@ def _t2i_steps(
     codebook_size=8192,
     rng=None,
     trace: Optional[list] = None,
+    image_sampler: str = "torch",
+    sampler_seed: Optional[int] = None,
     **kwargs,
 ):
     """Step generator shared by t2i_generate and t2i_generate_decoding_stepwise: yields (step, sampled_ids) right after
-    the draw of every step (where the stepwise variant decodes, :841-848), then commits the step."""
+    the draw of every step (where the stepwise variant decodes, :841-848), then commits the step.
+
+    `image_sampler="device"` with `sampler_seed` (opt-in, one rank): a step is mmada_head_rows, mmada_image_sample_m and
+    mmada_image_commit_m_sampled as in interleave_generate — no probabilities, no torch random tensor, `rng` / `generator` never
+    called; the counter starts at 1 << 62 and advances by 1 per step.  The cumulative temperature (:349) stays host arithmetic, each
+    step's value handed over through a device [1] buffer.  The commit has then run when the step's sampled ids are yielded (they are
+    the ids it committed from, the same values the torch path computes before its commit)."""
     if not isinstance(model, LLaDAForMultiModalGeneration):
         raise TypeError("t2i_generate (MI355X) needs mmada_parallel_amd.LLaDAForMultiModalGeneration")
     if int(model.config.get("mask_token_id", 126336)) != mask_token_id:
         raise ValueError("mask_token_id differs from the model's")
+    dev_img, _ = check_m_samplers(model, image_sampler, sampler_seed=sampler_seed)
     rng = rng or TorchRng()
     lib, h, device = model._lib, model._handle, model.device
     uni_prompting = kwargs.get("uni_prompting", None)
@@ -66,8 +75,20 @@ def _t2i_steps(
     rows = torch.cat([rows1, rows1 + B * L]).contiguous() if use_cfg else rows1.contiguous()
     argmax = torch.empty((B, N), dtype=torch.int32, device=device)
     pmax = torch.empty((B, N), dtype=torch.bfloat16, device=device)
-    probs = torch.empty((B * N, CB), dtype=torch.bfloat16, device=device)
+    probs = None if dev_img else torch.empty((B * N, CB), dtype=torch.bfloat16, device=device)
     sampled_ids = None
+    if dev_img:
+        seed64 = int(sampler_seed) & 0xFFFFFFFFFFFFFFFF
+        img_counter = torch.full((1,), 1 << 62, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_m_sampled
+        temps, t_run = [], temperature
+        for step in range(timesteps):
+            t_run = t_run * (1.0 - 1.0 * (step + 1) / timesteps)                    # :349 (cumulative), host double as below
+            temps.append(t_run)
+        temp_dev = torch.tensor(temps, dtype=torch.float32, device=device)
+        temp_cur = torch.zeros(1, dtype=torch.float32, device=device)
+        drawn = torch.empty((B, N), dtype=torch.int32, device=device)
+        p_dev = torch.empty((B, N), dtype=torch.bfloat16, device=device)
+        sampled_dev = torch.empty((B, N), dtype=torch.int32, device=device)
 
     for step in range(timesteps):
         if use_cfg:
@@ -81,6 +102,18 @@ def _t2i_steps(
         il = model.head_rows(rows, tok_len, tok_len + CB)
         st = abi.stream_ptr()
         il_c, il_u = (il[:B * N], il[B * N:]) if use_cfg else (il, il)
+        if dev_img:
+            temp_cur.copy_(temp_dev[step:step + 1])
+            abi.check(lib.mmada_image_sample_m(h, il_c.data_ptr(), il_u.data_ptr(), B, N, CB,
+                                               float(guidance_scale) if use_cfg else 0.0, tok_len, seed64, img_counter.data_ptr(),
+                                               drawn.data_ptr(), p_dev.data_ptr(), None, None, st), "mmada_image_sample_m")
+            abi.check(lib.mmada_image_commit_m_sampled(h, ids.data_ptr(), B, L, pos_map.data_ptr(), N, drawn.data_ptr(),
+                                                       p_dev.data_ptr(), temp_cur.data_ptr(), seed64, img_counter.data_ptr(),
+                                                       mlen_dev[step:step + 1].data_ptr(), tok_len, sampled_dev.data_ptr(), st),
+                      "mmada_image_commit_m_sampled")
+            sampled_ids = sampled_dev.long()
+            yield step, sampled_ids
+            continue
         abi.check(lib.mmada_image_probs_m(h, il_c.data_ptr(), il_u.data_ptr(), B, N, CB,
                                           float(guidance_scale) if use_cfg else 0.0, probs.data_ptr(), argmax.data_ptr(),
                                           pmax.data_ptr(), st), "mmada_image_probs_m")
@@ -106,12 +139,15 @@ def _t2i_steps(
 def t2i_generate(model, input_ids=None, uncond_input_ids=None, attention_mask=None, uncond_attention_mask=None,
                  temperature=1.0, timesteps=18, guidance_scale=0, noise_schedule: Callable = cosine_schedule,
                  generator: torch.Generator = None, config=None, seq_len=1024, mask_token_id=126336, resolution=512,
-                 codebook_size=8192, rng=None, trace: Optional[list] = None, **kwargs):
-    """Returns sampled_ids [B, seq_len] (codebook ids) like the reference (:358); `input_ids` is updated in place."""
+                 codebook_size=8192, rng=None, trace: Optional[list] = None, image_sampler: str = "torch",
+                 sampler_seed: Optional[int] = None, **kwargs):
+    """Returns sampled_ids [B, seq_len] (codebook ids) like the reference (:358); `input_ids` is updated in place.
+    `image_sampler="device"` with `sampler_seed`: the draws run in the image kernels (see _t2i_steps)."""
     sampled_ids = None
     for _step, sampled_ids in _t2i_steps(model, input_ids, uncond_input_ids, attention_mask, uncond_attention_mask,
                                          temperature, timesteps, guidance_scale, noise_schedule, generator, config, seq_len,
-                                         mask_token_id, resolution, codebook_size, rng, trace, **kwargs):
+                                         mask_token_id, resolution, codebook_size, rng, trace, image_sampler, sampler_seed,
+                                         **kwargs):
         pass
     check_tp_exchange(model)   # tensor parallel: a timed-out hand-off raises instead of returning void tokens
     return sampled_ids
@@ -122,14 +158,15 @@ def t2i_generate_decoding_stepwise(model, input_ids=None, uncond_input_ids=None,
                                    uncond_attention_mask=None, temperature=1.0, timesteps=18, guidance_scale=0,
                                    noise_schedule: Callable = cosine_schedule, generator: torch.Generator = None, config=None,
                                    seq_len=1024, mask_token_id=126336, resolution=512, codebook_size=8192, vq_model=None,
-                                   rng=None, **kwargs):
+                                   rng=None, image_sampler: str = "torch", sampler_seed: Optional[int] = None, **kwargs):
     """modeling_mmada.py:768-875: t2i_generate that decodes the current samples after every step and yields
     (PIL image of batch element 0, "Step i/T").  `vq_model` is anything with decode_code (mmada_parallel_amd.MAGVITv2)."""
     from PIL import Image
 
     for step, sampled_ids in _t2i_steps(model, input_ids, uncond_input_ids, attention_mask, uncond_attention_mask,
                                         temperature, timesteps, guidance_scale, noise_schedule, generator, config, seq_len,
-                                        mask_token_id, resolution, codebook_size, rng, None, **kwargs):
+                                        mask_token_id, resolution, codebook_size, rng, None, image_sampler, sampler_seed,
+                                        **kwargs):
         if step == timesteps - 1:
             check_tp_exchange(model)
         cur = torch.clamp(sampled_ids.clone(), 0, 8192 - 1)                         # :839-840 (constant as in the reference)
