@@ -408,6 +408,31 @@ int mmada_image_commit_g(mmada_handle* h, int64_t* ids, int B, int L, const int3
                          const int32_t* sampled_in, const void* p_in, const void* gumbel, float remask_temp,
                          const int32_t* keep_n, int text_vocab_size, void* stream);
 
+/* The generate_image step with both draws on the device (generate_image(image_sampler="device")): no probabilities, no torch random
+ * tensor, and the head may run on every image slot, so a step has one shape and replays as a captured graph.
+ *
+ * mmada_image_sample_g replaces mmada_image_probs_m + gumbel_max_sample + gather (generators/image_generation_generator.py:152-167,
+ * utils/generation_utils.py:42-45): mmada_image_sample_m with a temperature,
+ *   sampled_out[b,n] = first-index arg-max over i < CB of  fadd_rn(l_i, fmul_rn(temperature, g(seed, *counter, r, col0 + i))),
+ * r = b*N + n, l_i = bf16(bf16((1 + cfg_scale) * c_i) - bf16(cfg_scale * u_i)) — the key of mmada_head_sample and
+ * mmada_text_draw_cfg.  It samples softmax(l / temperature) evaluated in fp32; the reference's bf16 l / temperature + gumbel has the
+ * same arg-max in exact arithmetic (and another RNG stream).  p_sel_out, argmax_out (NULL = skip) and pmax_out (NULL = skip) are the
+ * bits of mmada_image_probs_m: the soft-max of the UNSCALED l.  temperature: finite and >= 0, anything else is an error; at 0 the
+ * draw is the first-index arg-max of l and no generator runs; at 1 every output equals mmada_image_sample_m's.  counter: read, never
+ * written.  Limits of mmada_image_sample.
+ *
+ * mmada_image_commit_g_sampled replaces the rand + two logs of mask_by_random_topk (utils/generation_utils.py:57) + mmada_image_commit_g:
+ * mmada_image_commit_g with gumbel[b,n] = bf16(g_remask(seed, *counter, b*N + n)) (mmada_sample_remask_gumbel, the value
+ * mmada_image_commit_m_sampled uses) computed in the kernel.  remask_temp stays by value: generate_image passes its constant
+ * temperature.  keep_n: device int32 [1].  With no unknown slot no id changes.  *counter is incremented by 1 by the call's last
+ * kernel. */
+int mmada_image_sample_g(mmada_handle* h, const void* cond, const void* uncond, int B, int N, int CB, float cfg_scale,
+                         float temperature, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out, void* p_sel_out,
+                         int32_t* argmax_out, void* pmax_out, void* stream);
+int mmada_image_commit_g_sampled(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
+                                 const int32_t* sampled_in, const void* p_in, float remask_temp, uint64_t seed, uint64_t* counter,
+                                 const int32_t* keep_n, int text_vocab_size, void* stream);
+
 /* (M variant) LFQ codebook gather, MMaDA-Parallel-M/models/modeling_magvitv2.py:186-194,208-221:
  * out[b, c, n] = 2·bit_c(idx[b,n]) − 1 as bf16/f32, c in [0,nbits) with bit 0 = most significant
  * (mask = 2^(nbits-1-c)).  idx: device int64 [B,N]; out: device [B,nbits,N] (dtype_f32 ? float : bf16). */

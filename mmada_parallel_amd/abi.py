@@ -104,6 +104,10 @@ SIGNATURES = {
     "mmada_sample_remask_gumbel": (c_float, [C.c_uint64, C.c_uint64, C.c_uint32]),
     "mmada_image_commit_g": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_float, c_void_p, c_int, c_void_p]),
+    "mmada_image_sample_g": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int, C.c_uint64,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mmada_image_commit_g_sampled": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_float,
+                                             C.c_uint64, c_void_p, c_void_p, c_int, c_void_p]),
     "mmada_lfq_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mmada_profile_begin": (c_int, [c_void_p, c_int]),
     "mmada_profile_end": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

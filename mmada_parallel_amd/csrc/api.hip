@@ -357,6 +357,27 @@ int mmada_image_commit_m_sampled(mmada_handle* h, int64_t* ids, int B, int L, co
                                        (hipStream_t)stream);
 }
 
+int mmada_image_sample_g(mmada_handle* h, const void* cond, const void* uncond, int B, int N, int CB, float cfg_scale,
+                         float temperature, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out, void* p_sel_out,
+                         int32_t* argmax_out, void* pmax_out, void* stream) {
+    if (!h || !cond || !uncond || !counter || !sampled_out || !p_sel_out) return mm_fail("mmada_image_sample_g: null argument");
+    if (!(temperature >= 0.f) || __builtin_isinf(temperature))
+        return mm_fail("mmada_image_sample_g: temperature %g is not a finite value >= 0", (double)temperature);
+    const float one_plus = (float)(1.0 + (double)cfg_scale);  // as mmada_image_probs_m
+    return launch_image_sample((const bf16_t*)cond, (const bf16_t*)uncond, nullptr, B, N, CB, cfg_scale, one_plus, col0, seed,
+                               counter, sampled_out, (bf16_t*)p_sel_out, argmax_out, (bf16_t*)pmax_out, 1, (hipStream_t)stream,
+                               &temperature);
+}
+
+int mmada_image_commit_g_sampled(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
+                                 const int32_t* sampled_in, const void* p_in, float remask_temp, uint64_t seed, uint64_t* counter,
+                                 const int32_t* keep_n, int text_vocab_size, void* stream) {
+    if (!h || !ids || !pos_map || !sampled_in || !p_in || !counter || !keep_n)
+        return mm_fail("mmada_image_commit_g_sampled: null argument");
+    return launch_image_commit_sampled(ids, B, L, pos_map, N, sampled_in, (const bf16_t*)p_in, nullptr, seed, counter, keep_n,
+                                       h->cfg.mask_token_id, text_vocab_size, 0, 2, nullptr, (hipStream_t)stream, remask_temp);
+}
+
 int mmada_text_draw_cfg(mmada_handle* h, const void* cond, const void* uncond, float text_cfg, int B, int T, int V, int ld_logits,
                         float temperature, uint64_t seed, uint64_t* counter, int32_t* x0_out, void* stream) {
     if (!h || !cond || !uncond || !counter || !x0_out) return mm_fail("mmada_text_draw_cfg: null argument");

@@ -159,13 +159,17 @@ int launch_image_commit(int64_t* ids, int B, int L, const int32_t* pos_map, int 
 // mvar != 0: the M variant of either (launch_image_probs / launch_image_commit with mvar = 1): ut = the uncond branch, cfg_scale =
 // image_cfg, cfg_img = 1 + image_cfg; the commit's noise is the Gumbel value of the same block, and sampled_out (M only, may be
 // null) receives the ids the commit writes back from.
+// temperature != null (M combine only): the draw's key is taken at *temperature (finite, >= 0; 0 = the arg-max of the logits), the
+// statistics stay those of the unscaled logits.  mvar == 2 on the commit: launch_image_commit's keep rule (keep_n.clamp(0, unknown -
+// 1), no floor of 1) with remask_temp null and the temperature by value in temp_value.
 int launch_image_sample(const bf16_t* cond, const bf16_t* ut, const bf16_t* ui, int B, int N, int CB, float cfg_scale,
                         float cfg_img, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out,
-                        bf16_t* p_sel_out, int32_t* argmax_out, bf16_t* pmax_out, int mvar, hipStream_t s);
+                        bf16_t* p_sel_out, int32_t* argmax_out, bf16_t* pmax_out, int mvar, hipStream_t s,
+                        const float* temperature = nullptr);
 int launch_image_commit_sampled(int64_t* ids, int B, int L, const int32_t* pos_map, int N, const int32_t* sampled_in,
                                 const bf16_t* p_in, const float* remask_temp, uint64_t seed, uint64_t* counter,
                                 const int32_t* mask_len_sched, int mask_id, int text_vocab, int codebook, int mvar,
-                                int32_t* sampled_out, hipStream_t s);
+                                int32_t* sampled_out, hipStream_t s, float temp_value = 0.0f);
 // the M text draw: x0_out[b*T + t] = arg-max of the CFG-combined logits' keys at (seed, *counter); its last launch adds 1 to *counter
 int launch_text_draw_cfg(const bf16_t* cond, const bf16_t* unc, float text_cfg, int B, int T, int V, int ld, float temperature,
                          uint64_t seed, uint64_t* counter, int32_t* x0_out, hipStream_t s);

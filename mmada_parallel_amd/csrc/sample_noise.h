@@ -23,6 +23,9 @@
 //   g_remask = -log(-log(u(word0)))     word0 as above: = g(seed ^ SAMPLE_NORMAL_KEY_XOR, counter, row r, column 0)
 // and the commit uses g_remask rounded to bf16 (the reference's uniform_ and its two logs are bf16 tensors).  The M text draw
 // (mmada_text_draw_cfg) is sample_key over the CFG-combined logits with g(seed, counter, row b * T + t, column v).
+//
+// The generate_image step (mmada_image_sample_g, mmada_image_commit_g_sampled) draws its tokens with sample_key at the run's
+// temperature — key = l + T * g, the row-head's key — and re-masks with the same g_remask rounded to bf16.
 #pragma once
 #include <math.h>
 #include <stdint.h>

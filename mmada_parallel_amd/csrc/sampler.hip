@@ -363,13 +363,19 @@ MM_DEVICE int block_argmax(float best, int bidx, float* s_v, int* s_x, float* be
 // MVAR (interleave_generate / t2i_generate with image_sampler="device": replaces torch.multinomial + gather, modeling_mmada.py:220-222,
 // :229-231): the sibling of image_probs_kernel<true> — ut = the uncond branch, cfg_scale = image_cfg, cfg_img = 1 + image_cfg
 // (host-computed), l_i = cfg_combine_m; everything after the combine is the same code.
-template <bool MVAR>
+// TEMP (generate_image with image_sampler="device": replaces gumbel_max_sample + gather, generators/image_generation_generator.py:152-167):
+// the key is sample_key(l_i, temperature, g) — the key of mmada_head_sample and text_draw_cfg_kernel — so the draw samples
+// softmax(l / temperature) evaluated in fp32 (the reference's bf16 l / temperature + g has the same arg-max in exact arithmetic);
+// temperature == 0: the plain first-index arg-max of l, no generator runs.  The statistics stay those of the UNSCALED l.  !TEMP:
+// `temperature` is not read and the key is taken at the constant 1, the code the A and M steps have always run.
+template <bool MVAR, bool TEMP>
 __global__ __launch_bounds__(TB) void image_sample_kernel(const bf16_t* __restrict__ cond, const bf16_t* __restrict__ ut,
                                                           const bf16_t* __restrict__ ui, int CB, float cfg_scale,
                                                           float cfg_img, uint32_t col0, uint64_t seed,
                                                           const uint64_t* __restrict__ counter,
                                                           int32_t* __restrict__ sampled_out, bf16_t* __restrict__ p_sel_out,
-                                                          int32_t* __restrict__ argmax_out, bf16_t* __restrict__ pmax_out) {
+                                                          int32_t* __restrict__ argmax_out, bf16_t* __restrict__ pmax_out,
+                                                          float temperature) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* e = (float*)smem;  // [CB]: l_i, then e_i
     __shared__ float s_f[TB / 64];
@@ -417,16 +423,18 @@ __global__ __launch_bounds__(TB) void image_sample_kernel(const bf16_t* __restri
     // the draw, while e still holds the logits: one Philox block per four columns of the whole vocabulary, whatever col0 & 3 is
     const uint64_t ctr = *counter;
     const uint32_t blk0 = col0 >> 2, nblk = ((col0 + (uint32_t)CB - 1u) >> 2) - blk0 + 1u;
+    const bool noisy = !TEMP || temperature != 0.0f;
     float kbest = -INFINITY;
     int kidx = 0x7fffffff;
     for (uint32_t q = tid; q < nblk; q += TB) {
-        uint32_t w0, w1, w2, w3;
-        sample_words4(seed, ctr, (uint32_t)row, blk0 + q, w0, w1, w2, w3);
+        uint32_t w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u;
+        if (noisy) sample_words4(seed, ctr, (uint32_t)row, blk0 + q, w0, w1, w2, w3);
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
             const int i = (int)(((blk0 + q) << 2) + j - col0);  // ascends per thread -> first index kept
             if (i < 0 || i >= CB) continue;
-            const float key = sample_key(e[i], 1.0f, sample_gumbel(sample_pick(w0, w1, w2, w3, j)));
+            float key = e[i];
+            if (noisy) key = sample_key(key, TEMP ? temperature : 1.0f, sample_gumbel(sample_pick(w0, w1, w2, w3, j)));
             if (key > kbest) { kbest = key; kidx = i; }
         }
     }
@@ -549,6 +557,9 @@ __global__ __launch_bounds__(1024) void image_commit_kernel(int64_t* __restrict_
 // gumbel, the cut-off rule rank <= k and the mask_len rule are image_commit_kernel<true>'s.  sampled_out (null = skip): the id each
 // position is committed from, unknown ? sampled_in : vq - text_vocab (the reference's sampled_ids, :224-225), taken from the ids
 // this kernel READS — the barrier before the write-back separates the two.
+// remask_temp == null (generate_image with image_sampler="device", mmada_image_commit_g_sampled): the temperature is the by-value
+// temp_value, a constant of the whole run there.  keep_rule: image_commit_kernel's — k = keep_n.clamp(0, unknown - 1), no floor of
+// 1 — so a step with nothing unknown has k = 0 and rewrites every id with itself.
 template <bool MVAR>
 __global__ __launch_bounds__(1024) void image_commit_sampled_kernel(int64_t* __restrict__ ids, int L,
                                                                     const int32_t* __restrict__ pos_map, int N,
@@ -558,7 +569,8 @@ __global__ __launch_bounds__(1024) void image_commit_sampled_kernel(int64_t* __r
                                                                     const uint64_t* __restrict__ counter,
                                                                     const int32_t* __restrict__ mask_len_sched, int mask_id,
                                                                     int text_vocab, int codebook,
-                                                                    int32_t* __restrict__ sampled_out) {
+                                                                    int32_t* __restrict__ sampled_out, float temp_value,
+                                                                    int keep_rule) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* conf = (float*)smem;          // [N] bf16-valued
     int* samp = (int*)(conf + N);        // [N]
@@ -566,7 +578,7 @@ __global__ __launch_bounds__(1024) void image_commit_sampled_kernel(int64_t* __r
     const int b = blockIdx.x, tid = threadIdx.x;
     if (tid == 0) s_unknown = 0;
     __syncthreads();
-    const float temp = remask_temp[0];
+    const float temp = remask_temp ? remask_temp[0] : temp_value;
     const uint64_t ctr = *counter;
     int64_t* row = ids + (size_t)b * L;
     int my_unknown = 0;
@@ -595,7 +607,8 @@ __global__ __launch_bounds__(1024) void image_commit_sampled_kernel(int64_t* __r
     }
     if (my_unknown) atomicAdd(&s_unknown, my_unknown);
     __syncthreads();
-    int k = max(1, min(s_unknown - 1, mask_len_sched[0]));
+    int k = min(s_unknown - 1, mask_len_sched[0]);
+    k = keep_rule ? max(0, k) : max(1, k);
     k = max(0, min(k, N - 1));
     for (int n = tid; n < N; n += blockDim.x) {
         const float c = conf[n];
@@ -742,22 +755,28 @@ int launch_image_commit(int64_t* ids, int B, int L, const int32_t* pos_map, int 
 
 int launch_image_sample(const bf16_t* cond, const bf16_t* ut, const bf16_t* ui, int B, int N, int CB, float cfg_scale,
                         float cfg_img, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out,
-                        bf16_t* p_sel_out, int32_t* argmax_out, bf16_t* pmax_out, int mvar, hipStream_t s) {
+                        bf16_t* p_sel_out, int32_t* argmax_out, bf16_t* pmax_out, int mvar, hipStream_t s, const float* temperature) {
     if (CB <= 0 || CB % 8 || CB > 16384) return mm_fail("image_sample: codebook=%d must be a multiple of 8 and <= 16384", CB);
     if (col0 < 0 || col0 > INT32_MAX - CB) return mm_fail("image_sample: col0=%d is not a column of the vocabulary", col0);
     if (B * N <= 0) return 0;
     static MmOncePerDevice attr_set;
     MM_ONCE_PER_DEVICE(attr_set,
-        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_sample_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_sample_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          16384 * 4));
-        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_sample_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         16384 * 4));
+        MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_sample_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          16384 * 4)));
-    if (mvar)
-        hipLaunchKernelGGL(image_sample_kernel<true>, dim3(B * N), dim3(TB), (size_t)CB * 4, s, cond, ut, ui, CB, cfg_scale,
-                           cfg_img, (uint32_t)col0, seed, counter, sampled_out, p_sel_out, argmax_out, pmax_out);
+    if (temperature) {
+        if (!mvar) return mm_fail("image_sample: a temperature goes with the M combine only");
+        hipLaunchKernelGGL((image_sample_kernel<true, true>), dim3(B * N), dim3(TB), (size_t)CB * 4, s, cond, ut, ui, CB, cfg_scale,
+                           cfg_img, (uint32_t)col0, seed, counter, sampled_out, p_sel_out, argmax_out, pmax_out, *temperature);
+    } else if (mvar)
+        hipLaunchKernelGGL((image_sample_kernel<true, false>), dim3(B * N), dim3(TB), (size_t)CB * 4, s, cond, ut, ui, CB, cfg_scale,
+                           cfg_img, (uint32_t)col0, seed, counter, sampled_out, p_sel_out, argmax_out, pmax_out, 1.0f);
     else
-        hipLaunchKernelGGL(image_sample_kernel<false>, dim3(B * N), dim3(TB), (size_t)CB * 4, s, cond, ut, ui, CB, cfg_scale,
-                           cfg_img, (uint32_t)col0, seed, counter, sampled_out, p_sel_out, argmax_out, pmax_out);
+        hipLaunchKernelGGL((image_sample_kernel<false, false>), dim3(B * N), dim3(TB), (size_t)CB * 4, s, cond, ut, ui, CB, cfg_scale,
+                           cfg_img, (uint32_t)col0, seed, counter, sampled_out, p_sel_out, argmax_out, pmax_out, 1.0f);
     MM_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -765,9 +784,10 @@ int launch_image_sample(const bf16_t* cond, const bf16_t* ut, const bf16_t* ui, 
 int launch_image_commit_sampled(int64_t* ids, int B, int L, const int32_t* pos_map, int N, const int32_t* sampled_in,
                                 const bf16_t* p_in, const float* remask_temp, uint64_t seed, uint64_t* counter,
                                 const int32_t* mask_len_sched, int mask_id, int text_vocab, int codebook, int mvar,
-                                int32_t* sampled_out, hipStream_t s) {
+                                int32_t* sampled_out, hipStream_t s, float temp_value) {
     if (B <= 0 || N <= 0) return 0;
     if (N > 8192) return mm_fail("image_commit_sampled: N=%d too large", N);
+    if (mvar == 2 ? remask_temp != nullptr : !remask_temp) return mm_fail("image_commit_sampled: the temperature is by value with the keep rule only");
     static MmOncePerDevice attr_set;  // as launch_image_commit: above the 64 KiB default near N = 8192
     MM_ONCE_PER_DEVICE(attr_set,
         MM_CHECK_HIP(hipFuncSetAttribute((const void*)image_commit_sampled_kernel<false>,
@@ -776,10 +796,12 @@ int launch_image_commit_sampled(int64_t* ids, int B, int L, const int32_t* pos_m
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8)));
     if (mvar)
         hipLaunchKernelGGL(image_commit_sampled_kernel<true>, dim3(B), dim3(1024), (size_t)N * 8, s, ids, L, pos_map, N,
-                           sampled_in, p_in, remask_temp, seed, counter, mask_len_sched, mask_id, text_vocab, codebook, sampled_out);
+                           sampled_in, p_in, remask_temp, seed, counter, mask_len_sched, mask_id, text_vocab, codebook, sampled_out,
+                           temp_value, mvar == 2);
     else
         hipLaunchKernelGGL(image_commit_sampled_kernel<false>, dim3(B), dim3(1024), (size_t)N * 8, s, ids, L, pos_map, N,
-                           sampled_in, p_in, remask_temp, seed, counter, mask_len_sched, mask_id, text_vocab, codebook, nullptr);
+                           sampled_in, p_in, remask_temp, seed, counter, mask_len_sched, mask_id, text_vocab, codebook, nullptr,
+                           0.0f, 0);
     MM_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(counter_bump_kernel, dim3(1), dim3(1), 0, s, counter);
     MM_CHECK_HIP(hipGetLastError());

@@ -11,10 +11,17 @@ arithmetic; the argument is accepted and has no effect here either.
 
 Random draws (temperature > 0) go through an `rng` object (default: torch's RNG calls in the reference's order) so that
 parity tests can replay the reference's draws; at temperature 0 the path is deterministic and bit-exact.
+
+Opt-in, `image_sampler="device"` with `sampler_seed`: the draws run inside the kernels (mmada_image_sample_g,
+mmada_image_commit_g_sampled) on the counter-based generator of csrc/sample_noise.h, every step has the same shape and reads
+nothing on the host, and a step can replay as one hipGraph (`graph=True`); see generate_image.
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes as C
 import math
+import os
 from typing import Callable, Optional
 
 import torch
@@ -55,6 +62,118 @@ def keep_schedule(vq_len: int, timesteps: int, noise_schedule: Callable = cosine
     return out
 
 
+def check_image_sampler(model, image_sampler, sampler_seed, temperature):
+    """The refusals of generate_image's device sampler, in generate_ti2ti's wording; returns whether it is on."""
+    if image_sampler not in ("torch", "device"):
+        raise ValueError(f"image_sampler={image_sampler!r}: 'torch' or 'device'")
+    if image_sampler != "device":
+        return False
+    why = None
+    if not temperature > 0:
+        why = "temperature > 0 (at 0 the image step is an arg-max: nothing is drawn)"
+    elif model.tp_size != 1 or model._comm_in_library:
+        why = "one rank (tensor parallelism is out of scope)"
+    elif sampler_seed is None:
+        why = "sampler_seed"
+    if why:
+        raise ValueError(f"image_sampler='device' needs {why}")
+    return True
+
+
+def _device_image_steps(model, x, slots, win, keep, timesteps, temperature, cfg_scale, uncon_ids, code_start, off, CB, seed64, graph,
+                        trace, debug):
+    """generate_image's loop with the device sampler: the same forwards, then mmada_image_sample_g and mmada_image_commit_g_sampled
+    over buffers that all exist before the loop.  The head runs on ALL N slots every step (the commit ignores the draws at known
+    slots), so a step has one shape, takes no argument that changes from step to step and reads nothing on the host; it can be
+    captured and replayed (the scheme of interleave_generator._device_steps).  There is no early exit: a step with nothing unknown
+    re-masks nothing (k = 0) and rewrites every id with itself."""
+    lib, h, device = model._lib, model._handle, model.device
+    L, N = x.shape[1], int(slots.numel())
+    use_cfg = cfg_scale > 0
+    pos_map = slots.to(torch.int32).contiguous()
+    cond = torch.empty((N, CB), dtype=torch.bfloat16, device=device)
+    unc = cond
+    if use_cfg:
+        U, tail = uncon_ids.shape[1], code_start - 2
+        unc_seq = torch.empty((1, U + L - tail), dtype=torch.long, device=device)
+        unc_seq[:, :U].copy_(uncon_ids)                                   # the prefix, once; the tail is refreshed every step
+        urows = (pos_map - tail + U).contiguous()                         # uncond_vq_mask (:124)
+        uwin = (win[0] - tail + U, win[1] - tail + U)
+        unc = torch.empty((N, CB), dtype=torch.bfloat16, device=device)
+        # before the first step: a workspace that grew later would leave a captured graph pointing at freed memory
+        model._ensure_ws(1, max(L, unc_seq.shape[1]))
+    else:
+        model._ensure_ws(1, L)
+    drawn = torch.empty((1, N), dtype=torch.int32, device=device)
+    p_sel = torch.empty((1, N), dtype=torch.bfloat16, device=device)
+    keep_cur = torch.zeros(1, dtype=torch.int32, device=device)
+    counter = torch.full((1,), 1 << 62, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_g_sampled
+
+    def step_body():
+        if trace is not None:
+            trace.append(x.cpu().clone())
+        model.forward_body(x, consumed=win)
+        model.head_rows(pos_map, off, off + CB, out=cond)                 # every slot, known or not
+        if use_cfg:
+            unc_seq[:, U:].copy_(x[:, tail:])                             # :123
+            if trace is not None:
+                trace.append(unc_seq.cpu().clone())
+            model.forward_body(unc_seq, consumed=uwin)
+            model.head_rows(urows, off, off + CB, out=unc)
+        st = abi.stream_ptr()
+        abi.check(lib.mmada_image_sample_g(h, cond.data_ptr(), unc.data_ptr(), 1, N, CB, float(cfg_scale) if use_cfg else 0.0,
+                                           float(temperature), off, seed64, counter.data_ptr(), drawn.data_ptr(), p_sel.data_ptr(),
+                                           None, None, st), "mmada_image_sample_g")
+        abi.check(lib.mmada_image_commit_g_sampled(h, x.data_ptr(), 1, L, pos_map.data_ptr(), N, drawn.data_ptr(), p_sel.data_ptr(),
+                                                   float(temperature), seed64, counter.data_ptr(), keep_cur.data_ptr(), off, st),
+                  "mmada_image_commit_g_sampled")
+
+    if graph is None:
+        graph = os.environ.get("MMADA_GRAPH") == "1"
+    graph = bool(graph) and trace is None and model.graph_capturable()
+    g_step, seen = None, False
+    ws_epoch = model._ws_epoch
+    side = torch.cuda.Stream(device=device) if graph else None
+    if graph:  # the legacy default stream cannot be captured: the loop runs on a side stream, ordered after the caller's
+        side.wait_stream(torch.cuda.current_stream(device))
+    try:
+        with torch.cuda.stream(side) if graph else contextlib.nullcontext():
+            for step in range(timesteps if N else 0):
+                keep_cur.copy_(keep[step:step + 1])
+                if g_step is not None and model._ws_epoch != ws_epoch:
+                    # the workspace moved after all (a foreign forward in between): captured pointers are stale
+                    lib.mmada_graph_destroy(g_step)
+                    g_step, seen = None, False
+                ws_epoch = model._ws_epoch
+                if g_step is not None:
+                    abi.check(lib.mmada_graph_launch(g_step, abi.stream_ptr()), "mmada_graph_launch")
+                    model.graph_replays += 1
+                    continue
+                capture = graph and seen   # the first step runs eagerly (first calls set attributes / carve)
+                if capture:
+                    abi.check(lib.mmada_graph_begin(abi.stream_ptr()), "mmada_graph_begin")
+                try:
+                    step_body()
+                except Exception:
+                    if capture:
+                        lib.mmada_graph_abort(abi.stream_ptr())
+                    raise
+                if capture:
+                    g = C.c_void_p()
+                    abi.check(lib.mmada_graph_end(abi.stream_ptr(), C.byref(g)), "mmada_graph_end")
+                    g_step = g
+                    model.graph_nodes[("generate_image",)] = lib.mmada_graph_num_nodes(g)
+                    abi.check(lib.mmada_graph_launch(g, abi.stream_ptr()), "mmada_graph_launch")   # the captured step's own run
+                seen = True
+                if debug:
+                    print(f"[generate_image] step {step}: keep {int(keep[step])}")
+        if graph:
+            torch.cuda.current_stream(device).wait_stream(side)   # whoever consumes the ids sees the finished run
+    finally:
+        if g_step is not None:
+            lib.mmada_graph_destroy(g_step)
+
+
 @torch.no_grad()
 def generate_image(
     model,
@@ -82,13 +201,31 @@ def generate_image(
     max_print_tokens: int = 100,
     rng=None,
     trace: Optional[list] = None,
+    image_sampler: str = "torch",
+    sampler_seed: Optional[int] = None,
+    graph: Optional[bool] = None,
 ) -> torch.LongTensor:
     """Returns vq_ids [1, seq_len] (token ids in the full vocabulary, newlines removed), like the reference :239-250.
-    `debug` only prints one line per step (the reference's per-step dumps are host-side diagnostics)."""
+    `debug` only prints one line per step (the reference's per-step dumps are host-side diagnostics).
+
+    `image_sampler="device"` (opt-in; the default "torch" is the reference's path, draw for draw; needs temperature > 0, `sampler_seed`
+    and one rank, anything else raises ValueError): a step is mmada_head_rows on ALL image slots, mmada_image_sample_g (col0 =
+    text_vocab_size) and mmada_image_commit_g_sampled.  Neither the [n, codebook] probabilities nor any torch random tensor exists
+    and `rng` / `generator` are never called.  The token is a Gumbel-max draw from soft-max(l / temperature) evaluated in fp32 on the
+    bf16 CFG-combined logits l — the reference's bf16 l / temperature + gumbel has the same arg-max in exact arithmetic — and the
+    re-mask noise is a counter-based Gumbel value per slot.  Both are keyed by `sampler_seed` and a counter that starts at 1 << 62
+    per call and advances by 1 per step; the noise row of a slot is its index in the slot list, whatever is still masked.  The loop
+    reads nothing on the host: it runs all `timesteps` (a step with nothing unknown changes no id, where the torch path leaves
+    early).  The draws do not reproduce torch's RNG stream.
+
+    `graph` (None = env MMADA_GRAPH=1): on the device path, with trace is None and a forward that issues no host-side collective,
+    the step replays as ONE hipGraph — the first step runs eagerly, the second is captured, the rest replay, bit-identical to the
+    eager run.  With image_sampler="torch" it has no effect."""
     if not isinstance(model, LLaDAForMultiModalGeneration):
         raise TypeError("generate_image (MI355X) needs mmada_parallel_amd.LLaDAForMultiModalGeneration")
     if temperature > 8.0:
         raise ValueError("temperature > 8 is not supported (known slots must out-rank every noisy confidence)")
+    dev_img = check_image_sampler(model, image_sampler, sampler_seed, temperature)
     rng = rng or TorchRng()
     lib, h, device = model._lib, model._handle, model.device
     prompt = prompt.to(device)
@@ -113,6 +250,12 @@ def generate_image(
             raise ValueError("masked tokens before code_start - 2 are dropped from the unconditional sequence")
     keep = torch.tensor(keep_schedule(vq_len, timesteps, noise_schedule), dtype=torch.int32, device=device)
     win = (int(slots[0]), int(slots[-1]) + 1) if N else None   # the only rows ever decoded (one host read, before the loop)
+    if dev_img:
+        _device_image_steps(model, x, slots, win, keep, timesteps, temperature, cfg_scale, uncon_ids, code_start, off, CB,
+                            int(sampler_seed) & 0xFFFFFFFFFFFFFFFF, graph, trace, debug)
+        check_tp_exchange(model)
+        vq_ids = x[0, code_start:-2]                                   # :239-241
+        return vq_ids[vq_ids != newline_id].view(1, seq_len)
     pos_map = slots.to(torch.int32).contiguous()
     argmax = torch.empty((1, N), dtype=torch.int32, device=device)
     pmax = torch.empty((1, N), dtype=torch.bfloat16, device=device)

@@ -67,15 +67,17 @@ def _log(t, eps=1e-20):
     return torch.log(t.clamp(min=eps))  # sampling.py:11-12
 
 
-def check_m_samplers(model, image_sampler, text_sampler="torch", sampler_seed=None, text_temperature=0.0):
-    """The refusals of the M generators' device samplers, in generate_ti2ti's wording; returns (dev_img, dev_text)."""
+def check_m_samplers(model, image_sampler, text_sampler="torch", sampler_seed=None, text_temperature=0.0,
+                     temperature_name="text_temperature"):
+    """The refusals of the M generators' device samplers, in generate_ti2ti's wording; returns (dev_img, dev_text).
+    temperature_name: what the caller's signature calls the text temperature (mmu_generate: `temperature`)."""
     if text_sampler not in ("torch", "device"):
         raise ValueError(f"text_sampler={text_sampler!r}: 'torch' or 'device'")
     if image_sampler not in ("torch", "device"):
         raise ValueError(f"image_sampler={image_sampler!r}: 'torch' or 'device'")
     dev_img, dev_text = image_sampler == "device", text_sampler == "device"
     if dev_text and not text_temperature > 0:
-        raise ValueError("text_sampler='device' needs text_temperature > 0 (at 0 the text step is an arg-max: nothing is drawn)")
+        raise ValueError(f"text_sampler='device' needs {temperature_name} > 0 (at 0 the text step is an arg-max: nothing is drawn)")
     for name, on in (("text_sampler", dev_text), ("image_sampler", dev_img)):
         if on and (model.tp_size != 1 or model._comm_in_library):
             raise ValueError(f"{name}='device' needs one rank (tensor parallelism is out of scope)")
