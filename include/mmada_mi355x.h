@@ -544,7 +544,9 @@ int mmada_profile_end(mmada_handle* h, int32_t* count_out /*[5]*/, double* ms_ou
  *                    tiles per XCD-round (9904 = the round-4 order; the FETCH_SIZE sweep, tools/tile_order_fetch.py)
  *   "tp_allow_single_rank" 1: mmada_comm_create accepts tp_size == 1 and mmada_forward_body runs a connected one-rank handle through
  *                    the tensor-parallel path (every line of the RCCL / pull transports executes; bit-identical to the plain
- *                    forward: tests/test_gpu_tp.py).  0 (default): tp_size must be 2..8 */
+ *                    forward: tests/test_gpu_tp.py).  0 (default): tp_size must be 2..8
+ *   "tp_emulate_mbps" MB/s (10^6 bytes per second) per link and direction of the emulated link, mmada_comm_set_mode(h, 5); an
+ *                    integer >= 1 (anything else is refused); default: MMADA_TP_EMULATE_MBPS or 76000 */
 int mmada_set_option(const char* name, int value);
 /* The tile configuration the GEMM planner picks for a plain [M, K] x [N, K]^T product (host arithmetic, no launch): 0..3 = the
  * 8-phase configurations in the order above, 1000 + BM = the 16-wave kernel, -1 = unsupported shape.  Honours "gemm_config". */
@@ -622,7 +624,12 @@ int mmada_probe_gemm(mmada_gemm_probe* p, void* stream);
  *                            the pull transport, bytes moved by hipMemcpyAsync / SDMA into local staging, the owner kernel
  *                            reads local memory only, the all-gather half is copies); 3 = DIAGNOSTIC "no exchange": the
  *                            forward runs its owner-side kernels on this rank's own partial sums only (no peer traffic,
- *                            no hand-off; wrong values) — bench.py times it to report the exposed exchange time
+ *                            no hand-off; wrong values) — bench.py times it to report the exposed exchange time;
+ *                            5 = DIAGNOSTIC "emulated link": the data path of 3, and where each half of an exchange would move
+ *                            bytes — same stream, same dependencies — a one-wave kernel that sleeps for ceil(rows / tp) * d * 2
+ *                            bytes over "tp_emulate_mbps" (mmada_set_option) on the device's wall clock: times the exchange
+ *                            SCHEDULE against a fixed-rate, contention-free link on one GPU; a wait above 20 ms is refused
+ *                            before anything is launched.  3 and 5 need a connected transport; the vocabulary-parallel heads refuse both
  *   mmada_comm_set_partition exchange_cus > 0 (a multiple of 8): the exchange stream owns that many CUs (the same number on
  *                            every XCD, hipExtStreamCreateWithCUMask) and the forward's compute kernels run on a library
  *                            stream masked to the other CUs, forked from / joined to the caller's stream by events — the

@@ -3,6 +3,7 @@
 // dLLM cache cache.hip, the LM head heads.hip.  Host code only; every kernel lives in gemm.hip / attention.hip / elementwise.hip /
 // sampler.hip.
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -31,6 +32,7 @@ static struct {
     std::atomic<int> attention_form{-1};     // < 0: the environment's (MMADA_ATTN_FORM, else 1)
     std::atomic<int> probe_variant{0};
     std::atomic<int> tp_allow_single_rank{0};
+    std::atomic<int> tp_emulate_mbps{0};     // 0: the environment's (MMADA_TP_EMULATE_MBPS >= 1, else 76000)
 } g_switches;
 
 static int env_int(const char* name, int fallback) {
@@ -44,12 +46,13 @@ static int env_flag(const char* name) {
 
 Switches switches() {
     static const Switches env = {env_int("MMADA_GEMM_CFG", -1), env_flag("MMADA_GEMM_SILU_LUT"), env_flag("MMADA_GEMM_SHORT_TILES"),
-                                 env_int("MMADA_GEMM_TILE_ORDER", 0), env_int("MMADA_ATTN_FORM", 1), 0, 0};
+                                 env_int("MMADA_GEMM_TILE_ORDER", 0), env_int("MMADA_ATTN_FORM", 1), 0, 0,
+                                 env_int("MMADA_TP_EMULATE_MBPS", 0) >= 1 ? env_int("MMADA_TP_EMULATE_MBPS", 0) : 76000};
     const int cfg = g_switches.gemm_config, lut = g_switches.gemm_silu_lut, shrt = g_switches.gemm_short_tiles,
-              order = g_switches.gemm_tile_order, form = g_switches.attention_form;
+              order = g_switches.gemm_tile_order, form = g_switches.attention_form, mbps = g_switches.tp_emulate_mbps;
     return {cfg == -2 ? env.gemm_config : cfg, lut < 0 ? env.gemm_silu_lut : lut, shrt < 0 ? env.gemm_short_tiles : shrt,
             order < 0 ? env.gemm_tile_order : order, form < 0 ? env.attention_form : form, g_switches.probe_variant,
-            g_switches.tp_allow_single_rank};
+            g_switches.tp_allow_single_rank, mbps < 1 ? env.tp_emulate_mbps : mbps};
 }
 
 // the [text_start, text_start + T) span of the three mmada_text_select* calls lies inside the sequence
@@ -191,17 +194,19 @@ int mmada_set_workspace(mmada_handle* h, void* ws, size_t bytes) {
 
 int mmada_set_option(const char* name, int value) {
     if (!name) return mm_fail("mmada_set_option: null name");
-    static const struct { const char* name; std::atomic<int>* field; bool flag; } table[] = {
-        {"gemm_config", &g_switches.gemm_config, false},
-        {"gemm_silu_lut", &g_switches.gemm_silu_lut, true},
-        {"gemm_short_tiles", &g_switches.gemm_short_tiles, true},
-        {"gemm_tile_order", &g_switches.gemm_tile_order, false},
-        {"attention_form", &g_switches.attention_form, false},
-        {"probe_variant", &g_switches.probe_variant, false},
-        {"tp_allow_single_rank", &g_switches.tp_allow_single_rank, true},
+    static const struct { const char* name; std::atomic<int>* field; bool flag; int least; } table[] = {   // least: smallest value taken
+        {"gemm_config", &g_switches.gemm_config, false, INT_MIN},
+        {"gemm_silu_lut", &g_switches.gemm_silu_lut, true, INT_MIN},
+        {"gemm_short_tiles", &g_switches.gemm_short_tiles, true, INT_MIN},
+        {"gemm_tile_order", &g_switches.gemm_tile_order, false, INT_MIN},
+        {"attention_form", &g_switches.attention_form, false, INT_MIN},
+        {"probe_variant", &g_switches.probe_variant, false, INT_MIN},
+        {"tp_allow_single_rank", &g_switches.tp_allow_single_rank, true, INT_MIN},
+        {"tp_emulate_mbps", &g_switches.tp_emulate_mbps, false, 1},
     };
     for (const auto& o : table)
         if (!strcmp(name, o.name)) {
+            if (value < o.least) return mm_fail("mmada_set_option: '%s' must be an integer >= %d (got %d)", name, o.least, value);
             o.field->store(o.flag ? value != 0 : value);   // flag: nonzero -> 1
             return 0;
         }

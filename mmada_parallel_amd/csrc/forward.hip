@@ -222,6 +222,7 @@ int mmada_forward_body(mmada_handle* h, const int64_t* ids, int B, int L, void* 
         if (!h->tp)
             return mm_fail("mmada_forward_body: tp_size=%d needs a connected collective (mmada_comm_create + "
                            "mmada_comm_connect_*) or the host-issued all-reduce of the segment API", h->cfg.tp_size);
+        if (B > 0 && L > 0 && tp_forward_refused(h, B * ((L + 7) / 8 * 8))) return 1;  // before anything is enqueued
         if (mmada_embed(h, ids, B, L, stream)) return 1;
         return tp_forward_body(h, (hipStream_t)stream);
     }

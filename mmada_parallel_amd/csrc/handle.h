@@ -123,7 +123,9 @@ int check_head_range(const mmada_handle* h, const char* who, int R, int limit, i
 int tp_forward_body(mmada_handle* h, hipStream_t s);              // all blocks of a tensor-parallel forward, after mmada_embed
 int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s);  // residual stream rows of every owner -> [M, d]
 void tp_comm_free(mmada_handle* h);
-bool tp_comm_connected(const mmada_handle* h);   // a transport (or the no-exchange diagnostic) is active on this handle
+bool tp_comm_connected(const mmada_handle* h);   // a transport (or the no-exchange diagnostic / the emulated link) is active on this handle
+// nonzero (mm_fail) when a tensor-parallel forward over M stream rows must not start: the emulated link would wait beyond its cap
+int tp_forward_refused(const mmada_handle* h, int M);
 // this handle's forward is the tensor-parallel one (a connected one-rank group: the tp_allow_single_rank test switch)
 inline bool runs_tensor_parallel(const mmada_handle* h) { return h->cfg.tp_size != 1 || tp_comm_connected(h); }
 // tp_heads.hip

@@ -58,9 +58,11 @@ static inline GemmArgs gemm_bt_args(const bf16_t* A, const bf16_t* W, bf16_t* C,
 
 // The measurement / test switches of mmada_set_option (include/mmada_mi355x.h: what each value means), resolved at one point in
 // time: a switch never set takes the environment's default (MMADA_GEMM_CFG, MMADA_GEMM_SILU_LUT, MMADA_GEMM_SHORT_TILES,
-// MMADA_GEMM_TILE_ORDER, MMADA_ATTN_FORM: parsed once per process).  A launch takes one snapshot and decides everything from it.
+// MMADA_GEMM_TILE_ORDER, MMADA_ATTN_FORM, MMADA_TP_EMULATE_MBPS: parsed once per process).  A launch takes one snapshot and decides
+// everything from it.
 struct Switches {
     int gemm_config, gemm_silu_lut, gemm_short_tiles, gemm_tile_order, attention_form, probe_variant, tp_allow_single_rank;
+    int tp_emulate_mbps;   // >= 1: MB/s per link and direction of the emulated link (mmada_comm_set_mode 5)
 };
 Switches switches();
 

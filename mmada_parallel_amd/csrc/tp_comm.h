@@ -18,6 +18,7 @@ enum TpMode {
     TP_RCCL = 2,
     TP_NO_EXCHANGE = 3,  // DIAGNOSTIC: owner-side kernel on this rank's own partial only (wrong values, timing only)
     TP_COPY = 4,         // copy engines over the mapped peer buffers (connected like pull)
+    TP_EMULATE = 5,      // DIAGNOSTIC: mode 3's data path with a timed wait of bytes / link rate where each transfer would sit
 };
 
 // The four allocations a rank publishes to its peers, in the order of the export record (mmada_comm_create -> connect_ipc)
@@ -98,8 +99,22 @@ struct TpComm {
 
 // the peers' published buffers are mapped: hand-offs by counters, remote reads or copies
 inline bool peers_mapped(const TpComm* c) { return c->mode == TP_PULL || c->mode == TP_COPY; }
-// a transport that really exchanges is connected (not none, not the no-exchange diagnostic)
-inline bool transport_connected(const TpComm* c) { return c && c->mode != TP_NONE && c->mode != TP_NO_EXCHANGE; }
+// a transport that really exchanges is connected (not none, not the no-exchange diagnostic, not the emulated link)
+inline bool transport_connected(const TpComm* c) {
+    return c && c->mode != TP_NONE && c->mode != TP_NO_EXCHANGE && c->mode != TP_EMULATE;
+}
+// the timing-only modes: the owner kernel runs on this rank's own partial, nothing is handed off and no peer is touched
+inline bool exchange_void(const TpComm* c) { return c->mode == TP_NO_EXCHANGE || c->mode == TP_EMULATE; }
+
+// The emulated link (TP_EMULATE).  One phase of an exchange over `rows` stream rows — the reduce-scatter half or the all-gather
+// half — moves ceil(rows / tp) * d bf16 values over each link (a full mesh, every peer's share on a link of its
+// own), so it lasts that many bytes over `mbps` MB/s (10^6 bytes per second, per link and direction), rounded up to a whole
+// nanosecond.  tp.link_wait_ns is the same arithmetic.  No single wait may exceed the cap: 20 MB at 76 GB/s is 0.26 ms.
+constexpr long long LINK_WAIT_CAP_NS = 20 * 1000 * 1000;
+inline long long link_wait_ns(int rows, int d, int tp, int mbps) {
+    const long long bytes = (long long)((rows + tp - 1) / tp) * d * 2;
+    return (bytes * 1000 + mbps - 1) / mbps;
+}
 
 // rank j's published buffers as this rank addresses them -> the table the kernels take
 inline void set_peer(TpPeers& p, int j, void* const buf[PUB_COUNT]) {

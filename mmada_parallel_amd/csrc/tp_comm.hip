@@ -26,6 +26,12 @@
 //                  rank's rows into local staging, then the owner kernel reads LOCAL memory only; the all-gather half is
 //                  tp-1 copies and no kernel.  No compute unit waits on a remote load, so nothing of the exchange competes
 //                  with the GEMMs for CUs except the owner kernel (1/tp of the rows, local operands).
+// Two diagnostics (values void, timing only) share one data path, the owner kernel on this rank's own partial with no hand-off:
+//   no exchange (mode 3)    nothing stands for the transfers: a rank's compute alone.
+//   emulated link (mode 5)  one tp_link_wait_kernel in front of the owner kernel (the reduce-scatter half) and one behind it (the
+//                  all-gather half), on the exchange's stream: each sleeps for the bytes one link would carry over the
+//                  "tp_emulate_mbps" switch.  Forward time in mode 5 minus mode 3 is the exchange time the schedule leaves
+//                  exposed against a fixed-rate link without contention — measurable on one GPU.
 // CU partition (round 5, mmada_comm_set_partition): the 8-phase GEMM's 320x256 tile holds 2 waves x 256 VGPRs per SIMD and
 // 144+ KiB of LDS — while one runs on a CU no exchange wave can be resident there, so "the exchange runs under the next GEMM" was
 // time-slicing at workgroup granularity driven by stream priority.  With a partition the exchange stream is created with a CU
@@ -38,6 +44,7 @@
 // The LM heads on top of these transports (text select, scoring) are tp_heads.hip; the state both units share is tp_comm.h.
 #include <dlfcn.h>
 
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 
@@ -218,6 +225,48 @@ __global__ void tp_flush_kernel() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// The emulated link (mode 5): one wave that does nothing for `ticks` of the device's constant-rate wall clock, counted from its
+// own first read.  It stands where a transfer would sit — same stream, same dependencies — and occupies no CU while it sleeps
+// beyond the one wave slot.  Bounded by construction: the loop ends on elapsed time, never on another agent, and the host caps
+// `ticks` (link_wait_ticks).  No memory is touched, so it is capturable and leaves no state.
+__global__ void tp_link_wait_kernel(long long ticks) {
+    const long long t0 = wall_clock64();
+    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);  // 8 x 64 clocks: well under a microsecond per turn
+}
+
+// kHz of wall_clock64() on the current device (hipDeviceAttributeWallClockRate), asked once per device
+int wall_clock_khz(int* out) {
+    static std::atomic<int> khz[16];
+    int dev = 0;
+    MM_CHECK_HIP(hipGetDevice(&dev));
+    int v = dev >= 0 && dev < 16 ? khz[dev].load(std::memory_order_relaxed) : 0;
+    if (v <= 0) {
+        MM_CHECK_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeWallClockRate, dev));
+        if (v <= 0) return mm_fail("emulated link: the device reports no wall clock rate");
+        if (dev >= 0 && dev < 16) khz[dev].store(v, std::memory_order_relaxed);
+    }
+    *out = v;
+    return 0;
+}
+
+// Ticks of one emulated phase over `rows` stream rows at `mbps`; refuses a wait beyond the cap (nothing is launched by this)
+int link_wait_ticks(const TpComm* c, int rows, int mbps, long long* ticks) {
+    const long long ns = link_wait_ns(rows, c->d, c->size, mbps);
+    if (ns > LINK_WAIT_CAP_NS)
+        return mm_fail("emulated link: one wait of %lld ns (%d rows x %d over %d ranks at tp_emulate_mbps=%d) exceeds the cap of %lld ns "
+                       "(20 ms) per wait", ns, rows, c->d, c->size, mbps, LINK_WAIT_CAP_NS);
+    int khz = 0;
+    if (wall_clock_khz(&khz)) return 1;
+    *ticks = (ns * khz + 999999) / 1000000;
+    return 0;
+}
+
+int launch_link_wait(long long ticks, hipStream_t s) {
+    hipLaunchKernelGGL(tp_link_wait_kernel, dim3(1), dim3(64), 0, s, ticks);
+    MM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 long long default_timeout_ticks() {
     const char* e = getenv("MMADA_TP_TIMEOUT_S");
     const double sec = e ? atof(e) : 20.0;
@@ -249,10 +298,15 @@ int launch_reduce_norm(const ReduceArgs& a, int own, int tp, hipStream_t s) {
 }
 
 // One exchange over rows [m0, m1): partial sums in c->part  ->  x (own rows), xn (all rows) ; on stream s
-int exchange(mmada_handle* h, const Slice& sl, const bf16_t* norm_w, hipStream_t s) {
+// emulate_mbps: the caller's snapshot of the "tp_emulate_mbps" switch (read in mode 5 only)
+int exchange(mmada_handle* h, const Slice& sl, const bf16_t* norm_w, int emulate_mbps, hipStream_t s) {
     TpComm* c = h->tp;
     if (c->mode == TP_NONE) return mm_fail("tensor-parallel forward: no transport connected (mmada_comm_connect_ipc / _local / _rccl)");
     const int d = h->cfg.d_model, tp = c->size, own = sl.r1 - sl.r0;
+    // emulated link: each half of the exchange is one timed wait where its transfer would sit (callers have checked the cap for
+    // every slice before their first launch: emulated_waits_ok)
+    long long wait_ticks = 0;
+    if (c->mode == TP_EMULATE && link_wait_ticks(c, sl.m1 - sl.m0, emulate_mbps, &wait_ticks)) return 1;
     const bool mapped = peers_mapped(c);
     // RCCL: every rank contributes its `slice` rows (rows past M are pad rows of the buffers: never read by a GEMM)
     const size_t cnt = (size_t)sl.slice * d;
@@ -276,8 +330,9 @@ int exchange(mmada_handle* h, const Slice& sl, const bf16_t* norm_w, hipStream_t
         ncclResult_t r = c->nccl.ReduceScatter(c->part + (size_t)sl.m0 * d, c->rs_tmp, cnt, ncclBfloat16, ncclSum, c->comm, s);
         if (r != ncclSuccess) return nccl_fail(c, "ncclReduceScatter", r);
         a.presum = c->rs_tmp;
-    } else if (c->mode == TP_NO_EXCHANGE) {  // diagnostic: the forward without its exchange (bench.py: exposed exchange time = real - this)
+    } else if (exchange_void(c)) {  // diagnostic: the forward without its exchange (bench.py: exposed exchange time = real - this)
         a.presum = c->part + (size_t)sl.r0 * d;
+        if (c->mode == TP_EMULATE && launch_link_wait(wait_ticks, s)) return 1;  // where the pulls / copies / reduce-scatter sit
     }
     if (own > 0 && launch_reduce_norm(a, own, mapped ? tp : 0, s)) return 1;
     // ---- all-gather half ----
@@ -298,7 +353,17 @@ int exchange(mmada_handle* h, const Slice& sl, const bf16_t* norm_w, hipStream_t
         ncclResult_t r = c->nccl.AllGather(c->hn_pub + (size_t)(sl.m0 + c->rank * sl.slice) * d, h->xn + (size_t)sl.m0 * d, cnt,
                                            ncclBfloat16, c->comm, s);
         if (r != ncclSuccess) return nccl_fail(c, "ncclAllGather", r);
+    } else if (c->mode == TP_EMULATE) {  // where the gather kernel / the copies / the all-gather sit
+        if (launch_link_wait(wait_ticks, s)) return 1;
     }
+    return 0;
+}
+
+// Mode 5, before the first launch of a forward / an exchange over M rows: every wait its slices ask for is within the cap
+int emulated_waits_ok(const TpComm* c, const ChunkPlan& plan, int mbps) {
+    long long ticks = 0;
+    for (int k = 0; k < plan.n; ++k)
+        if (link_wait_ticks(c, plan.sl[k].m1 - plan.sl[k].m0, mbps, &ticks)) return 1;
     return 0;
 }
 
@@ -421,6 +486,7 @@ static int tp_forward_body_on(mmada_handle* h, hipStream_t s);
 int tp_forward_body(mmada_handle* h, hipStream_t s_user) {
     TpComm* c = h->tp;
     if (!c || c->mode == TP_NONE) return mm_fail("tensor-parallel forward: no transport connected (mmada_comm_create + connect)");
+    if (tp_forward_refused(h, h->res.M)) return 1;
     if (!c->s_cmp) return tp_forward_body_on(h, s_user);
     // CU partition: the blocks run on the library's masked compute stream, forked from and joined to the caller's stream
     MM_CHECK_HIP(hipEventRecord(c->ev_in, s_user));
@@ -437,6 +503,7 @@ static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
     const int d = h->cfg.d_model, M = h->res.M, nl = h->cfg.n_layers;
     if ((d >> 3) > 64 * MAXCH) return mm_fail("tensor-parallel forward: d_model > %d is not supported", 64 * MAXCH * 8);
     const ChunkPlan plan = chunk_plan(c, M);
+    const int emulate_mbps = switches().tp_emulate_mbps;  // one snapshot for every exchange of this forward
     const double rows_real = (double)h->res.B * h->res.L / M;  // fraction of stream rows that are not padding (FLOP accounting)
     // first RMSNorm of the forward: the embeddings are replicated, no exchange needed
     if (h->res.xn_is_layer0) h->res.xn_is_layer0 = false;  // fused into the embedding kernel
@@ -468,7 +535,7 @@ static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
             }
             MM_CHECK_HIP(hipEventRecord(c->ev_g[k], s));
             MM_CHECK_HIP(hipStreamWaitEvent(c->sc, c->ev_g[k], 0));
-            if (exchange(h, plan.sl[k], w, c->sc)) return 1;
+            if (exchange(h, plan.sl[k], w, emulate_mbps, c->sc)) return 1;
             MM_CHECK_HIP(hipEventRecord(c->ev_c[k], c->sc));
             pending[k] = true;
         }
@@ -520,6 +587,12 @@ int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s) {
 }
 
 bool tp_comm_connected(const mmada_handle* h) { return h->tp && h->tp->mode != TP_NONE; }
+
+int tp_forward_refused(const mmada_handle* h, int M) {
+    const TpComm* c = h->tp;
+    if (!c || c->mode != TP_EMULATE) return 0;
+    return emulated_waits_ok(c, chunk_plan(c, M), switches().tp_emulate_mbps);
+}
 
 void tp_comm_free(mmada_handle* h) {
     TpComm* c = h->tp;
@@ -635,9 +708,9 @@ int mmada_comm_set_timeout(mmada_handle* h, double seconds) {
     return 0;
 }
 
-/* mode: 0 none, 1 pull (IPC / same-process peers), 2 RCCL, 3 the "no exchange" DIAGNOSTIC (the forward's values are void: callers
- * that report results must treat 3 as an error — check_tp_exchange does).  err: != 0 after a hand-off timed out (synchronises
- * `stream`). */
+/* mode: 0 none, 1 pull (IPC / same-process peers), 2 RCCL, 4 copy engines, 3 the "no exchange" DIAGNOSTIC and 5 the emulated link on
+ * top of it (the forward's values are void: callers that report results must treat 3 and 5 as an error — check_tp_exchange
+ * does).  err: != 0 after a hand-off timed out (synchronises `stream`). */
 int mmada_comm_status(mmada_handle* h, int* mode_out, int* err_out, int* finegrained_out, void* stream) {
     if (!h) return mm_fail("mmada_comm_status: null handle");
     if (mode_out) *mode_out = h->tp ? h->tp->mode : 0;
@@ -656,11 +729,13 @@ int mmada_comm_status(mmada_handle* h, int* mode_out, int* err_out, int* finegra
 int mmada_comm_set_mode(mmada_handle* h, int mode) {
     if (!h || !h->tp) return mm_fail("mmada_comm_set_mode: no comm");
     TpComm* c = h->tp;
-    if (mode < TP_PULL || mode > TP_COPY) return mm_fail("mmada_comm_set_mode: mode must be 1 (pull), 2 (RCCL), 3 (diagnostic: no exchange) or 4 (copy engines)");
+    if (mode < TP_PULL || mode > TP_EMULATE)
+        return mm_fail("mmada_comm_set_mode: mode must be 1 (pull), 2 (RCCL), 3 (diagnostic: no exchange), 4 (copy engines) or 5 (diagnostic: emulated link)");
     const int other = c->size == 1 ? 0 : (c->rank == 0 ? 1 : 0);
     if (mode == TP_PULL && !c->peers.ctr[other]) return mm_fail("mmada_comm_set_mode: the pull transport was never connected");
     if (mode == TP_RCCL && !c->comm) return mm_fail("mmada_comm_set_mode: the RCCL transport was never connected");
     if (mode == TP_NO_EXCHANGE && c->mode == TP_NONE) return mm_fail("mmada_comm_set_mode: connect a transport before the no-exchange diagnostic");
+    if (mode == TP_EMULATE && c->mode == TP_NONE) return mm_fail("mmada_comm_set_mode: connect a transport before the emulated link");
     if (mode == TP_COPY && !c->peers.ctr[other]) return mm_fail("mmada_comm_set_mode: the copy transport needs the mapped peer buffers (connect_ipc / connect_local)");
     if (mode == TP_COPY && !c->stage) MM_CHECK_HIP(hipMalloc(&c->stage, c->stage_stride * c->size * 2));  // pull / RCCL users never pay for it
     c->mode = (TpMode)mode;
@@ -733,9 +808,15 @@ void* mmada_comm_part_ptr(mmada_handle* h) { return h && h->tp ? (void*)h->tp->p
 int mmada_comm_exchange(mmada_handle* h, const void* norm_w, void* stream) {
     if (!h || !h->tp || !resident(h) || !norm_w) return mm_fail("mmada_comm_exchange: need a comm and a resident carve (mmada_embed)");
     const Slice sl = chunk_slice(h->res.M, h->tp->size, h->tp->rank, 1, 0);
+    const int emulate_mbps = switches().tp_emulate_mbps;
+    if (h->tp->mode == TP_EMULATE) {  // refuse a wait beyond the cap before anything is launched
+        ChunkPlan one;
+        one.n = 1; one.sl[0] = sl;
+        if (emulated_waits_ok(h->tp, one, emulate_mbps)) return 1;
+    }
     h->res.xn_is_layer0 = false;  // xn is about to be overwritten
     if (peers_mapped(h->tp)) hipLaunchKernelGGL(tp_flush_kernel, dim3(256), dim3(64), 0, (hipStream_t)stream);
-    return exchange(h, sl, (const bf16_t*)norm_w, (hipStream_t)stream);
+    return exchange(h, sl, (const bf16_t*)norm_w, emulate_mbps, (hipStream_t)stream);
 }
 
 int mmada_comm_destroy(mmada_handle* h) {

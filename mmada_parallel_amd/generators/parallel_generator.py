@@ -77,6 +77,9 @@ def check_tp_exchange(model):
         if st["mode"] == "no-exchange diagnostic":
             raise abi.MmadaError("tensor-parallel exchange: the no-exchange diagnostic (mmada_comm_set_mode 3) is still on; "
                                  "the generated tokens are void")
+        if st["mode"] == "emulate":
+            raise abi.MmadaError("tensor-parallel exchange: the emulated link (mmada_comm_set_mode 5) is still on; "
+                                 "the generated tokens are void")
         if st["error"]:
             raise abi.MmadaError(f"tensor-parallel exchange: hand-off timed out waiting for rank {st['error'] - 1} "
                                  f"(transport {st['mode']}); the generated tokens are void")

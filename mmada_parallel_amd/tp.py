@@ -81,6 +81,27 @@ def owned_rows(M: int, rank: int, size: int, n_chunks: int = 2):
     return [(min(m1, m0 + rank * sl), min(m1, m0 + (rank + 1) * sl)) for m0, m1, sl in chunk_slices(M, size, n_chunks)]
 
 
+# ---- the emulated link (mmada_comm_set_mode 5, csrc/tp_comm.h link_wait_ns) ----------------------------------------------
+LINK_WAIT_CAP_NS = 20_000_000   # the library refuses a single wait beyond 20 ms
+DEFAULT_EMULATE_MBPS = 76000    # "tp_emulate_mbps" when neither mmada_set_option nor MMADA_TP_EMULATE_MBPS sets it
+
+
+def link_wait_ns(rows: int, d: int, tp: int, mbps: int) -> int:
+    """Nanoseconds one phase (the reduce-scatter half or the all-gather half) of an exchange over `rows` stream rows waits on the
+    emulated link: ceil(rows / tp) * d bf16 values over one link at `mbps` MB/s (10^6 bytes per second), rounded up."""
+    if rows < 0 or d < 1 or tp < 1 or mbps < 1:
+        raise ValueError(f"link_wait_ns({rows}, {d}, {tp}, {mbps})")
+    nbytes = (rows + tp - 1) // tp * d * 2
+    return (nbytes * 1000 + mbps - 1) // mbps
+
+
+def forward_link_waits_ns(M: int, d: int, tp: int, n_layers: int, mbps: int, n_chunks: int = 2):
+    """Every wait a forward over M stream rows asks of the emulated link, in launch order: per block two exchanges (after attn_out
+    and after ff_out), per exchange and row chunk (chunk_slices) two phases.  sum() of it is the requested wait per forward."""
+    per_exchange = [link_wait_ns(m1 - m0, d, tp, mbps) for m0, m1, _ in chunk_slices(M, tp, n_chunks) for _phase in (0, 1)]
+    return per_exchange * (2 * n_layers)
+
+
 def vocab_slice(V: int, rank: int, size: int) -> Tuple[int, int]:
     """Columns of ff_out.weight rank `rank` multiplies in the vocabulary-parallel text head (mmada_text_select_tp)."""
     w = ((V + size - 1) // size + 7) // 8 * 8

@@ -21,7 +21,43 @@ from . import abi
 MODE_NONE, MODE_PULL, MODE_RCCL, MODE_NO_EXCHANGE, MODE_COPY = 0, 1, 2, 3, 4
 MODE_NAMES = {MODE_NONE: "none", MODE_PULL: "pull", MODE_RCCL: "rccl", MODE_NO_EXCHANGE: "no-exchange diagnostic", MODE_COPY: "copy"}
 MODE_OF = {name: mode for mode, name in MODE_NAMES.items()}
+# The emulated link: the no-exchange data path with a timed wait where each transfer would sit (timing only, values void).  It has
+# tables of its own: MODE_NAMES / MODE_OF are the five modes tests/test_lanes_and_link_host.py pins entry for entry.  mode_name()
+# and mode_of() look through both, and comm_status() / set_transport() go through them.
+MODE_EMULATE = 5
+DIAGNOSTIC_NAMES = {MODE_EMULATE: "emulate"}
+DIAGNOSTIC_OF = {name: mode for mode, name in DIAGNOSTIC_NAMES.items()}
 HOST_ALL_REDUCE = "host all-reduce (torch.distributed)"
+_emulate_mbps = None   # what set_emulate_mbps() last gave the library (the switch is process-wide and has no getter)
+
+
+def mode_name(mode: int) -> str:
+    """What comm_status() calls a mode of mmada_comm_status."""
+    return DIAGNOSTIC_NAMES[mode] if mode in DIAGNOSTIC_NAMES else MODE_NAMES[mode]
+
+
+def mode_of(name: str) -> int:
+    """The mode of mmada_comm_set_mode behind a name of comm_status() / set_transport()."""
+    return DIAGNOSTIC_OF[name] if name in DIAGNOSTIC_OF else MODE_OF[name]
+
+
+def emulate_mbps_in_use() -> int:
+    """The emulated link's rate in use: the last set_emulate_mbps(), else MMADA_TP_EMULATE_MBPS, else 76000 (as the library)."""
+    if _emulate_mbps is not None:
+        return _emulate_mbps
+    try:
+        env = int(os.environ.get("MMADA_TP_EMULATE_MBPS", "0"))
+    except ValueError:
+        env = 0
+    from .tp import DEFAULT_EMULATE_MBPS
+    return env if env >= 1 else DEFAULT_EMULATE_MBPS
+
+
+def set_emulate_mbps(lib, mbps: int) -> None:
+    """mmada_set_option("tp_emulate_mbps", mbps): MB/s per link and direction, an integer >= 1 (the library refuses anything else)."""
+    global _emulate_mbps
+    abi.check(lib.mmada_set_option(b"tp_emulate_mbps", int(mbps)), "mmada_set_option(tp_emulate_mbps)")
+    _emulate_mbps = int(mbps)
 
 
 @dataclass
@@ -30,6 +66,15 @@ class TpLink:
     rows: int = 0                    # stream rows the comm was created for
     transport: Optional[str] = None  # model.tp_collective: "pull" / "copy" / "rccl" / HOST_ALL_REDUCE, None before any connect
     rccl_also: bool = False          # a second, RCCL communicator exists beside a mapped transport (MMADA_TP_PROBE_RCCL)
+    chunks: int = 2                  # row chunks per exchange the comm was created with (MMADA_TP_CHUNKS at mmada_comm_create)
+
+
+def _chunks_at_create() -> int:
+    """What mmada_comm_create makes of MMADA_TP_CHUNKS right now: two row chunks unless it says fewer."""
+    try:
+        return 2 if int(os.environ.get("MMADA_TP_CHUNKS", "2")) >= 2 else 1
+    except ValueError:
+        return 1   # atoi() of a non-number is 0
 
 
 def connect_local_group(ranks, max_rows: int, transport: str = "pull", exchange_cus: int = 0):
@@ -42,7 +87,7 @@ def connect_local_group(ranks, max_rows: int, transport: str = "pull", exchange_
     lib = ranks[0]._lib
     for m in ranks:
         abi.check(lib.mmada_comm_create(m._handle, max_rows, None), "mmada_comm_create")
-        m._link = TpLink(rows=max_rows)
+        m._link = TpLink(rows=max_rows, chunks=_chunks_at_create())
     arr = (C.c_void_p * len(ranks))(*[m._handle.value for m in ranks])
     for m in ranks:
         if transport == "rccl":
@@ -82,9 +127,13 @@ class TpLinkMixin:
         abi.check(self._lib.mmada_comm_set_mode(self._handle, mode), "mmada_comm_set_mode")
 
     def set_transport(self, name: str) -> None:
-        """Move the forward's exchange to another CONNECTED transport ("pull" <-> "copy" share their mapped buffers)."""
-        self._set_mode(MODE_OF[name])
-        self._link.transport = name
+        """Move the forward's exchange to another CONNECTED transport ("pull" <-> "copy" share their mapped buffers), or to
+        "emulate": the emulated link on top of whichever transport is connected (timing only, the forward's values are void; the
+        rate is set_emulate_mbps).  The link record keeps naming the connected transport under it, so
+        set_transport(model.tp_collective) ends the emulation."""
+        self._set_mode(mode_of(name))
+        if name not in DIAGNOSTIC_OF:
+            self._link.transport = name
 
     def set_exchange_partition(self, exchange_cus: int) -> None:
         """Give the exchange stream `exchange_cus` CUs of its own (0: none) — mmada_comm_set_partition."""
@@ -99,7 +148,7 @@ class TpLinkMixin:
         mode, err, fine = C.c_int(), C.c_int(), C.c_int()
         abi.check(self._lib.mmada_comm_status(self._handle, C.byref(mode), C.byref(err), C.byref(fine), abi.stream_ptr()),
                   "mmada_comm_status")
-        return {"mode": MODE_NAMES[mode.value], "error": err.value, "finegrained_counters": bool(fine.value & 1),
+        return {"mode": mode_name(mode.value), "error": err.value, "finegrained_counters": bool(fine.value & 1),
                 "finegrained_buffers": bool(fine.value & 2)}
 
     def comm_selftest(self, iters: int = 3, L: int = 96, wait: bool = True):
@@ -166,7 +215,7 @@ class TpLinkMixin:
         exported = lib.mmada_comm_create(self._handle, rows, buf) == 0
         if not exported:
             abi.check(lib.mmada_comm_create(self._handle, rows, None), "mmada_comm_create")
-        link = self._link = TpLink(rows=rows)
+        link = self._link = TpLink(rows=rows, chunks=_chunks_at_create())
 
         def all_agree(flag: bool) -> bool:
             got = [None] * self.tp_size
@@ -293,16 +342,32 @@ class TpLinkMixin:
         """Ranks of the RCCL communicator the LIBRARY created (ncclCommCount), 0 when it holds none."""
         return int(self._lib.mmada_comm_rccl_nranks(self._handle)) if self._link.connected or self._link.rccl_also else 0
 
-    def exchange_exposure_probe(self, input_ids: torch.Tensor, reps: int = 3):
+    def emulated_wait_ns_per_forward(self, B: int, L: int, mbps: int) -> int:
+        """The waits the emulated link is asked for over one forward of a (B, L) batch on this model's group at `mbps`, summed
+        (tp.forward_link_waits_ns with the row chunks the library cuts: the link record's `chunks`)."""
+        from . import tp as tp_plan
+
+        return sum(tp_plan.forward_link_waits_ns(B * ((L + 7) // 8 * 8), self.config.d_model, self.tp_size, self.config.n_layers,
+                                                 int(mbps), self._link.chunks))
+
+    def exchange_exposure_probe(self, input_ids: torch.Tensor, reps: int = 3, emulate_mbps: Optional[int] = None):
         """Outside any timed region: wall time of one tensor-parallel forward with its exchanges and of the same forward
         with the library's "no exchange" diagnostic (MODE_NO_EXCHANGE: identical GEMM / attention / owner-side kernels,
         no peer traffic, no hand-off; the values are wrong, only the time is used).  The difference is what the exchanges
-        cost the forward AFTER the two-chunk overlap: the exposed exchange time.  Every rank must call it."""
+        cost the forward AFTER the two-chunk overlap: the exposed exchange time.  Every rank must call it.
+
+        emulate_mbps: instead of the real transport, time the EMULATED link at that rate (MODE_EMULATE: a timed wait of bytes /
+        rate where each transfer would sit, no peer traffic — so one rank alone can call it).  The result then also holds
+        emulated_link_mbps, emulated_wait_ms_per_forward (the sum of the requested waits) and exposed_fraction = exposed ms /
+        that sum: the share of a fixed-rate, contention-free link's time the schedule fails to hide.  The mode and the rate in
+        use before the call are restored."""
         if not self._comm_in_library or self.tp_size == 1:
             return None
         import torch.distributed as dist
 
-        real_mode = MODE_OF[self.tp_collective]
+        emulated = emulate_mbps is not None
+        real_mode = mode_of(self.comm_status()["mode"]) if emulated else MODE_OF[self.tp_collective]
+        mbps_before = emulate_mbps_in_use() if emulated else None
 
         def timed(mode):
             self._set_mode(mode)
@@ -321,6 +386,22 @@ class TpLinkMixin:
                 self._set_mode(real_mode)
             return sorted(ts)[len(ts) // 2]
 
+        if emulated:
+            try:
+                set_emulate_mbps(self._lib, emulate_mbps)
+                with_x = timed(MODE_EMULATE)
+                without = timed(MODE_NO_EXCHANGE)
+                with_x2 = timed(MODE_EMULATE)
+            finally:
+                set_emulate_mbps(self._lib, mbps_before)
+            ms = min(with_x, with_x2)
+            wait_ms = self.emulated_wait_ns_per_forward(int(input_ids.shape[0]), int(input_ids.shape[1]), emulate_mbps) * 1e-6
+            return {"forward_ms_with_exchange": ms, "forward_ms_no_exchange_diagnostic": without,
+                    "exposed_exchange_ms_per_forward": ms - without, "exchanges_per_forward": 2 * self.config.n_layers,
+                    "batch": int(input_ids.shape[0]), "emulated_link_mbps": int(emulate_mbps),
+                    "emulated_wait_ms_per_forward": wait_ms, "exposed_fraction": (ms - without) / wait_ms,
+                    "what": "median wall time of a synchronised forward_body, mmada_comm_set_mode(5) (the emulated link: a "
+                    "timed wait of bytes / rate where each transfer would sit; fixed rate, no contention) vs mmada_comm_set_mode(3)"}
         with_x = timed(real_mode)
         without = timed(MODE_NO_EXCHANGE)
         with_x2 = timed(real_mode)
