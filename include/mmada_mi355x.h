@@ -610,7 +610,12 @@ int mmada_probe_gemm(mmada_gemm_probe* p, void* stream);
  * = reduce-scatter -> residual add + RMSNorm on the rows this rank owns -> all-gather of the normalised rows
  * (csrc/tp_comm.hip): the residual stream stays sharded by rows, the all-gathered tensor is the next GEMM's input.
  * Once a transport is connected, mmada_forward_body runs the whole tensor-parallel forward (exchanges on a second,
- * high-priority stream, two row chunks in flight so an exchange runs under the neighbouring GEMM also at batch 1);
+ * high-priority stream, two row chunks in flight so an exchange runs under the neighbouring GEMM also at batch 1).
+ * MMADA_TP_CHUNKS, read by mmada_comm_create, is kept as 1 (<= 1), 2 (2, 3; the default), 4 (4..7) or 8 (>= 8).  4 and 8, on a
+ * forward that is plain (no dLLM-cache slot), has B >= 2 sequences and does not run over RCCL, select SEQUENCE CHAINS: n =
+ * min(count, B) chains, chain k = the whole sequences [k*B/n, (k+1)*B/n), each an independent chain QKV -> attention of its
+ * sequences -> attn_out -> exchange -> gate/up -> down -> exchange through a block, so a chain's exchange runs under the other
+ * chains' compute; in every other case 4 and 8 give the plan of 2.  Every plan gives the same bits (csrc/tp_plan.h; tp.chunk_plan).
  * mmada_head_rows / mmada_read_stream work as at tp_size == 1.  mmada_set_consumed_rows is ignored (every row is kept).
  *
  *   mmada_comm_create        allocate the published buffers for up to max_rows (= B*Lp) stream rows; export_out receives

@@ -115,10 +115,14 @@ GemmArgs down_args(const mmada_handle* h, int layer, int m0, int rows) {
     return gemm_bt_args(h->hbuf + (size_t)m0 * h->f_l, h->layers[layer].wdown, h->y + (size_t)m0 * d, rows, d, h->f_l, d);
 }
 
-int block_attention(mmada_handle* h, int layer, hipStream_t s, int wbeg, int W) {
+int block_attention(mmada_handle* h, int layer, hipStream_t s, int wbeg, int W, int b0, int b1) {
     const Resident& r = h->res;
     const CacheSlot* cc = r.cc;
-    const double rows = W ? (double)r.B * W : (double)r.B * r.L;
+    if (b1 < 0) b1 = r.B;
+    if (b0 < 0 || b0 >= b1 || b1 > r.B) return mm_fail("forward: attention over sequences [%d,%d) of a batch of %d", b0, b1, r.B);
+    const int nb = b1 - b0;
+    if (nb != r.B && (cc || W)) return mm_fail("forward: a sequence range of the attention needs a plain forward (no cache slot, no row window)");
+    const double rows = W ? (double)nb * W : (double)nb * r.L;
     ProfScope p(h, layer, 1, 4.0 * h->hq_l * rows * (cc ? cc->L : r.L) * 128.0, s);
     if (cc)  // compact (or all) queries of this call against the slot's keys / values of the whole sequence
         return launch_attention(h->q, cc->K(layer), cc->vT(layer), h->att, r.B, h->hq_l, h->hkv_l, cc->L, r.Lp, cc->Lkv, r.Lp,
@@ -126,7 +130,10 @@ int block_attention(mmada_handle* h, int layer, hipStream_t s, int wbeg, int W) 
     if (W)
         return launch_attention(h->q, h->k, h->vT, h->att, r.B, h->hq_l, h->hkv_l, r.L, wbeg + W, r.Lkv, W, h->hq_l * 128, s,
                                 wbeg);
-    return launch_attention(h->q, h->k, h->vT, h->att, r.B, h->hq_l, h->hkv_l, r.L, r.Lp, r.Lkv, r.Lp, h->hq_l * 128, s);
+    // sequences [b0, b1): the same launch on a batch of nb whose first sequence is b0 (q / k / vT are [B, heads, ...], att is [B * Lp, ...])
+    const size_t per_q = (size_t)h->hq_l * r.Lkv * 128, per_kv = (size_t)h->hkv_l * r.Lkv * 128;
+    return launch_attention(h->q + b0 * per_q, h->k + b0 * per_kv, h->vT + b0 * per_kv, h->att + (size_t)b0 * r.Lp * h->hq_l * 128, nb,
+                            h->hq_l, h->hkv_l, r.L, r.Lp, r.Lkv, r.Lp, h->hq_l * 128, s);
 }
 
 // the one-rank output side of a row-parallel GEMM: + the residual stream, on the rows this rank owns (GemmArgs::resid_mod)
@@ -222,7 +229,7 @@ int mmada_forward_body(mmada_handle* h, const int64_t* ids, int B, int L, void* 
         if (!h->tp)
             return mm_fail("mmada_forward_body: tp_size=%d needs a connected collective (mmada_comm_create + "
                            "mmada_comm_connect_*) or the host-issued all-reduce of the segment API", h->cfg.tp_size);
-        if (B > 0 && L > 0 && tp_forward_refused(h, B * ((L + 7) / 8 * 8))) return 1;  // before anything is enqueued
+        if (B > 0 && L > 0 && tp_forward_refused(h, B, (L + 7) / 8 * 8, false)) return 1;  // before anything is enqueued
         if (mmada_embed(h, ids, B, L, stream)) return 1;
         return tp_forward_body(h, (hipStream_t)stream);
     }

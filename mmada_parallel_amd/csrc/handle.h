@@ -112,8 +112,10 @@ GemmArgs gate_up_args(const mmada_handle* h, int layer, int m0, int rows);
 GemmArgs attn_out_args(const mmada_handle* h, int layer, int m0, int rows);
 GemmArgs down_args(const mmada_handle* h, int layer, int m0, int rows);
 // the block's attention over this rank's heads, timed as kernel class 1: a cache step's queries against the slot, the row window
-// [wbeg, wbeg + W) of each sequence (W > 0: the one-rank forward's last block), or every row
-int block_attention(mmada_handle* h, int layer, hipStream_t s, int wbeg = 0, int W = 0);
+// [wbeg, wbeg + W) of each sequence (W > 0: the one-rank forward's last block), or every row.  [b0, b1) (b1 < 0: the whole batch):
+// only these sequences, for the tensor-parallel forward's sequence chains — pointer offsets into q / k / vT / att and a launch
+// over b1 - b0 sequences; a plain forward only (no cache slot, no window)
+int block_attention(mmada_handle* h, int layer, hipStream_t s, int wbeg = 0, int W = 0, int b0 = 0, int b1 = -1);
 // every block of a one-rank forward, after the embedding
 int run_blocks(mmada_handle* h, void* stream);
 // heads.hip: the (R, limit, col_begin, col_end) checks of a head entry point named `who` (R <= 0 is the caller's early return)
@@ -124,8 +126,9 @@ int tp_forward_body(mmada_handle* h, hipStream_t s);              // all blocks 
 int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s);  // residual stream rows of every owner -> [M, d]
 void tp_comm_free(mmada_handle* h);
 bool tp_comm_connected(const mmada_handle* h);   // a transport (or the no-exchange diagnostic / the emulated link) is active on this handle
-// nonzero (mm_fail) when a tensor-parallel forward over M stream rows must not start: the emulated link would wait beyond its cap
-int tp_forward_refused(const mmada_handle* h, int M);
+// nonzero (mm_fail) when a tensor-parallel forward over B sequences of Lp stream rows each (cached: through a dLLM-cache slot) must
+// not start: the emulated link would wait beyond its cap
+int tp_forward_refused(const mmada_handle* h, int B, int Lp, bool cached);
 // this handle's forward is the tensor-parallel one (a connected one-rank group: the tp_allow_single_rank test switch)
 inline bool runs_tensor_parallel(const mmada_handle* h) { return h->cfg.tp_size != 1 || tp_comm_connected(h); }
 // tp_heads.hip

@@ -5,6 +5,7 @@
 #include <rccl/rccl.h>
 
 #include "handle.h"
+#include "tp_plan.h"
 
 constexpr int TP_MAX = 8;
 constexpr int STAT_ROWS = 16384;   // text rows (B*T) a vocabulary-parallel select can take
@@ -88,8 +89,9 @@ struct TpComm {
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     bf16_t* stage = nullptr;   // copy transport: [size][ceil(max_rows / size) + 16, d] peer slices of this rank's rows
     size_t stage_stride = 0;   // elements per peer
-    hipEvent_t ev_g[2] = {}, ev_c[2] = {};
-    int chunks = 2;
+    hipEvent_t ev_g[TP_CHUNKS_MAX] = {}, ev_c[TP_CHUNKS_MAX] = {};  // per chunk: its row-parallel GEMM is done / its exchange is done
+    int chunks = 2;            // 1, 2, 4 or 8: normalise_chunks(MMADA_TP_CHUNKS) at mmada_comm_create
+    bool fwd_chains = false;   // the last forward ran a sequence-chain plan (tp_gather_stream must find the same owners)
     long long timeout = 0;     // hand-off timeout in wall_clock64 ticks (100 MHz)
     // RCCL
     RcclApi nccl;
@@ -140,27 +142,9 @@ inline int nccl_fail(TpComm* c, const char* what, ncclResult_t r) {
     return mm_fail("%s: %s", what, c->nccl.GetErrorString ? c->nccl.GetErrorString(r) : "RCCL error");
 }
 
-struct Slice { int m0, m1, slice, r0, r1; };
-
-// chunk k of `nch` over M rows; every chunk but the last is a multiple of 8*tp rows, so only the last one is padded
-inline Slice chunk_slice(int M, int tp, int rank, int nch, int k) {
-    Slice s;
-    const int unit = 8 * tp;
-    const int first = nch == 2 ? (M / 2 + unit - 1) / unit * unit : M;
-    s.m0 = k == 0 ? 0 : min(first, M);
-    s.m1 = (k == nch - 1) ? M : min(first, M);
-    const int rows = s.m1 - s.m0;
-    s.slice = max(8, ((rows + tp - 1) / tp + 7) / 8 * 8);
-    s.r0 = min(s.m1, s.m0 + rank * s.slice);
-    s.r1 = min(s.m1, s.r0 + s.slice);
-    return s;
+static_assert(TP_RCCL == PLAN_MODE_RCCL, "tp_plan.h names the RCCL mode by its value");
+// the plan of a forward over M stream rows, B sequences of Lp rows each, on comm c in its current mode
+inline ChunkPlan chunk_plan(const TpComm* c, int M, int B, int Lp, bool cached) {
+    return chunk_plan_of(M, B, Lp, c->size, c->rank, c->chunks, c->mode, cached);
 }
-
-// The row chunks of a forward over M rows: two (the exchange of one runs under the GEMM of the other) once M is large enough
-struct ChunkPlan { int n; Slice sl[2]; };
-inline ChunkPlan chunk_plan(const TpComm* c, int M) {
-    ChunkPlan p;
-    p.n = (c->chunks >= 2 && M >= 4 * 8 * c->size) ? 2 : 1;
-    for (int k = 0; k < p.n; ++k) p.sl[k] = chunk_slice(M, c->size, c->rank, p.n, k);
-    return p;
-}
+inline ChunkPlan chunk_plan(const TpComm* c, const Resident& r) { return chunk_plan(c, r.M, r.B, r.Lp, r.cc != nullptr); }

@@ -40,7 +40,10 @@
 // the exchange kernels own their CUs by construction, the GEMMs lose n / 256 of the chip, deterministically.
 // Overlap: the M rows are cut into two chunks; the exchange of chunk i runs on a second (high-priority) stream under the
 // row-parallel GEMM of chunk i+1 / the next column-parallel GEMM of chunk i-1 — also at batch 1, the only join point is
-// the attention (needs every key).
+// the attention (needs every key).  MMADA_TP_CHUNKS = 4 or 8 (opt-in) on a batch of two or more sequences replaces the row chunks by
+// SEQUENCE CHAINS (tp_plan.h: chunk_plan_of): up to 8 groups of whole sequences, each an independent chain through the block —
+// a sequence's attention needs that sequence's keys only — so a chain's exchange hides under every other chain's compute
+// (tp_forward_body_on).
 // The LM heads on top of these transports (text select, scoring) are tp_heads.hip; the state both units share is tp_comm.h.
 #include <dlfcn.h>
 
@@ -450,12 +453,12 @@ int comm_init(mmada_handle* h, int max_rows, void* export_out) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // the exchange must not queue behind a whole round of GEMM workgroups
     MM_CHECK_HIP(hipStreamCreateWithPriority(&c->sc, hipStreamNonBlocking, hi));
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < TP_CHUNKS_MAX; ++k) {
         MM_CHECK_HIP(hipEventCreateWithFlags(&c->ev_g[k], hipEventDisableTiming));
         MM_CHECK_HIP(hipEventCreateWithFlags(&c->ev_c[k], hipEventDisableTiming));
     }
     const char* e = getenv("MMADA_TP_CHUNKS");
-    c->chunks = e ? atoi(e) : 2;
+    c->chunks = normalise_chunks(e ? atoi(e) : 2);
     c->timeout = default_timeout_ticks();
     MM_CHECK_HIP(hipDeviceSynchronize());
     if (export_out) {
@@ -486,7 +489,7 @@ static int tp_forward_body_on(mmada_handle* h, hipStream_t s);
 int tp_forward_body(mmada_handle* h, hipStream_t s_user) {
     TpComm* c = h->tp;
     if (!c || c->mode == TP_NONE) return mm_fail("tensor-parallel forward: no transport connected (mmada_comm_create + connect)");
-    if (tp_forward_refused(h, h->res.M)) return 1;
+    if (tp_forward_refused(h, h->res.B, h->res.Lp, h->res.cc != nullptr)) return 1;
     if (!c->s_cmp) return tp_forward_body_on(h, s_user);
     // CU partition: the blocks run on the library's masked compute stream, forked from and joined to the caller's stream
     MM_CHECK_HIP(hipEventRecord(c->ev_in, s_user));
@@ -502,46 +505,85 @@ static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
     if (h->res.M > c->max_rows) return mm_fail("tensor-parallel forward: %d rows exceed the comm buffers (%d)", h->res.M, c->max_rows);
     const int d = h->cfg.d_model, M = h->res.M, nl = h->cfg.n_layers;
     if ((d >> 3) > 64 * MAXCH) return mm_fail("tensor-parallel forward: d_model > %d is not supported", 64 * MAXCH * 8);
-    const ChunkPlan plan = chunk_plan(c, M);
+    const ChunkPlan plan = chunk_plan(c, h->res);
+    c->fwd_chains = plan.chains;
     const int emulate_mbps = switches().tp_emulate_mbps;  // one snapshot for every exchange of this forward
     const double rows_real = (double)h->res.B * h->res.L / M;  // fraction of stream rows that are not padding (FLOP accounting)
     // first RMSNorm of the forward: the embeddings are replicated, no exchange needed
     if (h->res.xn_is_layer0) h->res.xn_is_layer0 = false;  // fused into the embedding kernel
     else if (launch_rmsnorm(h->x, h->layers[0].attn_norm, h->xn, M, d, h->cfg.rms_eps, s)) return 1;
-    bool pending[2] = {false, false};  // chunk k's xn rows are being produced on the exchange stream
+    bool pending[TP_CHUNKS_MAX] = {};  // chunk k's xn rows are being produced on the exchange stream
     using ArgsOf = GemmArgs (*)(const mmada_handle*, int, int, int);  // handle.h: qkv_args, gate_up_args, attn_out_args, down_args
-    // a column-parallel GEMM (ProfScope kind `kind`) chunk by chunk: wait for the chunk's xn rows, multiply
+    // chunk k of a column-parallel GEMM (ProfScope kind `kind`): wait for the chunk's xn rows, multiply
+    auto column_chunk = [&](int layer, int kind, int epi, ArgsOf args_of, int k) -> int {
+        if (pending[k]) {
+            MM_CHECK_HIP(hipStreamWaitEvent(s, c->ev_c[k], 0));
+            pending[k] = false;
+        }
+        const GemmArgs g = args_of(h, layer, plan.sl[k].m0, plan.sl[k].m1 - plan.sl[k].m0);
+        ProfScope p(h, layer, kind, 2.0 * g.M * rows_real * g.N * g.K, s);
+        return launch_gemm(epi, g, s);
+    };
+    // chunk k of a row-parallel GEMM into c->part, then the chunk's exchange (RMSNorm weight w) on the exchange stream: it runs
+    // under whatever the compute stream is given next
+    auto row_chunk = [&](int layer, int kind, ArgsOf args_of, const bf16_t* w, int k) -> int {
+        GemmArgs o = args_of(h, layer, plan.sl[k].m0, plan.sl[k].m1 - plan.sl[k].m0);
+        o.C = c->part + (size_t)plan.sl[k].m0 * d; o.publish = peers_mapped(c);
+        {
+            ProfScope p(h, layer, kind, 2.0 * o.M * rows_real * o.N * o.K, s);
+            if (launch_gemm(EPI_STORE, o, s)) return 1;
+        }
+        MM_CHECK_HIP(hipEventRecord(c->ev_g[k], s));
+        MM_CHECK_HIP(hipStreamWaitEvent(c->sc, c->ev_g[k], 0));
+        if (exchange(h, plan.sl[k], w, emulate_mbps, c->sc)) return 1;
+        MM_CHECK_HIP(hipEventRecord(c->ev_c[k], c->sc));
+        pending[k] = true;
+        return 0;
+    };
     auto column_parallel = [&](int layer, int kind, int epi, ArgsOf args_of) -> int {
-        for (int k = 0; k < plan.n; ++k) {
-            if (pending[k]) {
-                MM_CHECK_HIP(hipStreamWaitEvent(s, c->ev_c[k], 0));
-                pending[k] = false;
-            }
-            const GemmArgs g = args_of(h, layer, plan.sl[k].m0, plan.sl[k].m1 - plan.sl[k].m0);
-            ProfScope p(h, layer, kind, 2.0 * g.M * rows_real * g.N * g.K, s);
-            if (launch_gemm(epi, g, s)) return 1;
-        }
+        for (int k = 0; k < plan.n; ++k)
+            if (column_chunk(layer, kind, epi, args_of, k)) return 1;
         return 0;
     };
-    // a row-parallel GEMM into c->part chunk by chunk; chunk k's exchange (RMSNorm weight w) runs on the exchange stream under
-    // chunk k+1's GEMM
     auto row_parallel = [&](int layer, int kind, ArgsOf args_of, const bf16_t* w) -> int {
-        for (int k = 0; k < plan.n; ++k) {
-            GemmArgs o = args_of(h, layer, plan.sl[k].m0, plan.sl[k].m1 - plan.sl[k].m0);
-            o.C = c->part + (size_t)plan.sl[k].m0 * d; o.publish = peers_mapped(c);
-            {
-                ProfScope p(h, layer, kind, 2.0 * o.M * rows_real * o.N * o.K, s);
-                if (launch_gemm(EPI_STORE, o, s)) return 1;
-            }
-            MM_CHECK_HIP(hipEventRecord(c->ev_g[k], s));
-            MM_CHECK_HIP(hipStreamWaitEvent(c->sc, c->ev_g[k], 0));
-            if (exchange(h, plan.sl[k], w, emulate_mbps, c->sc)) return 1;
-            MM_CHECK_HIP(hipEventRecord(c->ev_c[k], c->sc));
-            pending[k] = true;
-        }
+        for (int k = 0; k < plan.n; ++k)
+            if (row_chunk(layer, kind, args_of, w, k)) return 1;
         return 0;
     };
+    // Write-after-read on the published buffers, for any number n of chunks or chains.  Three facts: (1) a rank's ev_c[k] completes
+    // only behind the SECOND hand-off of that exchange on its exchange stream; (2) a peer signals a hand-off behind everything
+    // earlier on ITS exchange stream — its reads included: the owner kernel (or the staging copies) reads part[] before the second
+    // hand-off's signal, the gather (kernel or copies) reads hn_pub[] before the first signal of the peer's next exchange;
+    // (3) every rank takes the same plan from the same inputs and issues its exchanges in one total order: per block c_0 .. c_n-1
+    // after attn_out, then c_0 .. c_n-1 after down — the hand-off counters are a plain sequence number, so the i-th hand-off of one
+    // rank only ever meets the i-th of another.
+    //   part[c_k] is rewritten by the NEXT row-parallel GEMM of chunk k (down after attn_out, the next block's attn_out after
+    //   down).  That GEMM follows, on the compute stream, the column-parallel GEMM of chunk k, which waited for ev_c[k]: by (1) this
+    //   rank's second hand-off of the exchange has passed, i.e. every peer has signalled its second hand-off, by (2) behind its
+    //   owner kernel's reads of part[c_k].  No peer reads part[c_k] again before its next first hand-off, which needs this rank's
+    //   signal behind the rewriting GEMM (ev_g[k]).
+    //   hn_pub[c_k] is rewritten by the owner kernel of chunk k's NEXT exchange on this rank's exchange stream, behind that
+    //   exchange's first hand-off: every peer has signalled it, by (2) behind everything of its previous exchanges — the gather of
+    //   chunk k's previous exchange among them, however many other chunks' exchanges lie between the two by (3).
+    // Nothing in this depends on n or on where the chunk boundaries lie; the chains only change what the compute stream runs
+    // between a chunk's two GEMMs.  The buffers of a rank's own device (xn, x, att, hbuf, q / k / vT) are ordered by ev_g / ev_c and
+    // stream order; chain k's attention reads the keys and values of chain k's sequences only, written by its own QKV launch.
     for (int layer = 0; layer < nl; ++layer) {
+        const bf16_t* next_norm = layer + 1 < nl ? h->layers[layer + 1].attn_norm : h->ln_f;
+        if (plan.chains) {
+            // sequence chains: chain k runs QKV -> attention of its sequences -> attn_out without a join; its exchange hides under
+            // the chains that follow, and its gate/up waits for it only after every other chain's attention half was issued
+            for (int k = 0; k < plan.n; ++k) {
+                if (column_chunk(layer, 0, EPI_QKV, qkv_args, k)) return 1;
+                if (block_attention(h, layer, s, 0, 0, plan.b0[k], plan.b1[k])) return 1;
+                if (row_chunk(layer, 2, attn_out_args, h->layers[layer].ff_norm, k)) return 1;
+            }
+            for (int k = 0; k < plan.n; ++k) {
+                if (column_chunk(layer, 3, EPI_SWIGLU, gate_up_args, k)) return 1;
+                if (row_chunk(layer, 4, down_args, next_norm, k)) return 1;
+            }
+            continue;
+        }
         // q/k/v (column-parallel: this rank's heads), RoPE in the epilogue; a dLLM cache step writes this rank's heads of the
         // block's keys / values into the slot
         if (column_parallel(layer, 0, EPI_QKV, qkv_args)) return 1;
@@ -550,7 +592,7 @@ static int tp_forward_body_on(mmada_handle* h, hipStream_t s) {
         if (row_parallel(layer, 2, attn_out_args, h->layers[layer].ff_norm)) return 1;
         // gate/up (column-parallel) + SiLU*mul, then down (row-parallel)
         if (column_parallel(layer, 3, EPI_SWIGLU, gate_up_args)) return 1;
-        if (row_parallel(layer, 4, down_args, layer + 1 < nl ? h->layers[layer + 1].attn_norm : h->ln_f)) return 1;
+        if (row_parallel(layer, 4, down_args, next_norm)) return 1;
     }
     for (int k = 0; k < plan.n; ++k)
         if (pending[k]) MM_CHECK_HIP(hipStreamWaitEvent(s, c->ev_c[k], 0));
@@ -563,7 +605,9 @@ int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s) {
     TpComm* c = h->tp;
     if (!transport_connected(c)) return mm_fail("tp_gather_stream: no transport connected (or the no-exchange diagnostic is on)");
     const int d = h->cfg.d_model;
-    const ChunkPlan plan = chunk_plan(c, h->res.M);
+    const ChunkPlan plan = chunk_plan(c, h->res);  // the owners of the forward that is resident
+    if (plan.chains != c->fwd_chains)  // the plan depends on the transport: RCCL never runs sequence chains
+        return mm_fail("tp_gather_stream: the transport was switched to or from RCCL since the resident forward ran; its rows have other owners");
     for (int k = 0; k < plan.n; ++k) {
         const Slice& sl = plan.sl[k];
         const int own = sl.r1 - sl.r0;
@@ -588,10 +632,10 @@ int tp_gather_stream(mmada_handle* h, bf16_t* full_out, hipStream_t s) {
 
 bool tp_comm_connected(const mmada_handle* h) { return h->tp && h->tp->mode != TP_NONE; }
 
-int tp_forward_refused(const mmada_handle* h, int M) {
+int tp_forward_refused(const mmada_handle* h, int B, int Lp, bool cached) {
     const TpComm* c = h->tp;
     if (!c || c->mode != TP_EMULATE) return 0;
-    return emulated_waits_ok(c, chunk_plan(c, M), switches().tp_emulate_mbps);
+    return emulated_waits_ok(c, chunk_plan(c, B * Lp, B, Lp, cached), switches().tp_emulate_mbps);
 }
 
 void tp_comm_free(mmada_handle* h) {
@@ -601,7 +645,7 @@ void tp_comm_free(mmada_handle* h) {
         for (int b = 0; b < PUB_COUNT; ++b)
             if (c->opened[j][b]) (void)hipIpcCloseMemHandle(c->opened[j][b]);
     if (c->comm && c->nccl.CommDestroy) (void)c->nccl.CommDestroy(c->comm);
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < TP_CHUNKS_MAX; ++k) {
         if (c->ev_g[k]) (void)hipEventDestroy(c->ev_g[k]);
         if (c->ev_c[k]) (void)hipEventDestroy(c->ev_c[k]);
     }
@@ -810,7 +854,7 @@ int mmada_comm_exchange(mmada_handle* h, const void* norm_w, void* stream) {
     const Slice sl = chunk_slice(h->res.M, h->tp->size, h->tp->rank, 1, 0);
     const int emulate_mbps = switches().tp_emulate_mbps;
     if (h->tp->mode == TP_EMULATE) {  // refuse a wait beyond the cap before anything is launched
-        ChunkPlan one;
+        ChunkPlan one{};
         one.n = 1; one.sl[0] = sl;
         if (emulated_waits_ok(h->tp, one, emulate_mbps)) return 1;
     }

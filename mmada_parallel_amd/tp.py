@@ -58,27 +58,63 @@ def shard_layer_weights(weights: dict, cfg: dict, rank: int, size: int) -> dict:
 
 
 # ---- the library's exchange step (csrc/tp_comm.hip) as plain index arithmetic --------------------------------------------
-def chunk_slices(M: int, size: int, n_chunks: int = 2):
+TP_CHUNKS_MAX = 8
+MODE_RCCL = 2   # mmada_comm_status: the one transport that never runs sequence chains
+
+
+def normalise_chunks(value: int) -> int:
+    """What mmada_comm_create keeps of MMADA_TP_CHUNKS: 1 (<= 1), 2 (2, 3), 4 (4..7) or 8 (>= 8) — normalise_chunks in csrc/tp_plan.h."""
+    return 1 if value <= 1 else 2 if value < 4 else 4 if value < 8 else 8
+
+
+def _owner_split(m0: int, m1: int, size: int):
+    return max(8, ((m1 - m0 + size - 1) // size + 7) // 8 * 8)
+
+
+def runs_chains(n_chunks: int, batch, rccl: bool = False, cached: bool = False) -> bool:
+    """True when a forward of batch = (B, Lp) runs SEQUENCE CHAINS: a count of 4 or 8, a plain forward (no dLLM-cache slot) of two
+    or more sequences, any transport but RCCL (chunk_plan_of in csrc/tp_plan.h)."""
+    return normalise_chunks(n_chunks) >= 4 and batch is not None and batch[0] >= 2 and not rccl and not cached
+
+
+def chunk_slices(M: int, size: int, n_chunks: int = 2, *, batch=None, rccl: bool = False, cached: bool = False):
     """Row plan of one exchange over M stream rows: [(m0, m1, slice)] per chunk; inside a chunk rank r owns rows
-    [m0 + r*slice, min(m1, m0 + (r+1)*slice)).  Every chunk but the last is a multiple of 8*size rows, so only the last one
-    is padded (chunk_slice in csrc/tp_comm.hip)."""
-    unit = 8 * size
-    if n_chunks == 2 and M >= 4 * unit:
-        first = (M // 2 + unit - 1) // unit * unit
-        bounds = [(0, min(first, M)), (min(first, M), M)]
+    [min(m1, m0 + r*slice), min(m1, m0 + (r+1)*slice)).  Row chunks (n_chunks 1 or 2, and every case that does not run chains):
+    every chunk but the last is a multiple of 8*size rows, so only the last one is padded (chunk_slice in csrc/tp_plan.h).
+    batch = (B, Lp) with M == B * Lp and a count of 4 or 8 (runs_chains): min(count, B) chains of whole sequences,
+    chain k = sequences [k*B // n, (k+1)*B // n), owners clipped to the chain."""
+    if runs_chains(n_chunks, batch, rccl, cached):
+        B, Lp = batch
+        if M != B * Lp:
+            raise ValueError(f"chunk_slices: M={M} is not B*Lp={B}*{Lp}")
+        n = min(normalise_chunks(n_chunks), B)
+        bounds = [(k * B // n * Lp, (k + 1) * B // n * Lp) for k in range(n)]
     else:
-        bounds = [(0, M)]
+        unit = 8 * size
+        if n_chunks >= 2 and M >= 4 * unit:
+            first = (M // 2 + unit - 1) // unit * unit
+            bounds = [(0, min(first, M)), (min(first, M), M)]
+        else:
+            bounds = [(0, M)]
+    return [(m0, m1, _owner_split(m0, m1, size)) for m0, m1 in bounds]
+
+
+def owned_rows(M: int, rank: int, size: int, n_chunks: int = 2, *, batch=None, rccl: bool = False, cached: bool = False):
+    """Row ranges of the residual stream rank `rank` keeps (and normalises) — one per chunk (a trailing rank's may be empty)."""
+    return [(min(m1, m0 + rank * sl), min(m1, m0 + (rank + 1) * sl))
+            for m0, m1, sl in chunk_slices(M, size, n_chunks, batch=batch, rccl=rccl, cached=cached)]
+
+
+def chunk_plan(B: int, Lp: int, tp: int, rank: int, chunks: int, transport_mode: int = 1, cached: bool = False):
+    """chunk_plan_of (csrc/tp_plan.h) as Python, held to it by tests/test_tp_chains_host.py: [(m0, m1, slice, r0, r1, b0, b1)] per chunk of a forward over B sequences of Lp stream rows
+    on rank `rank` of `tp`; [b0, b1) are the sequences whose attention runs with the chunk (a chain's own, else the whole batch)."""
+    M, rccl = B * Lp, transport_mode == MODE_RCCL
+    chains = runs_chains(chunks, (B, Lp), rccl, cached)
     out = []
-    for m0, m1 in bounds:
-        rows = m1 - m0
-        sl = max(8, ((rows + size - 1) // size + 7) // 8 * 8)
-        out.append((m0, m1, sl))
+    for m0, m1, sl in chunk_slices(M, tp, normalise_chunks(chunks), batch=(B, Lp), rccl=rccl, cached=cached):
+        r0 = min(m1, m0 + rank * sl)
+        out.append((m0, m1, sl, r0, min(m1, r0 + sl)) + ((m0 // Lp, m1 // Lp) if chains else (0, B)))
     return out
-
-
-def owned_rows(M: int, rank: int, size: int, n_chunks: int = 2):
-    """Row ranges of the residual stream rank `rank` keeps (and normalises) — one per chunk."""
-    return [(min(m1, m0 + rank * sl), min(m1, m0 + (rank + 1) * sl)) for m0, m1, sl in chunk_slices(M, size, n_chunks)]
 
 
 # ---- the emulated link (mmada_comm_set_mode 5, csrc/tp_comm.h link_wait_ns) ----------------------------------------------
@@ -95,10 +131,13 @@ def link_wait_ns(rows: int, d: int, tp: int, mbps: int) -> int:
     return (nbytes * 1000 + mbps - 1) // mbps
 
 
-def forward_link_waits_ns(M: int, d: int, tp: int, n_layers: int, mbps: int, n_chunks: int = 2):
+def forward_link_waits_ns(M: int, d: int, tp: int, n_layers: int, mbps: int, n_chunks: int = 2, *, batch=None, rccl: bool = False,
+                          cached: bool = False):
     """Every wait a forward over M stream rows asks of the emulated link, in launch order: per block two exchanges (after attn_out
-    and after ff_out), per exchange and row chunk (chunk_slices) two phases.  sum() of it is the requested wait per forward."""
-    per_exchange = [link_wait_ns(m1 - m0, d, tp, mbps) for m0, m1, _ in chunk_slices(M, tp, n_chunks) for _phase in (0, 1)]
+    and after ff_out), per exchange and row chunk (chunk_slices; batch = (B, Lp) for the sequence chains of a count of 4 or 8) two
+    phases.  sum() of it is the requested wait per forward."""
+    per_exchange = [link_wait_ns(m1 - m0, d, tp, mbps)
+                    for m0, m1, _ in chunk_slices(M, tp, n_chunks, batch=batch, rccl=rccl, cached=cached) for _phase in (0, 1)]
     return per_exchange * (2 * n_layers)
 
 

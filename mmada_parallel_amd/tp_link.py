@@ -66,13 +66,16 @@ class TpLink:
     rows: int = 0                    # stream rows the comm was created for
     transport: Optional[str] = None  # model.tp_collective: "pull" / "copy" / "rccl" / HOST_ALL_REDUCE, None before any connect
     rccl_also: bool = False          # a second, RCCL communicator exists beside a mapped transport (MMADA_TP_PROBE_RCCL)
-    chunks: int = 2                  # row chunks per exchange the comm was created with (MMADA_TP_CHUNKS at mmada_comm_create)
+    chunks: int = 2                  # chunk count the comm was created with: 1, 2, 4 or 8 (MMADA_TP_CHUNKS at mmada_comm_create;
+                                     # 4 and 8 run sequence chains where tp.runs_chains says so, else the plan of 2)
 
 
 def _chunks_at_create() -> int:
-    """What mmada_comm_create makes of MMADA_TP_CHUNKS right now: two row chunks unless it says fewer."""
+    """What mmada_comm_create makes of MMADA_TP_CHUNKS right now: 1, 2 (the default), 4 or 8 (tp.normalise_chunks)."""
+    from .tp import normalise_chunks
+
     try:
-        return 2 if int(os.environ.get("MMADA_TP_CHUNKS", "2")) >= 2 else 1
+        return normalise_chunks(int(os.environ.get("MMADA_TP_CHUNKS", "2")))
     except ValueError:
         return 1   # atoi() of a non-number is 0
 
@@ -344,17 +347,19 @@ class TpLinkMixin:
 
     def emulated_wait_ns_per_forward(self, B: int, L: int, mbps: int) -> int:
         """The waits the emulated link is asked for over one forward of a (B, L) batch on this model's group at `mbps`, summed
-        (tp.forward_link_waits_ns with the row chunks the library cuts: the link record's `chunks`)."""
+        (tp.forward_link_waits_ns with the chunks the library cuts for this batch shape: the link record's `chunks`; the emulated
+        link is never the RCCL transport, so a count of 4 or 8 means sequence chains once B >= 2)."""
         from . import tp as tp_plan
 
-        return sum(tp_plan.forward_link_waits_ns(B * ((L + 7) // 8 * 8), self.config.d_model, self.tp_size, self.config.n_layers,
-                                                 int(mbps), self._link.chunks))
+        Lp = (L + 7) // 8 * 8
+        return sum(tp_plan.forward_link_waits_ns(B * Lp, self.config.d_model, self.tp_size, self.config.n_layers, int(mbps),
+                                                 self._link.chunks, batch=(B, Lp)))
 
     def exchange_exposure_probe(self, input_ids: torch.Tensor, reps: int = 3, emulate_mbps: Optional[int] = None):
         """Outside any timed region: wall time of one tensor-parallel forward with its exchanges and of the same forward
         with the library's "no exchange" diagnostic (MODE_NO_EXCHANGE: identical GEMM / attention / owner-side kernels,
         no peer traffic, no hand-off; the values are wrong, only the time is used).  The difference is what the exchanges
-        cost the forward AFTER the two-chunk overlap: the exposed exchange time.  Every rank must call it.
+        cost the forward AFTER the overlap of its chunk plan: the exposed exchange time.  Every rank must call it.
 
         emulate_mbps: instead of the real transport, time the EMULATED link at that rate (MODE_EMULATE: a timed wait of bytes /
         rate where each transfer would sit, no peer traffic — so one rank alone can call it).  The result then also holds

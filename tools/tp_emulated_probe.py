@@ -7,7 +7,10 @@ the set-up of tools/tp_compute_probe.py — timed per block in
     mode 5  the emulated link: the same, plus a one-wave timed wait of bytes / rate where each half of every exchange would move
             its bytes (same stream, same dependencies; csrc/tp_comm.hip).
 mode 5 - mode 3 is the exchange time the schedule leaves exposed; over the requested wait it is f, the one unmeasured quantity of
-the scaling table.  Rates 76 000 and 153 000 MB/s per link and direction, MMADA_TP_CHUNKS 1 and 2.
+the scaling table.  Rates 76 000 and 153 000 MB/s per link and direction, MMADA_TP_CHUNKS 1, 2, 4 and 8 (--chunks): 1 and 2 cut the rows
+into chunks around a whole-batch attention, 4 and 8 run the batch's sequences as independent chains (csrc/tp_plan.h chunk_plan_of).
+After every rank count a summary compares each count with chunks = 2 OF THE SAME RUN: t3 (the compute-side price of smaller GEMMs
+and per-chain attention launches) and t5 (what a forward costs with the link in it).
 
 The emulated link has a FIXED rate and NO contention: no remote-load latency, no hand-off between ranks, no CU taken by a pull
 kernel, no link shared between transfers.  f is a property of the schedule on this GPU; it says nothing about what xGMI delivers.
@@ -16,7 +19,7 @@ The peers rank 0 is connected to are stand-ins (one tiny block each, tp_rank j o
 rank, and modes 3 and 5 touch no peer memory.  No other mode is ever run on this group.
 Timing: device events around ONE forward_body on a side stream, the modes alternating, `reps` repetitions, medians; each timed
 forward is enqueued behind a few large GEMMs so that the host's launch rate is not in the figure.
-    python tools/tp_emulated_probe.py [--layers 4] [--reps 7] [--tp 2,4,8] > profiles/tp_emulated.txt"""
+    python tools/tp_emulated_probe.py [--layers 4] [--reps 7] [--tp 2,4,8] [--chunks 1,2,4,8] >> profiles/tp_emulated.txt"""
 import argparse
 import os
 import statistics
@@ -77,11 +80,17 @@ def timed(model, ids, stream, mode_rates, reps, blocker):
     return out
 
 
+def wait_of(waits, layers):
+    """ms of requested wait per block"""
+    return sum(waits) * 1e-6 / layers
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--tp", default="2,4,8")
+    ap.add_argument("--chunks", default="1,2,4,8", help="MMADA_TP_CHUNKS values to create the comms under")
     args = ap.parse_args()
     dev = "cuda:0"
     layers = args.layers
@@ -99,10 +108,12 @@ def main():
         for tp in (int(t) for t in args.tp.split(",")):
             sd = synth.synthetic_state_dict(cfg, seed=0, device=dev)
             ids = job["input_ids"].repeat(tp, 1).to(dev)
-            M = tp * ((L + 7) // 8 * 8)
+            Lp = (L + 7) // 8 * 8
+            M = tp * Lp
+            summary = {}
             group = rank0_and_stand_ins(cfg, sd, tp, dev)
             del sd
-            for chunks in (1, 2):
+            for chunks in (int(c) for c in args.chunks.split(",")):
                 model = connect(group, M, chunks)
                 variants = [(MODE_NO_EXCHANGE, RATES[0])] + [(MODE_EMULATE, r) for r in RATES]
                 ts = timed(model, ids, stream, variants, args.reps, blocker)
@@ -112,13 +123,19 @@ def main():
                 for r in RATES:
                     t5 = ts[(MODE_EMULATE, r)]
                     m5 = statistics.median(t5) / layers
-                    waits = tp_plan.forward_link_waits_ns(M, d, tp, layers, r, chunks)
-                    wait = sum(waits) * 1e-6 / layers
+                    waits = tp_plan.forward_link_waits_ns(M, d, tp, layers, r, chunks, batch=(tp, Lp))
+                    summary[(chunks, r)] = (m3, m5, (m5 - m3) / wait_of(waits, layers))
+                    wait = wait_of(waits, layers)
                     print(f"TP={tp} B={tp} chunks={chunks} {r} MB/s: t3 {m3:.3f} ms/block (min {min(t3) / layers:.3f} max {max(t3) / layers:.3f})  "
                           f"t5 {m5:.3f} (min {min(t5) / layers:.3f} max {max(t5) / layers:.3f})  wait {wait:.3f} ({len(waits) // layers} x "
                           f"{max(waits) * 1e-3:.1f} us)  exposed {m5 - m3:.3f}  f = {(m5 - m3) / wait:.3f}", flush=True)
                 for m in group:
                     m.disconnect_tp()
+            for (chunks, r), (m3, m5, f) in summary.items():   # against chunks = 2 of this run
+                if chunks != 2 and (2, r) in summary:
+                    b3, b5, bf = summary[(2, r)]
+                    print(f"TP={tp} B={tp} {r} MB/s chunks={chunks} against chunks=2: t3 {m3:.3f} / {b3:.3f} = {m3 / b3:.3f}  "
+                          f"t5 {m5:.3f} / {b5:.3f} = {m5 / b5:.3f}  f {f:.3f} against {bf:.3f}", flush=True)
             del model, group
             torch.cuda.empty_cache()
     finally:
