@@ -265,12 +265,55 @@ int mmada_mfma_probe(const void* data, void* sink, int iters, int launches, void
     return launch_mfma_probe((const bf16_t*)data, (float*)sink, iters, launches, (hipStream_t)stream, tflops_out, ms_out);
 }
 
+// The records of sampler.hip's launchers (kernels.h: what each field means) from what every entry point of a kernel passes; the
+// entry points set the fields of their variant by name.
+static TextStatsArgs text_stats_args(TextMode mode, const mmada_handle* h, const void* logits, int B, int T, int V, int ld, int64_t* ids,
+                                     int L, int text_start) {
+    TextStatsArgs a{};
+    a.mode = mode;
+    a.logits = (const bf16_t*)logits;
+    a.B = B; a.T = T; a.V = V; a.ld = ld;
+    a.ids = ids; a.L = L; a.text_start = text_start; a.mask_id = h->cfg.mask_token_id;
+    return a;
+}
+static ImageRowArgs image_row_args(ImageCombine combine, const void* cond, const void* ut, const void* ui, int B, int N, int CB,
+                                   float cfg_scale, float cfg_img, int32_t* argmax_out, void* pmax_out) {
+    ImageRowArgs a{};
+    a.combine = combine;
+    a.cond = (const bf16_t*)cond; a.ut = (const bf16_t*)ut; a.ui = (const bf16_t*)ui;
+    a.B = B; a.N = N; a.CB = CB;
+    a.cfg_scale = cfg_scale; a.cfg_img = cfg_img;
+    a.argmax_out = argmax_out; a.pmax_out = (bf16_t*)pmax_out;
+    return a;
+}
+static void image_row_draw(ImageRowArgs& a, ImageDraw draw, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out,
+                           void* p_sel_out) {
+    a.draw = draw;
+    a.col0 = col0; a.seed = seed; a.counter = counter;
+    a.sampled_out = sampled_out; a.p_sel_out = (bf16_t*)p_sel_out;
+}
+static ImageCommitArgs image_commit_args(CommitRule rule, const mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
+                                         const int32_t* sampled_in, const void* p_in, const int32_t* mask_len_sched, int text_vocab,
+                                         int codebook) {
+    ImageCommitArgs a{};
+    a.rule = rule;
+    a.ids = ids; a.B = B; a.L = L; a.pos_map = pos_map; a.N = N;
+    a.sampled_in = sampled_in; a.p_in = (const bf16_t*)p_in;
+    a.mask_len_sched = mask_len_sched; a.mask_id = h->cfg.mask_token_id; a.text_vocab = text_vocab; a.codebook = codebook;
+    return a;
+}
+static void image_commit_device_noise(ImageCommitArgs& a, uint64_t seed, uint64_t* counter) {
+    a.noise_from = COMMIT_NOISE_DEVICE;
+    a.seed = seed; a.counter = counter;
+}
+
 int mmada_text_select(mmada_handle* h, const void* logits, const void* noisy, int B, int T, int V, int ld_logits,
                       int64_t* ids, int L, int text_start, const int32_t* k, void* scratch, void* stream) {
     if (!h || !logits || !ids || !k || !scratch) return mm_fail("mmada_text_select: null argument");
     if (check_text_span("mmada_text_select", text_start, T, L)) return 1;
-    return launch_text_select((const bf16_t*)logits, (const bf16_t*)noisy, nullptr, 0.f, nullptr, B, T, V, ld_logits, ids, L,
-                              text_start, k, scratch, h->cfg.mask_token_id, (hipStream_t)stream);
+    TextStatsArgs a = text_stats_args(TEXT_PLAIN, h, logits, B, T, V, ld_logits, ids, L, text_start);
+    a.noisy = (const bf16_t*)noisy;
+    return launch_text_select(a, k, scratch, nullptr, (hipStream_t)stream);
 }
 
 int mmada_text_select_random(mmada_handle* h, const void* logits, const void* noisy, const float* uniform, int B, int T,
@@ -278,8 +321,9 @@ int mmada_text_select_random(mmada_handle* h, const void* logits, const void* no
                              void* stream) {
     if (!h || !logits || !uniform || !ids || !k || !scratch) return mm_fail("mmada_text_select_random: null argument");
     if (check_text_span("mmada_text_select_random", text_start, T, L)) return 1;
-    return launch_text_select((const bf16_t*)logits, (const bf16_t*)noisy, nullptr, 0.f, nullptr, B, T, V, ld_logits, ids, L,
-                              text_start, k, scratch, h->cfg.mask_token_id, (hipStream_t)stream, uniform);
+    TextStatsArgs a = text_stats_args(TEXT_PLAIN, h, logits, B, T, V, ld_logits, ids, L, text_start);
+    a.noisy = (const bf16_t*)noisy;
+    return launch_text_select(a, k, scratch, uniform, (hipStream_t)stream);
 }
 
 int mmada_text_select_cfg(mmada_handle* h, const void* cond, const void* uncond, float text_cfg, const int32_t* x0_in,
@@ -287,16 +331,18 @@ int mmada_text_select_cfg(mmada_handle* h, const void* cond, const void* uncond,
                           void* scratch, void* stream) {
     if (!h || !cond || !uncond || !ids || !k || !scratch) return mm_fail("mmada_text_select_cfg: null argument");
     if (check_text_span("mmada_text_select_cfg", text_start, T, L)) return 1;
-    return launch_text_select((const bf16_t*)cond, nullptr, (const bf16_t*)uncond, text_cfg, x0_in, B, T, V, ld_logits, ids,
-                              L, text_start, k, scratch, h->cfg.mask_token_id, (hipStream_t)stream);
+    TextStatsArgs a = text_stats_args(TEXT_CFG, h, cond, B, T, V, ld_logits, ids, L, text_start);
+    a.unc = (const bf16_t*)uncond; a.text_cfg = text_cfg; a.x0_in = x0_in;
+    return launch_text_select(a, k, scratch, nullptr, (hipStream_t)stream);
 }
 
 int mmada_image_probs_m(mmada_handle* h, const void* cond, const void* uncond, int B, int N, int CB, float image_cfg,
                         void* probs_out, int32_t* argmax_out, void* pmax_out, void* stream) {
     if (!h || !cond || !uncond || !argmax_out || !pmax_out) return mm_fail("mmada_image_probs_m: null argument");
     const float one_plus = (float)(1.0 + (double)image_cfg);
-    return launch_image_probs((const bf16_t*)cond, (const bf16_t*)uncond, nullptr, B, N, CB, image_cfg, one_plus,
-                              (bf16_t*)probs_out, argmax_out, (bf16_t*)pmax_out, 1, (hipStream_t)stream);
+    ImageRowArgs a = image_row_args(IMAGE_COMBINE_M, cond, uncond, nullptr, B, N, CB, image_cfg, one_plus, argmax_out, pmax_out);
+    a.probs_out = (bf16_t*)probs_out;
+    return launch_image_row(a, (hipStream_t)stream);
 }
 
 int mmada_image_commit_m(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
@@ -304,8 +350,9 @@ int mmada_image_commit_m(mmada_handle* h, int64_t* ids, int B, int L, const int3
                          const int32_t* mask_len_sched, int text_vocab_size, void* stream) {
     if (!h || !ids || !pos_map || !sampled_in || !p_in || !gumbel || !mask_len_sched)
         return mm_fail("mmada_image_commit_m: null argument");
-    return launch_image_commit(ids, B, L, pos_map, N, sampled_in, (const bf16_t*)p_in, (const bf16_t*)gumbel, remask_temp,
-                               mask_len_sched, h->cfg.mask_token_id, text_vocab_size, 0, 1, (hipStream_t)stream);
+    ImageCommitArgs a = image_commit_args(COMMIT_RULE_M, h, ids, B, L, pos_map, N, sampled_in, p_in, mask_len_sched, text_vocab_size, 0);
+    a.noise = (const bf16_t*)gumbel; a.temp_value = remask_temp;
+    return launch_image_commit(a, (hipStream_t)stream);
 }
 
 int mmada_image_commit_g(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
@@ -313,33 +360,37 @@ int mmada_image_commit_g(mmada_handle* h, int64_t* ids, int B, int L, const int3
                          const int32_t* keep_n, int text_vocab_size, void* stream) {
     if (!h || !ids || !pos_map || !sampled_in || !p_in || !gumbel || !keep_n)
         return mm_fail("mmada_image_commit_g: null argument");
-    return launch_image_commit(ids, B, L, pos_map, N, sampled_in, (const bf16_t*)p_in, (const bf16_t*)gumbel, remask_temp,
-                               keep_n, h->cfg.mask_token_id, text_vocab_size, 0, 2, (hipStream_t)stream);
+    ImageCommitArgs a = image_commit_args(COMMIT_RULE_M_KEEP, h, ids, B, L, pos_map, N, sampled_in, p_in, keep_n, text_vocab_size, 0);
+    a.noise = (const bf16_t*)gumbel; a.temp_value = remask_temp;
+    return launch_image_commit(a, (hipStream_t)stream);
 }
 
 int mmada_image_probs(mmada_handle* h, const void* cond, const void* unc_text, const void* unc_img, int B, int N, int CB,
                       float cfg_scale, float cfg_img, void* probs_out, int32_t* argmax_out, void* pmax_out,
                       void* stream) {
     if (!h || !cond || !argmax_out || !pmax_out) return mm_fail("mmada_image_probs: null argument");
-    return launch_image_probs((const bf16_t*)cond, (const bf16_t*)unc_text, (const bf16_t*)unc_img, B, N, CB, cfg_scale,
-                              cfg_img, (bf16_t*)probs_out, argmax_out, (bf16_t*)pmax_out, 0, (hipStream_t)stream);
+    ImageRowArgs a = image_row_args(IMAGE_COMBINE_A, cond, unc_text, unc_img, B, N, CB, cfg_scale, cfg_img, argmax_out, pmax_out);
+    a.probs_out = (bf16_t*)probs_out;
+    return launch_image_row(a, (hipStream_t)stream);
 }
 
 int mmada_image_commit(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
                        const int32_t* sampled_in, const void* p_in, const void* noise, float remask_temp,
                        const int32_t* mask_len_sched, int text_vocab_size, int codebook_size, void* stream) {
     if (!h || !ids || !pos_map || !sampled_in || !p_in || !mask_len_sched) return mm_fail("mmada_image_commit: null argument");
-    return launch_image_commit(ids, B, L, pos_map, N, sampled_in, (const bf16_t*)p_in, (const bf16_t*)noise, remask_temp,
-                               mask_len_sched, h->cfg.mask_token_id, text_vocab_size, codebook_size, 0, (hipStream_t)stream);
+    ImageCommitArgs a = image_commit_args(COMMIT_RULE_A, h, ids, B, L, pos_map, N, sampled_in, p_in, mask_len_sched, text_vocab_size,
+                                          codebook_size);
+    a.noise = (const bf16_t*)noise; a.temp_value = remask_temp;
+    return launch_image_commit(a, (hipStream_t)stream);
 }
 
 int mmada_image_sample(mmada_handle* h, const void* cond, const void* unc_text, const void* unc_img, int B, int N, int CB,
                        float cfg_scale, float cfg_img, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out,
                        void* p_sel_out, int32_t* argmax_out, void* pmax_out, void* stream) {
     if (!h || !cond || !counter || !sampled_out || !p_sel_out) return mm_fail("mmada_image_sample: null argument");
-    return launch_image_sample((const bf16_t*)cond, (const bf16_t*)unc_text, (const bf16_t*)unc_img, B, N, CB, cfg_scale, cfg_img,
-                               col0, seed, counter, sampled_out, (bf16_t*)p_sel_out, argmax_out, (bf16_t*)pmax_out, 0,
-                               (hipStream_t)stream);
+    ImageRowArgs a = image_row_args(IMAGE_COMBINE_A, cond, unc_text, unc_img, B, N, CB, cfg_scale, cfg_img, argmax_out, pmax_out);
+    image_row_draw(a, IMAGE_DRAW_UNIT, col0, seed, counter, sampled_out, p_sel_out);
+    return launch_image_row(a, (hipStream_t)stream);
 }
 
 int mmada_image_sample_m(mmada_handle* h, const void* cond, const void* uncond, int B, int N, int CB, float image_cfg, int col0,
@@ -347,8 +398,9 @@ int mmada_image_sample_m(mmada_handle* h, const void* cond, const void* uncond, 
                          void* pmax_out, void* stream) {
     if (!h || !cond || !uncond || !counter || !sampled_out || !p_sel_out) return mm_fail("mmada_image_sample_m: null argument");
     const float one_plus = (float)(1.0 + (double)image_cfg);  // as mmada_image_probs_m
-    return launch_image_sample((const bf16_t*)cond, (const bf16_t*)uncond, nullptr, B, N, CB, image_cfg, one_plus, col0, seed,
-                               counter, sampled_out, (bf16_t*)p_sel_out, argmax_out, (bf16_t*)pmax_out, 1, (hipStream_t)stream);
+    ImageRowArgs a = image_row_args(IMAGE_COMBINE_M, cond, uncond, nullptr, B, N, CB, image_cfg, one_plus, argmax_out, pmax_out);
+    image_row_draw(a, IMAGE_DRAW_UNIT, col0, seed, counter, sampled_out, p_sel_out);
+    return launch_image_row(a, (hipStream_t)stream);
 }
 
 int mmada_image_commit_m_sampled(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
@@ -357,9 +409,10 @@ int mmada_image_commit_m_sampled(mmada_handle* h, int64_t* ids, int B, int L, co
                                  void* stream) {
     if (!h || !ids || !pos_map || !sampled_in || !p_in || !remask_temp || !counter || !mask_len_sched)
         return mm_fail("mmada_image_commit_m_sampled: null argument");
-    return launch_image_commit_sampled(ids, B, L, pos_map, N, sampled_in, (const bf16_t*)p_in, remask_temp, seed, counter,
-                                       mask_len_sched, h->cfg.mask_token_id, text_vocab_size, 0, 1, sampled_out,
-                                       (hipStream_t)stream);
+    ImageCommitArgs a = image_commit_args(COMMIT_RULE_M, h, ids, B, L, pos_map, N, sampled_in, p_in, mask_len_sched, text_vocab_size, 0);
+    image_commit_device_noise(a, seed, counter);
+    a.temp_dev = remask_temp; a.sampled_out = sampled_out;
+    return launch_image_commit(a, (hipStream_t)stream);
 }
 
 int mmada_image_sample_g(mmada_handle* h, const void* cond, const void* uncond, int B, int N, int CB, float cfg_scale,
@@ -369,9 +422,10 @@ int mmada_image_sample_g(mmada_handle* h, const void* cond, const void* uncond, 
     if (!(temperature >= 0.f) || __builtin_isinf(temperature))
         return mm_fail("mmada_image_sample_g: temperature %g is not a finite value >= 0", (double)temperature);
     const float one_plus = (float)(1.0 + (double)cfg_scale);  // as mmada_image_probs_m
-    return launch_image_sample((const bf16_t*)cond, (const bf16_t*)uncond, nullptr, B, N, CB, cfg_scale, one_plus, col0, seed,
-                               counter, sampled_out, (bf16_t*)p_sel_out, argmax_out, (bf16_t*)pmax_out, 1, (hipStream_t)stream,
-                               &temperature);
+    ImageRowArgs a = image_row_args(IMAGE_COMBINE_M, cond, uncond, nullptr, B, N, CB, cfg_scale, one_plus, argmax_out, pmax_out);
+    image_row_draw(a, IMAGE_DRAW_TEMPERATURE, col0, seed, counter, sampled_out, p_sel_out);
+    a.temperature = temperature;
+    return launch_image_row(a, (hipStream_t)stream);
 }
 
 int mmada_image_commit_g_sampled(mmada_handle* h, int64_t* ids, int B, int L, const int32_t* pos_map, int N,
@@ -379,8 +433,10 @@ int mmada_image_commit_g_sampled(mmada_handle* h, int64_t* ids, int B, int L, co
                                  const int32_t* keep_n, int text_vocab_size, void* stream) {
     if (!h || !ids || !pos_map || !sampled_in || !p_in || !counter || !keep_n)
         return mm_fail("mmada_image_commit_g_sampled: null argument");
-    return launch_image_commit_sampled(ids, B, L, pos_map, N, sampled_in, (const bf16_t*)p_in, nullptr, seed, counter, keep_n,
-                                       h->cfg.mask_token_id, text_vocab_size, 0, 2, nullptr, (hipStream_t)stream, remask_temp);
+    ImageCommitArgs a = image_commit_args(COMMIT_RULE_M_KEEP, h, ids, B, L, pos_map, N, sampled_in, p_in, keep_n, text_vocab_size, 0);
+    image_commit_device_noise(a, seed, counter);
+    a.temp_value = remask_temp;  // a constant of the run: by value
+    return launch_image_commit(a, (hipStream_t)stream);
 }
 
 int mmada_text_draw_cfg(mmada_handle* h, const void* cond, const void* uncond, float text_cfg, int B, int T, int V, int ld_logits,
@@ -398,9 +454,11 @@ int mmada_image_commit_sampled(mmada_handle* h, int64_t* ids, int B, int L, cons
                                void* stream) {
     if (!h || !ids || !pos_map || !sampled_in || !p_in || !remask_temp || !counter || !mask_len_sched)
         return mm_fail("mmada_image_commit_sampled: null argument");
-    return launch_image_commit_sampled(ids, B, L, pos_map, N, sampled_in, (const bf16_t*)p_in, remask_temp, seed, counter,
-                                       mask_len_sched, h->cfg.mask_token_id, text_vocab_size, codebook_size, 0, nullptr,
-                                       (hipStream_t)stream);
+    ImageCommitArgs a = image_commit_args(COMMIT_RULE_A, h, ids, B, L, pos_map, N, sampled_in, p_in, mask_len_sched, text_vocab_size,
+                                          codebook_size);
+    image_commit_device_noise(a, seed, counter);
+    a.temp_dev = remask_temp;
+    return launch_image_commit(a, (hipStream_t)stream);
 }
 
 int mmada_lfq_gather(mmada_handle* h, const int64_t* idx, int B, int N, int nbits, int dtype_f32, void* out,

@@ -137,41 +137,102 @@ int launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* vT, bf16_t*
 
 int attention_chunks(int pairs, int groups, int keys);  // workgroups per (batch, head) pair (the launch plan; host arithmetic)
 
-// sampler.hip
+// sampler.hip: three row kernels, one launcher and one argument record each.  A field a variant has no use for stays zero.
 struct TextStat { float lmax; int32_t arg; double sum; };  // one rank's record of a text row (vocabulary-parallel head)
-int launch_text_stats_partial(const bf16_t* logits, int B, int T, int Vl, int ld, int col_off, const int64_t* ids, int L,
-                              int text_start, int mask_id, TextStat* out, hipStream_t s);
+
+// Text step part 1: per masked (b, t) row x0 = arg-max, conf = softmax_f64(logits)[x0].
+enum TextMode {
+    TEXT_PLAIN,    // the logits as they are
+    TEXT_CFG,      // logits = cond + text_cfg * (unc - cond), bf16 per op (the M variant)
+    TEXT_PARTIAL,  // this rank's columns [col_off, col_off + V) only: a TextStat per row instead of conf / x0
+};
+struct TextStatsArgs {
+    TextMode mode;
+    const bf16_t* logits;    // [B*T, ld]; TEXT_CFG: the conditional branch
+    const bf16_t* noisy;     // [B*T, ld] or null: the arg-max is taken over these instead (not TEXT_PARTIAL)
+    const bf16_t* unc;       // TEXT_CFG: the unconditional branch
+    float text_cfg;          // TEXT_CFG
+    const int32_t* x0_in;    // [B*T] or null: an externally sampled x0 (not TEXT_PARTIAL)
+    int B, T, V, ld;         // ld % 8 == 0
+    int64_t* ids;            // [B, L]: read here; launch_text_select's commit writes it
+    int L, text_start, mask_id;
+    double* conf_out;        // [B*T]  (launch_text_select points both into its scratch)
+    int32_t* x0_out;         // [B*T]
+    int col_off;             // TEXT_PARTIAL
+    TextStat* stat_out;      // TEXT_PARTIAL: [B*T], published to the other ranks
+};
+int launch_text_stats(const TextStatsArgs& a, hipStream_t s);
+// scratch: conf [B*T] fp64 | x0 [B*T] int32
 int launch_text_commit(const void* scratch, int B, int T, int64_t* ids, int L, int text_start, const int32_t* k, hipStream_t s);
 // the scratch layout of launch_text_commit from a draw: x0 [B*T] int32 is already in place (scratch + B*T*8); conf[i] =
 // (double)logprob[i] where ids holds the mask token, else -inf
 int launch_text_sampled_conf(const float* logprob, int B, int T, const int64_t* ids, int L, int text_start, int mask_id, void* scratch,
                              hipStream_t s);
-int launch_text_select(const bf16_t* logits, const bf16_t* noisy, const bf16_t* unc, float text_cfg, const int32_t* x0_in,
-                       int B, int T, int V, int ld, int64_t* ids, int L, int text_start, const int32_t* k, void* scratch,
-                       int mask_id, hipStream_t s, const float* rand_conf = nullptr);
-int launch_image_probs(const bf16_t* cond, const bf16_t* ut, const bf16_t* ui, int B, int N, int CB, float cfg_scale,
-                       float cfg_img, bf16_t* probs_out, int32_t* argmax_out, bf16_t* pmax_out, int mvar, hipStream_t s);
-int launch_image_commit(int64_t* ids, int B, int L, const int32_t* pos_map, int N, const int32_t* sampled_in,
-                        const bf16_t* p_in, const bf16_t* noise, float remask_temp, const int32_t* mask_len_sched,
-                        int mask_id, int text_vocab, int codebook, int mvar, hipStream_t s);
-// the image step with both draws on the device (sample_noise.h).  launch_image_sample: launch_image_probs' A variant without the
-// probabilities, the token a Gumbel-max draw at (seed, *counter), col0 = the column of codebook entry 0 in the whole vocabulary;
-// argmax_out / pmax_out may be null.  launch_image_commit_sampled: launch_image_commit's A variant with the noise of (seed,
-// *counter) and the temperature in device memory; its last launch adds 1 to *counter.
-// mvar != 0: the M variant of either (launch_image_probs / launch_image_commit with mvar = 1): ut = the uncond branch, cfg_scale =
-// image_cfg, cfg_img = 1 + image_cfg; the commit's noise is the Gumbel value of the same block, and sampled_out (M only, may be
-// null) receives the ids the commit writes back from.
-// temperature != null (M combine only): the draw's key is taken at *temperature (finite, >= 0; 0 = the arg-max of the logits), the
-// statistics stay those of the unscaled logits.  mvar == 2 on the commit: launch_image_commit's keep rule (keep_n.clamp(0, unknown -
-// 1), no floor of 1) with remask_temp null and the temperature by value in temp_value.
-int launch_image_sample(const bf16_t* cond, const bf16_t* ut, const bf16_t* ui, int B, int N, int CB, float cfg_scale,
-                        float cfg_img, int col0, uint64_t seed, const uint64_t* counter, int32_t* sampled_out,
-                        bf16_t* p_sel_out, int32_t* argmax_out, bf16_t* pmax_out, int mvar, hipStream_t s,
-                        const float* temperature = nullptr);
-int launch_image_commit_sampled(int64_t* ids, int B, int L, const int32_t* pos_map, int N, const int32_t* sampled_in,
-                                const bf16_t* p_in, const float* remask_temp, uint64_t seed, uint64_t* counter,
-                                const int32_t* mask_len_sched, int mask_id, int text_vocab, int codebook, int mvar,
-                                int32_t* sampled_out, hipStream_t s, float temp_value = 0.0f);
+// the whole text step: launch_text_stats (TEXT_PLAIN / TEXT_CFG) into scratch, conf replaced by rand_conf [B*T] on masked rows
+// when it is not null (remasking == 'random'), launch_text_commit
+int launch_text_select(TextStatsArgs a, const int32_t* k, void* scratch, const float* rand_conf, hipStream_t s);
+
+// Image step part 1: per (b, n) row the combined logits' bf16 soft-max statistics and, with a draw, the token.
+enum ImageCombine {
+    IMAGE_COMBINE_A,  // cond + cfg_scale * (cond - ut) + cfg_img * (cond - ui); a null branch or a zero scale drops its term
+    IMAGE_COMBINE_M,  // cfg_img * cond - cfg_scale * ut with ut = the uncond branch, cfg_scale = image_cfg, cfg_img = 1 + image_cfg
+};
+enum ImageDraw {
+    IMAGE_DRAW_NONE,         // statistics only: probs_out (may be null), argmax_out, pmax_out
+    IMAGE_DRAW_UNIT,         // Gumbel-max draw at (seed, *counter) with the key at T = 1 (sample_noise.h)
+    IMAGE_DRAW_TEMPERATURE,  // IMAGE_COMBINE_M only: the key at `temperature` (finite, >= 0; 0 = the arg-max of the logits); the
+                             // statistics stay those of the unscaled logits
+};
+struct ImageRowArgs {
+    ImageCombine combine;
+    ImageDraw draw;
+    const bf16_t *cond, *ut, *ui;  // [B*N, CB]
+    int B, N, CB;
+    float cfg_scale, cfg_img;
+    int col0;                      // draw: the column of codebook entry 0 in the whole vocabulary
+    uint64_t seed;                 // draw
+    const uint64_t* counter;       // draw: device [1], read only
+    float temperature;             // IMAGE_DRAW_TEMPERATURE: by value, a constant of the whole run
+    bf16_t* probs_out;             // IMAGE_DRAW_NONE: [B*N, CB] or null
+    int32_t* sampled_out;          // draw: [B*N]
+    bf16_t* p_sel_out;             // draw: [B*N], the bits probs_out would hold at the drawn entry
+    int32_t* argmax_out;           // [B*N]; a draw may leave it and pmax_out null
+    bf16_t* pmax_out;              // [B*N]
+};
+int launch_image_row(const ImageRowArgs& a, hipStream_t s);
+
+// Image step part 2: per batch row confidence, re-mask, write-back.
+enum CommitRule {
+    COMMIT_RULE_A,       // ids clamped to the codebook, log(p + 1e-10), the mask_len lowest in stable order, floor of 1
+    COMMIT_RULE_M,       // no clamp, log(clamp(p, 1e-20)), cut-off compare, floor of 1
+    COMMIT_RULE_M_KEEP,  // COMMIT_RULE_M with generate_image's keep rule: keep_n.clamp(0, unknown - 1), no floor of 1
+};
+enum CommitNoise {
+    COMMIT_NOISE_TENSOR,  // `noise`, temperature temp_value
+    COMMIT_NOISE_DEVICE,  // the normal (A) or Gumbel (M) value of (seed, *counter) (sample_noise.h), temperature *temp_dev —
+                          // with COMMIT_RULE_M_KEEP, and only there, temp_dev is null and the temperature is temp_value.  The
+                          // last launch adds 1 to *counter.
+};
+struct ImageCommitArgs {
+    CommitRule rule;
+    CommitNoise noise_from;
+    int64_t* ids;                   // [B, L]
+    int B, L;
+    const int32_t* pos_map;         // [N]
+    int N;                          // <= 8192
+    const int32_t* sampled_in;      // [B, N]
+    const bf16_t* p_in;             // [B, N]
+    const int32_t* mask_len_sched;  // device [1]
+    int mask_id, text_vocab, codebook;
+    const bf16_t* noise;            // COMMIT_NOISE_TENSOR: [B, N]; null with COMMIT_RULE_A = no noise term, required otherwise
+    float temp_value;
+    const float* temp_dev;          // COMMIT_NOISE_DEVICE: device [1]
+    uint64_t seed;                  // COMMIT_NOISE_DEVICE
+    uint64_t* counter;              // COMMIT_NOISE_DEVICE: device [1]
+    int32_t* sampled_out;           // COMMIT_NOISE_DEVICE with an M rule: [B, N] or null, the ids the commit writes back from
+};
+int launch_image_commit(const ImageCommitArgs& a, hipStream_t s);
+
 // the M text draw: x0_out[b*T + t] = arg-max of the CFG-combined logits' keys at (seed, *counter); its last launch adds 1 to *counter
 int launch_text_draw_cfg(const bf16_t* cond, const bf16_t* unc, float text_cfg, int B, int T, int V, int ld, float temperature,
                          uint64_t seed, uint64_t* counter, int32_t* x0_out, hipStream_t s);

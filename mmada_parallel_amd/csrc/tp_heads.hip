@@ -153,8 +153,13 @@ extern "C" int mmada_text_select_tp(mmada_handle* h, const int32_t* rows, int B,
     if (v1 > v0) {
         if (launch_gemm(EPI_STORE, gemm_bt_args(h->xg, h->lm_head + (size_t)v0 * d, c->head_buf, R, v1 - v0, d, w), s)) return 1;
     }
-    if (launch_text_stats_partial(c->head_buf, B, T, v1 - v0, w, v0, ids, L, text_start, h->cfg.mask_token_id, c->stats_pub, s))
-        return 1;
+    TextStatsArgs ta{};
+    ta.mode = TEXT_PARTIAL;
+    ta.logits = c->head_buf;
+    ta.B = B; ta.T = T; ta.V = v1 - v0; ta.ld = w; ta.col_off = v0;
+    ta.ids = ids; ta.L = L; ta.text_start = text_start; ta.mask_id = h->cfg.mask_token_id;
+    ta.stat_out = c->stats_pub;
+    if (launch_text_stats(ta, s)) return 1;
     double* conf = (double*)scratch;
     int32_t* x0 = (int32_t*)((char*)scratch + (size_t)R * 8);
     const TextStat* gathered = nullptr;

@@ -1,4 +1,4 @@
-"""The image step sampled on the GPU: mmada_image_sample (the Gumbel-max draw beside image_probs_kernel's statistics),
+"""The image step sampled on the GPU: mmada_image_sample (image_row_kernel's Gumbel-max draw beside its statistics),
 mmada_image_commit_sampled (the re-mask noise computed in the commit), mmada_probe_normal, and generate_ti2ti(image_sampler="device")
 with its hipGraph replay.  Everything is equality — against torch's own bf16 ops, the device's own noise (mmada_probe_gumbel /
 mmada_probe_normal), mmada_image_probs, mmada_image_commit and the row head — except the accuracy of z itself, which has a derived

@@ -356,6 +356,41 @@ def test_text_select_with_noisy_argmax(handle):
     assert torch.equal(ids_dev.cpu(), ref)
 
 
+def test_text_select_noisy_argmax_in_the_tail(handle):
+    """The arg-max over `noisy` where V % 8 != 0: the last V % 8 columns are scanned by the tail loop, not by the 16-byte chunks.
+    Planted: a row whose maximum is a tail column, a tie between a tail column and an earlier one (the earlier wins) and a tie
+    between two tail columns (the first wins).  The pad columns [V, ld) of `noisy` hold a larger value still: they are no columns."""
+    from oracle import sampler_oracle as so
+
+    B, T, V, ld, ts = 1, 8, 1004, 1008, 9
+    L = T + 20
+    g = torch.Generator().manual_seed(1004)
+    logits = (torch.randn(B, T, V, generator=g) * 2).to(torch.bfloat16)
+    noisy = (logits.float() + torch.randn(B, T, V, generator=g)).to(torch.bfloat16)
+    noisy[0, 1, 1002] = 50.0
+    noisy[0, 3, 417] = noisy[0, 3, 1001] = 50.0
+    noisy[0, 5, 1000] = noisy[0, 5, 1003] = 50.0
+    ids = torch.randint(0, 1000, (B, L), generator=g)
+    ids[:, ts:ts + T] = synth.MASK
+    ids[0, ts + 7] = 7  # one position already unmasked
+    lpad, npad = torch.zeros(B, T, ld, dtype=torch.bfloat16), torch.full((B, T, ld), 1e4, dtype=torch.bfloat16)
+    lpad[..., :V], npad[..., :V] = logits, noisy
+    lg, nz, ids_dev = lpad.to(DEV), npad.to(DEV), ids.to(DEV)
+    k_dev = torch.tensor([3], dtype=torch.int32, device=DEV)
+    scratch = torch.empty(B * T * 16, dtype=torch.uint8, device=DEV)
+    abi.check(abi.lib().mmada_text_select(handle, lg.data_ptr(), nz.data_ptr(), B, T, V, ld, ids_dev.data_ptr(), L, ts,
+                                          k_dev.data_ptr(), scratch.data_ptr(), st()), "text_select")
+    ref, conf_ref, x0_ref = so.text_select(logits, noisy, ids, ts, [3])
+    assert [int(x0_ref[0, t]) for t in (1, 3, 5)] == [1002, 417, 1000]   # what was planted decides these rows
+    assert torch.equal(ids_dev.cpu(), ref)
+    conf = scratch[: B * T * 8].view(torch.float64).cpu().view(B, T)
+    x0 = scratch[B * T * 8: B * T * 12].view(torch.int32).cpu().view(B, T)
+    assert torch.equal(x0, x0_ref)
+    m = torch.isfinite(conf_ref)
+    assert torch.equal(torch.isfinite(conf), m)
+    assert torch.allclose(conf[m], conf_ref[m], rtol=1e-12, atol=0)
+
+
 # ------------------------------------------------------------------------------------------------------- image sampler
 @pytest.mark.parametrize("B,N,CB,cs,ci,quant", [(1, 64, 8192, 0.0, 4.0, None), (2, 100, 8192, 2.5, 4.0, None),
                                                 (1, 1024, 8192, 2.3, 0.0, None), (1, 50, 512, 0.0, 0.0, 4),
@@ -410,6 +445,64 @@ def test_image_commit_bit_exact(handle, case):
                                                synth.CODEBOOK, st()), "image_commit")
         ref = so.image_commit(ids, pos.to(torch.int32), sampled, p, noise, temp, mlen)
         assert torch.equal(ids_dev.cpu(), ref), f"{case} mlen={mlen}"
+
+
+@pytest.mark.parametrize("known", [0, 3])
+def test_image_commit_without_a_noise_tensor(handle, known):
+    """noise = NULL drops the noise term whatever the temperature says: the ids are those of a zero noise tensor."""
+    from oracle import sampler_oracle as so
+
+    g = torch.Generator().manual_seed(20 + known)
+    B, N, L = 2, 8, 20
+    pos = torch.sort(torch.randperm(L - 4, generator=g)[:N]).values.to(torch.int32) + 2
+    ids = torch.randint(0, 1000, (B, L), generator=g)
+    for b in range(B):
+        ids[b, pos.long()] = synth.MASK
+        kn = pos.long()[torch.randperm(N, generator=g)[:known]]
+        ids[b, kn] = synth.TEXT_VOCAB + torch.randint(0, synth.CODEBOOK, (known,), generator=g)
+    sampled = torch.randint(0, synth.CODEBOOK, (B, N), generator=g, dtype=torch.int32)
+    p = (torch.randint(1, 40, (B, N), generator=g).float() / 4096).to(torch.bfloat16)  # coarse: ties in the log-confidence
+    pos_d, samp_d, p_d = pos.to(DEV), sampled.to(DEV), p.to(DEV)
+    for mlen in (-1, 0, 1, 3, N + 5):
+        ids_dev = ids.to(DEV)
+        ml = torch.tensor([mlen], dtype=torch.int32, device=DEV)
+        abi.check(abi.lib().mmada_image_commit(handle, ids_dev.data_ptr(), B, L, pos_d.data_ptr(), N, samp_d.data_ptr(),
+                                               p_d.data_ptr(), None, 0.37, ml.data_ptr(), synth.TEXT_VOCAB, synth.CODEBOOK,
+                                               st()), "image_commit")
+        ref = so.image_commit(ids, pos, sampled, p, torch.zeros(B, N, dtype=torch.bfloat16), 0.37, mlen)
+        assert torch.equal(ids_dev.cpu(), ref), f"known={known} mlen={mlen}"
+
+
+@pytest.mark.parametrize("CB", [8, 264])
+def test_image_probs_without_a_probabilities_buffer(handle, CB):
+    """probs_out = NULL (A and M combine): arg-max and pmax are the bits of the call that writes the probabilities, and the oracle's."""
+    from oracle import sampler_oracle as so
+
+    B, N = 1, 3
+    g = torch.Generator().manual_seed(CB)
+    c = ((torch.randn(B, N, CB, generator=g) * 1.5 * 2).round() / 2).to(torch.bfloat16)  # coarse: ties for the arg-max
+    ut = (c.float() + torch.randn(B, N, CB, generator=g) * 0.5).to(torch.bfloat16)
+    ui = (c.float() + torch.randn(B, N, CB, generator=g) * 0.5).to(torch.bfloat16)
+    cd, utd, uid = c.to(DEV), ut.to(DEV), ui.to(DEV)
+    lib = abi.lib()
+
+    def run(call, probs):
+        am = torch.full((B, N), -1, dtype=torch.int32, device=DEV)
+        pm = torch.full((B, N), -1.0, dtype=torch.bfloat16, device=DEV)
+        abi.check(call(abi.ptr(probs), am.data_ptr(), pm.data_ptr()), "image_probs")
+        return am.cpu(), bits(pm)
+
+    calls = {
+        "A": (lambda pr, am, pm: lib.mmada_image_probs(handle, cd.data_ptr(), utd.data_ptr(), uid.data_ptr(), B, N, CB, 2.5, 4.0,
+                                                       pr, am, pm, st()), so.image_probs(c, ut, ui, 2.5, 4.0)),
+        "M": (lambda pr, am, pm: lib.mmada_image_probs_m(handle, cd.data_ptr(), utd.data_ptr(), B, N, CB, 3.5, pr, am, pm, st()),
+              so.image_probs_m(c, ut, 3.5)),
+    }
+    for name, (call, ref) in calls.items():
+        am0, pm0 = run(call, None)
+        am1, pm1 = run(call, torch.empty(B, N, CB, dtype=torch.bfloat16, device=DEV))
+        assert torch.equal(am0, am1) and torch.equal(pm0, pm1), name
+        assert torch.equal(am0, ref[0]) and torch.equal(pm0, bits(ref[1])), name
 
 
 def test_log_conf_all_bf16_probabilities(handle, golden_dir):

@@ -1,4 +1,4 @@
-"""The M samplers drawn on the GPU: mmada_image_sample_m (the Gumbel-max draw beside image_probs_kernel<true>'s statistics),
+"""The M samplers drawn on the GPU: mmada_image_sample_m (image_row_kernel<true>'s Gumbel-max draw beside its statistics),
 mmada_image_commit_m_sampled (the Gumbel re-mask noise computed in the commit), mmada_text_draw_cfg (the text draw on the CFG-combined
 logits), and interleave_generate / t2i_generate with image_sampler="device" / text_sampler="device" and the hipGraph replay.  Every
 check is equality — against torch's own bf16 ops, the device's own noise (mmada_probe_gumbel), mmada_image_probs_m,
