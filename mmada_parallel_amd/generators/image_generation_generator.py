@@ -18,10 +18,7 @@ nothing on the host, and a step can replay as one hipGraph (`graph=True`); see g
 """
 from __future__ import annotations
 
-import contextlib
-import ctypes as C
 import math
-import os
 from typing import Callable, Optional
 
 import torch
@@ -29,6 +26,8 @@ import torch
 from .. import abi
 from ..model import LLaDAForMultiModalGeneration
 from .parallel_generator import check_tp_exchange
+from .sampler_options import IMAGE_COUNTER0, check_samplers, seed_u64
+from .step_graph import StepGraphs
 
 
 def cosine_schedule(t: torch.Tensor) -> torch.Tensor:
@@ -62,31 +61,13 @@ def keep_schedule(vq_len: int, timesteps: int, noise_schedule: Callable = cosine
     return out
 
 
-def check_image_sampler(model, image_sampler, sampler_seed, temperature):
-    """The refusals of generate_image's device sampler, in generate_ti2ti's wording; returns whether it is on."""
-    if image_sampler not in ("torch", "device"):
-        raise ValueError(f"image_sampler={image_sampler!r}: 'torch' or 'device'")
-    if image_sampler != "device":
-        return False
-    why = None
-    if not temperature > 0:
-        why = "temperature > 0 (at 0 the image step is an arg-max: nothing is drawn)"
-    elif model.tp_size != 1 or model._comm_in_library:
-        why = "one rank (tensor parallelism is out of scope)"
-    elif sampler_seed is None:
-        why = "sampler_seed"
-    if why:
-        raise ValueError(f"image_sampler='device' needs {why}")
-    return True
-
-
 def _device_image_steps(model, x, slots, win, keep, timesteps, temperature, cfg_scale, uncon_ids, code_start, off, CB, seed64, graph,
                         trace, debug):
     """generate_image's loop with the device sampler: the same forwards, then mmada_image_sample_g and mmada_image_commit_g_sampled
     over buffers that all exist before the loop.  The head runs on ALL N slots every step (the commit ignores the draws at known
     slots), so a step has one shape, takes no argument that changes from step to step and reads nothing on the host; it can be
-    captured and replayed (the scheme of interleave_generator._device_steps).  There is no early exit: a step with nothing unknown
-    re-masks nothing (k = 0) and rewrites every id with itself."""
+    captured and replayed (step_graph.StepGraphs).  There is no early exit: a step with nothing unknown re-masks nothing (k = 0) and
+    rewrites every id with itself."""
     lib, h, device = model._lib, model._handle, model.device
     L, N = x.shape[1], int(slots.numel())
     use_cfg = cfg_scale > 0
@@ -107,7 +88,7 @@ def _device_image_steps(model, x, slots, win, keep, timesteps, temperature, cfg_
     drawn = torch.empty((1, N), dtype=torch.int32, device=device)
     p_sel = torch.empty((1, N), dtype=torch.bfloat16, device=device)
     keep_cur = torch.zeros(1, dtype=torch.int32, device=device)
-    counter = torch.full((1,), 1 << 62, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_g_sampled
+    counter = torch.full((1,), IMAGE_COUNTER0, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_g_sampled
 
     def step_body():
         if trace is not None:
@@ -128,50 +109,14 @@ def _device_image_steps(model, x, slots, win, keep, timesteps, temperature, cfg_
                                                    float(temperature), seed64, counter.data_ptr(), keep_cur.data_ptr(), off, st),
                   "mmada_image_commit_g_sampled")
 
-    if graph is None:
-        graph = os.environ.get("MMADA_GRAPH") == "1"
-    graph = bool(graph) and trace is None and model.graph_capturable()
-    g_step, seen = None, False
-    ws_epoch = model._ws_epoch
-    side = torch.cuda.Stream(device=device) if graph else None
-    if graph:  # the legacy default stream cannot be captured: the loop runs on a side stream, ordered after the caller's
-        side.wait_stream(torch.cuda.current_stream(device))
-    try:
-        with torch.cuda.stream(side) if graph else contextlib.nullcontext():
+    with StepGraphs(model, graph, trace is None) as sg:
+        with sg.stream():
             for step in range(timesteps if N else 0):
                 keep_cur.copy_(keep[step:step + 1])
-                if g_step is not None and model._ws_epoch != ws_epoch:
-                    # the workspace moved after all (a foreign forward in between): captured pointers are stale
-                    lib.mmada_graph_destroy(g_step)
-                    g_step, seen = None, False
-                ws_epoch = model._ws_epoch
-                if g_step is not None:
-                    abi.check(lib.mmada_graph_launch(g_step, abi.stream_ptr()), "mmada_graph_launch")
-                    model.graph_replays += 1
-                    continue
-                capture = graph and seen   # the first step runs eagerly (first calls set attributes / carve)
-                if capture:
-                    abi.check(lib.mmada_graph_begin(abi.stream_ptr()), "mmada_graph_begin")
-                try:
-                    step_body()
-                except Exception:
-                    if capture:
-                        lib.mmada_graph_abort(abi.stream_ptr())
-                    raise
-                if capture:
-                    g = C.c_void_p()
-                    abi.check(lib.mmada_graph_end(abi.stream_ptr(), C.byref(g)), "mmada_graph_end")
-                    g_step = g
-                    model.graph_nodes[("generate_image",)] = lib.mmada_graph_num_nodes(g)
-                    abi.check(lib.mmada_graph_launch(g, abi.stream_ptr()), "mmada_graph_launch")   # the captured step's own run
-                seen = True
+                sg.step(("generate_image",), step_body)
                 if debug:
                     print(f"[generate_image] step {step}: keep {int(keep[step])}")
-        if graph:
-            torch.cuda.current_stream(device).wait_stream(side)   # whoever consumes the ids sees the finished run
-    finally:
-        if g_step is not None:
-            lib.mmada_graph_destroy(g_step)
+        sg.join()   # whoever consumes the ids sees the finished run
 
 
 @torch.no_grad()
@@ -225,7 +170,7 @@ def generate_image(
         raise TypeError("generate_image (MI355X) needs mmada_parallel_amd.LLaDAForMultiModalGeneration")
     if temperature > 8.0:
         raise ValueError("temperature > 8 is not supported (known slots must out-rank every noisy confidence)")
-    dev_img = check_image_sampler(model, image_sampler, sampler_seed, temperature)
+    dev_img, _ = check_samplers(model, image_sampler, sampler_seed=sampler_seed, temperature=temperature)
     rng = rng or TorchRng()
     lib, h, device = model._lib, model._handle, model.device
     prompt = prompt.to(device)
@@ -252,7 +197,7 @@ def generate_image(
     win = (int(slots[0]), int(slots[-1]) + 1) if N else None   # the only rows ever decoded (one host read, before the loop)
     if dev_img:
         _device_image_steps(model, x, slots, win, keep, timesteps, temperature, cfg_scale, uncon_ids, code_start, off, CB,
-                            int(sampler_seed) & 0xFFFFFFFFFFFFFFFF, graph, trace, debug)
+                            seed_u64(sampler_seed), graph, trace, debug)
         check_tp_exchange(model)
         vq_ids = x[0, code_start:-2]                                   # :239-241
         return vq_ids[vq_ids != newline_id].view(1, seq_len)

@@ -15,10 +15,7 @@ csrc/sample_noise.h, and a step can then replay as one hipGraph (`graph=True`); 
 """
 from __future__ import annotations
 
-import contextlib
-import ctypes as C
 import math
-import os
 from typing import Callable, Dict, Optional
 
 import torch
@@ -26,6 +23,8 @@ import torch
 from .. import abi
 from ..model import LLaDAForMultiModalGeneration
 from .parallel_generator import check_tp_exchange, mask_len_schedule
+from .sampler_options import IMAGE_COUNTER0, check_samplers, seed_u64
+from .step_graph import StepGraphs
 
 
 def cosine_schedule(t):
@@ -67,154 +66,6 @@ def _log(t, eps=1e-20):
     return torch.log(t.clamp(min=eps))  # sampling.py:11-12
 
 
-def check_m_samplers(model, image_sampler, text_sampler="torch", sampler_seed=None, text_temperature=0.0,
-                     temperature_name="text_temperature"):
-    """The refusals of the M generators' device samplers, in generate_ti2ti's wording; returns (dev_img, dev_text).
-    temperature_name: what the caller's signature calls the text temperature (mmu_generate: `temperature`)."""
-    if text_sampler not in ("torch", "device"):
-        raise ValueError(f"text_sampler={text_sampler!r}: 'torch' or 'device'")
-    if image_sampler not in ("torch", "device"):
-        raise ValueError(f"image_sampler={image_sampler!r}: 'torch' or 'device'")
-    dev_img, dev_text = image_sampler == "device", text_sampler == "device"
-    if dev_text and not text_temperature > 0:
-        raise ValueError(f"text_sampler='device' needs {temperature_name} > 0 (at 0 the text step is an arg-max: nothing is drawn)")
-    for name, on in (("text_sampler", dev_text), ("image_sampler", dev_img)):
-        if on and (model.tp_size != 1 or model._comm_in_library):
-            raise ValueError(f"{name}='device' needs one rank (tensor parallelism is out of scope)")
-        if on and sampler_seed is None:
-            raise ValueError(f"{name}='device' needs sampler_seed")
-    return dev_img, dev_text
-
-
-def _device_steps(model, ids0, uncond_input_ids, P, T, N, CB, text_vocab, text_cfg, image_cfg, text_temperature, text_steps,
-                  img_steps, k_dev, mlen_dev, temps, pos_map, text_rows, img_rows, scratch, argmax, pmax, rng, generator, trace,
-                  dev_img, dev_text, seed64, graph):
-    """interleave_generate's loop with a device sampler: the same launches over buffers that all exist before the loop, so that a
-    step takes no argument that changes from step to step and can be captured and replayed (generate_ti2ti's scheme, _ti2ti_steps).
-    A sampler left at "torch" still draws from `rng` in the reference's order; such a run is not captured."""
-    lib, h, device = model._lib, model._handle, model.device
-    L, V = ids0.shape[1], model.vocab
-    text_start, img_start = L - T, P + 1
-    # cond and uncond as ONE fixed [2, L] batch: row 0 IS the running ids, row 1 = the uncond prompt + a copy of row 0's tail (:166-169)
-    both = torch.empty((2, L), dtype=torch.long, device=device)
-    both[0].copy_(ids0[0])
-    both[1, :P].copy_(uncond_input_ids[0])
-    ids = both[0:1]
-    model._ensure_ws(2, L)   # before the first step: a workspace that grew later would leave a captured graph pointing at freed memory
-    tl = torch.empty((2 * T, V), dtype=torch.bfloat16, device=device)
-    il = torch.empty((2 * N, CB), dtype=torch.bfloat16, device=device) if img_steps else None
-    x0 = torch.zeros(T, dtype=torch.int32, device=device) if text_temperature != 0 else None
-    k_cur = torch.zeros(1, dtype=torch.int32, device=device)
-    mlen_cur = torch.zeros(1, dtype=torch.int32, device=device)
-    text_counter = torch.zeros(1, dtype=torch.int64, device=device)          # advanced by mmada_text_draw_cfg
-    if dev_img:
-        img_counter = torch.full((1,), 1 << 62, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_m_sampled
-        temp_dev = torch.tensor(temps, dtype=torch.float32, device=device)
-        temp_cur = torch.zeros(1, dtype=torch.float32, device=device)
-        drawn = torch.empty((1, N), dtype=torch.int32, device=device)
-        p_sel = torch.empty((1, N), dtype=torch.bfloat16, device=device)
-        sampled = torch.empty((1, N), dtype=torch.int32, device=device)
-    mask_id = int(model.config.get("mask_token_id", 126336))
-    state = {"sampled": None}
-
-    def step_body(i, is_img):
-        both[1, P:].copy_(both[0, P:])
-        if trace is not None:
-            trace.append(both.cpu().clone())
-        model.forward_body(both, consumed=(img_start if is_img else text_start, L))   # one batch-2 forward (:171)
-        st = abi.stream_ptr()
-        model.head_rows(text_rows, 0, V, out=tl)
-        if is_img:
-            model.head_rows(img_rows, text_vocab, text_vocab + CB, out=il)
-        if text_temperature != 0 and dev_text:
-            abi.check(lib.mmada_text_draw_cfg(h, tl[:T].data_ptr(), tl[T:].data_ptr(), text_cfg, 1, T, V, V, text_temperature,
-                                              seed64, text_counter.data_ptr(), x0.data_ptr(), st), "mmada_text_draw_cfg")
-        elif text_temperature != 0:
-            comb = tl[:T] + text_cfg * (tl[T:] - tl[:T])         # :173 on the text rows, bf16 tensor ops
-            x0.copy_(rng.text_gumbel_argmax(comb.view(1, T, V), text_temperature).view(T))
-        abi.check(lib.mmada_text_select_cfg(h, tl[:T].data_ptr(), tl[T:].data_ptr(), text_cfg, abi.ptr(x0), 1, T, V, V,
-                                            ids.data_ptr(), L, text_start, k_cur.data_ptr(), scratch.data_ptr(), st),
-                  "mmada_text_select_cfg")
-        if is_img and dev_img:
-            abi.check(lib.mmada_image_sample_m(h, il[:N].data_ptr(), il[N:].data_ptr(), 1, N, CB, image_cfg, text_vocab, seed64,
-                                               img_counter.data_ptr(), drawn.data_ptr(), p_sel.data_ptr(), None, None, st),
-                      "mmada_image_sample_m")
-            abi.check(lib.mmada_image_commit_m_sampled(h, ids.data_ptr(), 1, L, pos_map.data_ptr(), N, drawn.data_ptr(),
-                                                       p_sel.data_ptr(), temp_cur.data_ptr(), seed64, img_counter.data_ptr(),
-                                                       mlen_cur.data_ptr(), text_vocab, sampled.data_ptr(), st),
-                      "mmada_image_commit_m_sampled")
-        elif is_img:   # the reference's draws (:216-241) on the fixed buffers
-            probs = torch.empty((N, CB), dtype=torch.bfloat16, device=device)
-            abi.check(lib.mmada_image_probs_m(h, il[:N].data_ptr(), il[N:].data_ptr(), 1, N, CB, image_cfg, probs.data_ptr(),
-                                              argmax.data_ptr(), pmax.data_ptr(), st), "mmada_image_probs_m")
-            cur = ids[:, img_start:img_start + N]
-            unknown = cur == mask_id
-            s64 = torch.where(unknown, rng.multinomial(probs, generator).view(1, N), cur - text_vocab)
-            p = torch.gather(probs.view(1, N, CB), -1, s64[..., None]).squeeze(-1)
-            p = torch.where(unknown, p, torch.finfo(p.dtype).max).contiguous()
-            gumbel = (-_log(-_log(rng.uniform_like(p, generator)))).contiguous()
-            s32 = s64.to(torch.int32).contiguous()
-            abi.check(lib.mmada_image_commit_m(h, ids.data_ptr(), 1, L, pos_map.data_ptr(), N, s32.data_ptr(), p.data_ptr(),
-                                               gumbel.data_ptr(), float(temps[i]), mlen_cur.data_ptr(), text_vocab, st),
-                      "mmada_image_commit_m")
-            state["sampled"] = s64
-
-    if graph is None:
-        graph = os.environ.get("MMADA_GRAPH") == "1"
-    graph = (bool(graph) and dev_img and (text_temperature == 0 or dev_text) and trace is None
-             and model.graph_capturable())   # a replayed step would otherwise replay torch's draws
-    graphs, seen = {}, set()
-    ws_epoch = model._ws_epoch
-    side = torch.cuda.Stream(device=device) if graph else None
-    if graph:  # the legacy default stream cannot be captured: the loop runs on a side stream, ordered after the caller's
-        side.wait_stream(torch.cuda.current_stream(device))
-    try:
-        with torch.cuda.stream(side) if graph else contextlib.nullcontext():
-            for i in range(text_steps):
-                is_img = i in img_steps
-                k_cur.copy_(k_dev[i])
-                mlen_cur.copy_(mlen_dev[i:i + 1])
-                if dev_img:
-                    temp_cur.copy_(temp_dev[i:i + 1])
-                if graph and graphs and model._ws_epoch != ws_epoch:
-                    # the workspace moved after all (a foreign forward in between): captured pointers are stale
-                    for g_old in graphs.values():
-                        lib.mmada_graph_destroy(g_old)
-                    graphs.clear()
-                    seen.clear()
-                ws_epoch = model._ws_epoch
-                if graph and is_img in graphs:
-                    abi.check(lib.mmada_graph_launch(graphs[is_img], abi.stream_ptr()), "mmada_graph_launch")
-                    model.graph_replays += 1
-                    continue
-                capture = graph and is_img in seen   # first step of a kind: eager (first calls set attributes / carve)
-                if capture:
-                    abi.check(lib.mmada_graph_begin(abi.stream_ptr()), "mmada_graph_begin")
-                try:
-                    step_body(i, is_img)
-                except Exception:
-                    if capture:
-                        lib.mmada_graph_abort(abi.stream_ptr())
-                    raise
-                if capture:
-                    g = C.c_void_p()
-                    abi.check(lib.mmada_graph_end(abi.stream_ptr(), C.byref(g)), "mmada_graph_end")
-                    graphs[is_img] = g
-                    model.graph_nodes[("interleave", is_img)] = lib.mmada_graph_num_nodes(g)
-                    abi.check(lib.mmada_graph_launch(g, abi.stream_ptr()), "mmada_graph_launch")
-                    model.graph_replays += 1
-                seen.add(is_img)
-        if graph:
-            torch.cuda.current_stream(device).wait_stream(side)   # whoever consumes the ids sees the finished run
-    finally:
-        for g in graphs.values():
-            lib.mmada_graph_destroy(g)
-    check_tp_exchange(model)   # tensor parallel: a timed-out hand-off raises instead of returning void tokens
-    if dev_img and img_steps:
-        state["sampled"] = sampled.long()
-    return state["sampled"], ids[:, text_start:]
-
-
 @torch.no_grad()
 def interleave_generate(
     model,
@@ -241,31 +92,35 @@ def interleave_generate(
 ):
     """Returns (image ids [1, num_vq_tokens], text ids [1, max_seq_length]) like the reference.
 
+    ONE loop for every sampler setting: the launches of a step run over buffers that all exist before the loop, so that a step
+    takes no argument that changes from step to step (k, mask_len and the re-mask temperature are copied per step into device [1]
+    buffers).  A sampler left at "torch" draws from `rng` in the reference's order, on those buffers.
+
     `image_sampler="device"` (opt-in; the default "torch" is the reference's path, draw for draw): an image step is
     mmada_head_rows, mmada_image_sample_m (col0 = len(tokenizer)) and mmada_image_commit_m_sampled.  Neither the [N, codebook]
     probabilities nor any torch random tensor exists and `rng` / `generator` are never called for it.  The token is a Gumbel-max draw
     at temperature 1 over the CFG-combined bf16 logits — it samples their soft-max evaluated in fp32, where the reference's
     multinomial samples the bf16-rounded probabilities — and the re-mask noise is a counter-based Gumbel value per image position,
     both keyed by `sampler_seed` (required) and a counter that starts at 1 << 62 per call and advances by 1 per image step.  The
-    re-mask temperature image_temperature * (1 - (i + 1) / text_steps) is host double arithmetic as on the torch path, cast to fp32
-    and copied per step into a device [1] buffer, as k and mask_len are.  One rank only.
+    re-mask temperature image_temperature * (1 - (i + 1) / text_steps) is host double arithmetic as on the torch path, cast to fp32.
+    One rank only.
 
     `text_sampler="device"` (opt-in; needs text_temperature > 0): the text draw is mmada_text_draw_cfg on the cond / uncond halves of
     the text logits — a Gumbel-max draw in fp32 from soft-max(combined / text_temperature) instead of the reference's float64
     exp(l) / (-log u)^T on a [T, V] float64 copy — keyed by `sampler_seed` and a counter that starts at 0 and advances by 1 per step.
     The draws of neither sampler reproduce torch's RNG stream.
 
-    `graph` (None = env MMADA_GRAPH=1): replay each kind of step — text-only, image step — as ONE hipGraph (mmada_graph_*), as
-    generate_ti2ti does: the first step of a kind runs eagerly, the second is captured, the rest replay, bit-identical to the eager
-    run.  Only when image_sampler == "device" and (text_temperature == 0 or text_sampler == "device") and trace is None and the
-    forward issues no host-side collective; otherwise the run is eager."""
+    `graph` (None = env MMADA_GRAPH=1): replay each kind of step — text-only, image step — as ONE hipGraph (step_graph.StepGraphs):
+    the first step of a kind runs eagerly, the second is captured, the rest replay, bit-identical to the eager run.  Only when
+    image_sampler == "device" and (text_temperature == 0 or text_sampler == "device") and trace is None and the forward issues no
+    host-side collective; otherwise the run is eager."""
     if not isinstance(model, LLaDAForMultiModalGeneration):
         raise TypeError("interleave_generate (MI355X) needs mmada_parallel_amd.LLaDAForMultiModalGeneration")
     if remasking != "low_confidence":
         raise NotImplementedError(remasking)
     if not (text_cfg or image_cfg):
         raise ValueError("text_cfg and image_cfg cannot be both 0")  # modeling_mmada.py:176-177
-    dev_img, dev_text = check_m_samplers(model, image_sampler, text_sampler, sampler_seed, text_temperature)
+    dev_img, dev_text = check_samplers(model, image_sampler, text_sampler, sampler_seed, text_temperature=text_temperature)
     rng = rng or TorchRng()
     lib, h, device = model._lib, model._handle, model.device
     uni_prompting = kwargs.get("uni_prompting", None)
@@ -286,19 +141,20 @@ def interleave_generate(
 
     out_ids = torch.cat([full(1, reserved_token_mapping['<|soi|>']), full(N, mask_id),
                          full(1, reserved_token_mapping['<|eoi|>']), full(1, tok.bos_token_id), full(T - 1, mask_id)], dim=1)
-    ids = torch.cat([input_ids, out_ids], dim=1).contiguous()  # combined_input_ids (:144)
-    L = ids.shape[1]
-    Lu = uncond_input_ids.shape[1] + out_ids.shape[1]
-    if Lu != L:
+    L = P + out_ids.shape[1]
+    if uncond_input_ids.shape[1] != P:
         raise ValueError("cond and uncond prompts must have equal length (the reference batches them, :171)")
     text_start, img_start = L - T, P + 1
+    # cond and uncond as ONE fixed [2, L] batch: row 0 IS the running combined_input_ids (:144), row 1 = the uncond prompt + a copy of
+    # row 0's tail, refreshed every step (:166-169)
+    both = torch.cat([torch.cat([input_ids, out_ids], dim=1), torch.cat([uncond_input_ids, out_ids], dim=1)], dim=0).contiguous()
+    ids = both[0:1]
 
-    text_masked0 = (ids[:, text_start:] == mask_id).cpu()
-    num_transfer = get_num_transfer_tokens(text_masked0, text_steps)
+    num_transfer = get_num_transfer_tokens((ids[:, text_start:] == mask_id).cpu(), text_steps)
     img_steps = set(torch.linspace(text_steps // 4, text_steps - 1, image_steps).round().int().tolist())
-    mlen = mask_len_schedule(N, text_steps, noise_schedule)
+    temps = [image_temperature * (1.0 - 1.0 * (s + 1) / text_steps) for s in range(text_steps)]   # host double
     k_dev = num_transfer.t().contiguous().to(device=device, dtype=torch.int32)
-    mlen_dev = torch.tensor(mlen, dtype=torch.int32, device=device)
+    mlen_dev = torch.tensor(mask_len_schedule(N, text_steps, noise_schedule), dtype=torch.int32, device=device)
     pos_map = torch.arange(img_start, img_start + N, dtype=torch.int32, device=device)
     ar = torch.arange(text_start, L, dtype=torch.int32, device=device)
     text_rows = torch.cat([ar, ar + L])                       # cond rows then uncond rows (batch-major)
@@ -306,55 +162,80 @@ def interleave_generate(
     scratch = torch.empty(T * 16, dtype=torch.uint8, device=device)
     argmax = torch.empty((1, N), dtype=torch.int32, device=device)
     pmax = torch.empty((1, N), dtype=torch.bfloat16, device=device)
+    model._ensure_ws(2, L)   # before the first step: a workspace that grew later would leave a captured graph pointing at freed memory
+    tl = torch.empty((2 * T, V), dtype=torch.bfloat16, device=device)                   # [2T, V]: cond rows, uncond rows
+    il = torch.empty((2 * N, CB), dtype=torch.bfloat16, device=device) if img_steps else None
+    x0 = torch.zeros(T, dtype=torch.int32, device=device) if text_temperature != 0 else None
+    k_cur = torch.zeros(1, dtype=torch.int32, device=device)
+    mlen_cur = torch.zeros(1, dtype=torch.int32, device=device)
+    seed64 = seed_u64(sampler_seed) if dev_img or dev_text else None
+    if dev_text:
+        text_counter = torch.zeros(1, dtype=torch.int64, device=device)          # advanced by mmada_text_draw_cfg
+    if dev_img:
+        img_counter = torch.full((1,), IMAGE_COUNTER0, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_m_sampled
+        temp_dev = torch.tensor(temps, dtype=torch.float32, device=device)
+        temp_cur = torch.zeros(1, dtype=torch.float32, device=device)
+        drawn = torch.empty((1, N), dtype=torch.int32, device=device)
+        p_sel = torch.empty((1, N), dtype=torch.bfloat16, device=device)
+        sampled = torch.empty((1, N), dtype=torch.int32, device=device)
     sampled_ids = None
 
-    if dev_img or dev_text:
-        temps = [image_temperature * (1.0 - 1.0 * (i + 1) / text_steps) for i in range(text_steps)]   # host double, as below
-        return _device_steps(model, ids, uncond_input_ids, P, T, N, CB, text_vocab, float(text_cfg), float(image_cfg),
-                             float(text_temperature), text_steps, img_steps, k_dev, mlen_dev, temps, pos_map, text_rows, img_rows,
-                             scratch, argmax, pmax, rng, generator, trace, dev_img, dev_text,
-                             int(sampler_seed) & 0xFFFFFFFFFFFFFFFF, graph)
-
-    for i in range(text_steps):
-        unc = torch.cat([uncond_input_ids, ids[:, P:]], dim=1)  # :166-169
-        both = torch.cat([ids, unc], dim=0).contiguous()
+    def step_body(i, is_img):
+        nonlocal sampled_ids
+        both[1, P:].copy_(both[0, P:])
         if trace is not None:
             trace.append(both.cpu().clone())
-        is_img = i in img_steps
         # rows read this step: the text span, plus the image span on image steps (the last block computes only those)
         model.forward_body(both, consumed=(img_start if is_img else text_start, L))   # one batch-2 forward (:171)
         st = abi.stream_ptr()
-        tl = model.head_rows(text_rows, 0, V)                    # [2T, V]: cond rows, uncond rows
-        il = model.head_rows(img_rows, text_vocab, text_vocab + CB) if is_img else None
-
-        x0_in = None
-        if text_temperature != 0:
-            comb = tl[:T] + text_cfg * (tl[T:] - tl[:T])         # :173 on the text rows, bf16 tensor ops
-            x0_in = rng.text_gumbel_argmax(comb.view(1, T, V), text_temperature).to(torch.int32).contiguous()
-        tl_c, tl_u = tl[:T], tl[T:]  # views of `tl`
-        abi.check(lib.mmada_text_select_cfg(h, tl_c.data_ptr(), tl_u.data_ptr(), float(text_cfg), abi.ptr(x0_in), 1, T,
-                                            V, V, ids.data_ptr(), L, text_start, k_dev[i].data_ptr(), scratch.data_ptr(),
-                                            st), "mmada_text_select_cfg")
-
+        model.head_rows(text_rows, 0, V, out=tl)
         if is_img:
+            model.head_rows(img_rows, text_vocab, text_vocab + CB, out=il)
+        if text_temperature != 0 and dev_text:
+            abi.check(lib.mmada_text_draw_cfg(h, tl[:T].data_ptr(), tl[T:].data_ptr(), float(text_cfg), 1, T, V, V,
+                                              float(text_temperature), seed64, text_counter.data_ptr(), x0.data_ptr(), st),
+                      "mmada_text_draw_cfg")
+        elif text_temperature != 0:
+            comb = tl[:T] + text_cfg * (tl[T:] - tl[:T])         # :173 on the text rows, bf16 tensor ops
+            x0.copy_(rng.text_gumbel_argmax(comb.view(1, T, V), text_temperature).view(T))
+        abi.check(lib.mmada_text_select_cfg(h, tl[:T].data_ptr(), tl[T:].data_ptr(), float(text_cfg), abi.ptr(x0), 1, T, V, V,
+                                            ids.data_ptr(), L, text_start, k_cur.data_ptr(), scratch.data_ptr(), st),
+                  "mmada_text_select_cfg")
+        if is_img and dev_img:
+            abi.check(lib.mmada_image_sample_m(h, il[:N].data_ptr(), il[N:].data_ptr(), 1, N, CB, float(image_cfg), text_vocab, seed64,
+                                               img_counter.data_ptr(), drawn.data_ptr(), p_sel.data_ptr(), None, None, st),
+                      "mmada_image_sample_m")
+            abi.check(lib.mmada_image_commit_m_sampled(h, ids.data_ptr(), 1, L, pos_map.data_ptr(), N, drawn.data_ptr(),
+                                                       p_sel.data_ptr(), temp_cur.data_ptr(), seed64, img_counter.data_ptr(),
+                                                       mlen_cur.data_ptr(), text_vocab, sampled.data_ptr(), st),
+                      "mmada_image_commit_m_sampled")
+        elif is_img:   # the reference's draws (:216-241)
             probs = torch.empty((N, CB), dtype=torch.bfloat16, device=device)
-            il_c, il_u = il[:N], il[N:]
-            abi.check(lib.mmada_image_probs_m(h, il_c.data_ptr(), il_u.data_ptr(), 1, N, CB, float(image_cfg),
-                                              probs.data_ptr(), argmax.data_ptr(), pmax.data_ptr(), st),
-                      "mmada_image_probs_m")
-            drawn = rng.multinomial(probs, generator).view(1, N)
+            abi.check(lib.mmada_image_probs_m(h, il[:N].data_ptr(), il[N:].data_ptr(), 1, N, CB, float(image_cfg), probs.data_ptr(),
+                                              argmax.data_ptr(), pmax.data_ptr(), st), "mmada_image_probs_m")
             cur = ids[:, img_start:img_start + N]
             unknown = cur == mask_id
-            sampled_ids = torch.where(unknown, drawn, cur - text_vocab)                       # :224-225
-            p_sel = torch.gather(probs.view(1, N, CB), -1, sampled_ids.long()[..., None]).squeeze(-1)
-            p_sel = torch.where(unknown, p_sel, torch.finfo(p_sel.dtype).max)                 # :233
-            ratio = 1.0 * (i + 1) / text_steps
-            temperature = image_temperature * (1.0 - ratio)
-            gumbel = (-_log(-_log(rng.uniform_like(p_sel, generator)))).contiguous()          # sampling.py:15-17
-            s32, p_c = sampled_ids.to(torch.int32).contiguous(), p_sel.contiguous()  # named: must outlive the launch
-            abi.check(lib.mmada_image_commit_m(h, ids.data_ptr(), 1, L, pos_map.data_ptr(), N, s32.data_ptr(),
-                                               p_c.data_ptr(), gumbel.data_ptr(), float(temperature),
-                                               mlen_dev[i:i + 1].data_ptr(), text_vocab, st), "mmada_image_commit_m")
+            sampled_ids = torch.where(unknown, rng.multinomial(probs, generator).view(1, N), cur - text_vocab)   # :224-225
+            p = torch.gather(probs.view(1, N, CB), -1, sampled_ids[..., None]).squeeze(-1)
+            p = torch.where(unknown, p, torch.finfo(p.dtype).max).contiguous()                # :233
+            gumbel = (-_log(-_log(rng.uniform_like(p, generator)))).contiguous()              # sampling.py:15-17
+            s32 = sampled_ids.to(torch.int32).contiguous()
+            abi.check(lib.mmada_image_commit_m(h, ids.data_ptr(), 1, L, pos_map.data_ptr(), N, s32.data_ptr(), p.data_ptr(),
+                                               gumbel.data_ptr(), float(temps[i]), mlen_cur.data_ptr(), text_vocab, st),
+                      "mmada_image_commit_m")
 
+    # a replayed step would otherwise replay torch's draws
+    with StepGraphs(model, graph, dev_img and (text_temperature == 0 or dev_text) and trace is None) as sg:
+        with sg.stream():
+            for i in range(text_steps):
+                is_img = i in img_steps
+                k_cur.copy_(k_dev[i])
+                mlen_cur.copy_(mlen_dev[i:i + 1])
+                if dev_img:
+                    temp_cur.copy_(temp_dev[i:i + 1])
+                sg.step(is_img, lambda: step_body(i, is_img), nodes_key=("interleave", is_img))
+        sg.join()   # whoever consumes the ids sees the finished run
     check_tp_exchange(model)   # tensor parallel: a timed-out hand-off raises instead of returning void tokens
+    if dev_img and img_steps:
+        sampled_ids = sampled.long()
     return sampled_ids, ids[:, text_start:]

@@ -26,8 +26,9 @@ import torch
 
 from .. import abi
 from ..model import LLaDAForMultiModalGeneration
-from .interleave_generator import TorchRng, check_m_samplers, get_num_transfer_tokens
+from .interleave_generator import TorchRng, get_num_transfer_tokens
 from .parallel_generator import check_tp_exchange
+from .sampler_options import check_samplers, seed_u64
 
 
 @torch.no_grad()
@@ -53,7 +54,8 @@ def mmu_generate(model, idx=None, input_embeddings=None, max_new_tokens=128, ste
         raise NotImplementedError("input_embeddings")
     if remasking != 'low_confidence':
         raise NotImplementedError(remasking)  # 'random' is torch.rand plumbing only; not on any call path of the reference
-    _, dev_text = check_m_samplers(model, "torch", text_sampler, sampler_seed, temperature, temperature_name="temperature")
+    _, dev_text = check_samplers(model, text_sampler=text_sampler, sampler_seed=sampler_seed, text_temperature=temperature,
+                                 text_temperature_name="temperature")
     if dev_text and idx.shape[0] * (2 if cfg_scale > 0.0 else 1) >= 2 and os.environ.get("MMADA_MICROBATCH") == "1":
         raise ValueError("text_sampler='device' needs a forward without micro-batched lanes (MMADA_MICROBATCH=1 splits the batch)")
     del attention_mask  # dead in the reference (see the module docstring): attention is unmasked
@@ -77,7 +79,7 @@ def mmu_generate(model, idx=None, input_embeddings=None, max_new_tokens=128, ste
     ar = torch.arange(BL, dtype=torch.int32, device=device)
     boff = (torch.arange(B, dtype=torch.int32, device=device) * L)[:, None]
     if dev_text:
-        seed64 = int(sampler_seed) & 0xFFFFFFFFFFFFFFFF
+        seed64 = seed_u64(sampler_seed)
         counter = torch.zeros(1, dtype=torch.int64, device=device)   # advanced by the draw, once per step
         x0_dev = torch.empty(B * BL, dtype=torch.int32, device=device)
         lg_dev = torch.empty((2 * B * BL, V), dtype=torch.bfloat16, device=device) if use_cfg else None

@@ -14,8 +14,6 @@ All per-step counts (text k, image mask_len) are schedule-determined (SURVEY A.5
 """
 from __future__ import annotations
 
-import contextlib
-import ctypes as C
 import math
 import os
 from typing import List
@@ -24,6 +22,8 @@ import torch
 
 from .. import abi
 from ..model import LLaDAForMultiModalGeneration
+from .sampler_options import IMAGE_COUNTER0, check_samplers, seed_u64
+from .step_graph import StepGraphs
 
 MASK_TOKEN = 126336
 NEW_LINE = 126084
@@ -150,7 +150,7 @@ def _ti2ti_steps(
     `image_step_list` overrides the schedule of image steps (default: reference :157-159).
 
     `graph` (None = env MMADA_GRAPH=1): replay each kind of step — text-only, image step — as ONE hipGraph
-    (mmada_graph_*): the launches of a step are a fixed sequence over fixed buffers because k, mask_len and the set of
+    (step_graph.StepGraphs): the launches of a step are a fixed sequence over fixed buffers because k, mask_len and the set of
     forwards are schedule-determined.  The first step of each kind runs eagerly, the second is captured,
     the rest replay.  Only when every draw of a step is device-side or absent — (temperature == 0 or image_sampler == "device")
     and (text_temperature == 0 or text_sampler == "device"): a replayed step would otherwise replay torch's draws, and the torch
@@ -185,36 +185,13 @@ def _ti2ti_steps(
         # the reference asks torch.rand for an int64 uniform on this path (:195-196) and raises
         raise RuntimeError("remasking='random' with an explicit generator raises in the reference too "
                            "(torch.rand(dtype=int64)); pass generator=None")
-    if text_sampler not in ("torch", "device"):
-        raise ValueError(f"text_sampler={text_sampler!r}: 'torch' or 'device'")
-    dev_text = text_sampler == "device"
-    if dev_text:
-        why = None
-        if not text_temperature > 0:
-            why = "text_temperature > 0 (at 0 the text step is an arg-max: nothing is drawn)"
-        elif remasking != 'low_confidence':
-            why = "remasking == 'low_confidence'"
-        elif model.tp_size != 1 or model._comm_in_library:
-            why = "one rank (the vocabulary-parallel draw is a follow-up)"
-        elif input_ids.shape[0] >= 2 and os.environ.get("MMADA_MICROBATCH") == "1":
-            why = "a forward without micro-batched lanes (MMADA_MICROBATCH=1 splits the batch)"
-        elif sampler_seed is None:
-            why = "sampler_seed"
-        if why:
-            raise ValueError(f"text_sampler='device' needs {why}")
-    if image_sampler not in ("torch", "device"):
-        raise ValueError(f"image_sampler={image_sampler!r}: 'torch' or 'device'")
-    dev_img = image_sampler == "device"
-    if dev_img:
-        why = None
-        if not temperature > 0:
-            why = "temperature > 0 (at 0 the image step is an arg-max: nothing is drawn)"
-        elif model.tp_size != 1 or model._comm_in_library:
-            why = "one rank (tensor parallelism is out of scope)"
-        elif sampler_seed is None:
-            why = "sampler_seed"
-        if why:
-            raise ValueError(f"image_sampler='device' needs {why}")
+    dev_img, dev_text = check_samplers(model, image_sampler, text_sampler, sampler_seed, temperature=temperature,
+                                       text_temperature=text_temperature,
+                                       text_rank_note="the vocabulary-parallel draw is a follow-up")
+    if dev_text and remasking != 'low_confidence':
+        raise ValueError("text_sampler='device' needs remasking == 'low_confidence'")
+    if dev_text and input_ids.shape[0] >= 2 and os.environ.get("MMADA_MICROBATCH") == "1":
+        raise ValueError("text_sampler='device' needs a forward without micro-batched lanes (MMADA_MICROBATCH=1 splits the batch)")
     lib, h = model._lib, model._handle
     device = model.device
     rng = rng or TorchRng()
@@ -269,6 +246,7 @@ def _ti2ti_steps(
     vp_text = text_temperature == 0 and remasking == 'low_confidence' and model.vocab_parallel_head()
     text_logits = None if vp_text or dev_text else torch.empty((B * T, V), dtype=torch.bfloat16, device=device)
     draw_counter = torch.zeros(1, dtype=torch.int64, device=device) if dev_text else None
+    seed64 = seed_u64(sampler_seed) if dev_img or dev_text else None
     cond_vq = torch.empty((B * N, CBs), dtype=torch.bfloat16, device=device) if img_steps else None
     unc = torch.empty((2 * B, L), dtype=torch.long, device=device) if need_uncond else None
     unc_vq = torch.empty((2 * B * N, CBs), dtype=torch.bfloat16, device=device) if need_uncond and img_steps else None
@@ -280,14 +258,13 @@ def _ti2ti_steps(
     if temperature != 0 and img_steps and not dev_img:
         probs = torch.empty((B * N, CBs), dtype=torch.bfloat16, device=device)
     if dev_img:
-        img_counter = torch.full((1,), 1 << 62, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_sampled
+        img_counter = torch.full((1,), IMAGE_COUNTER0, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_sampled
         # the re-mask temperature per step: host double arithmetic as on the torch path, then the same cast to fp32
         temp_dev = torch.tensor([temperature * (1.0 - 1.0 * (step + 1) / text_steps) for step in range(text_steps)],
                                 dtype=torch.float32, device=device)
         temp_cur = torch.zeros(1, dtype=torch.float32, device=device)
         sampled_dev = torch.empty((B, N), dtype=torch.int32, device=device)
         p_sel_dev = torch.empty((B, N), dtype=torch.bfloat16, device=device)
-        seed64 = int(sampler_seed) & 0xFFFFFFFFFFFFFFFF
 
     masked_left = remaining_text.clone()
     # rows of the residual stream each forward is read at (host-side): the last block only computes those
@@ -309,8 +286,8 @@ def _ti2ti_steps(
                                                k_cur.data_ptr(), scratch.data_ptr(), st), "mmada_text_select_tp")
         elif need_text and dev_text:
             abi.check(lib.mmada_text_select_sampled(h, text_rows.data_ptr(), B, T, float(text_temperature),
-                                                    int(sampler_seed) & 0xFFFFFFFFFFFFFFFF, draw_counter.data_ptr(), ids.data_ptr(),
-                                                    L, text_start, k_cur.data_ptr(), scratch.data_ptr(), st),
+                                                    seed64, draw_counter.data_ptr(), ids.data_ptr(), L, text_start,
+                                                    k_cur.data_ptr(), scratch.data_ptr(), st),
                       "mmada_text_select_sampled")
         elif need_text:
             model.head_rows(text_rows, 0, V, out=text_logits)  # [B*T, V]
@@ -369,21 +346,26 @@ def _ti2ti_steps(
                                                  mlen_cur.data_ptr(), int(text_vocab_size), int(codebook_size),
                                                  abi.stream_ptr()), "mmada_image_commit_sampled")
 
-    if graph is None:
-        graph = os.environ.get("MMADA_GRAPH") == "1"
-    graph = (bool(graph) and (temperature == 0 or dev_img) and (text_temperature == 0 or dev_text)
-             and remasking == 'low_confidence' and model.graph_capturable())  # a replayed step would replay torch's draws
-    graphs, seen = {}, set()
-    ws_epoch = model._ws_epoch
-    side = torch.cuda.Stream(device=device) if graph else None
-    if graph:  # the legacy default stream cannot be captured: the loop runs on a side stream, ordered after the caller's
-        side.wait_stream(torch.cuda.current_stream(device))
-    try:
+    def launches(is_img, need_text, early_noise):
+        """Everything of a step that is a launch over the fixed buffers: what a captured step holds."""
+        text_part(is_img, need_text)
+        if is_img:
+            image_forwards()
+            if dev_img:
+                image_commit_sampled()
+            elif temperature == 0:
+                if not early_noise:  # the reference's draw order: text Gumbel noise first (:13-16, :30-33)
+                    noise_buf.copy_(rng.randn((B, N), torch.bfloat16, device, generator))
+                image_commit(argmax, pmax, 0.0)
+
+    # a replayed step would replay torch's draws
+    eligible = (temperature == 0 or dev_img) and (text_temperature == 0 or dev_text) and remasking == 'low_confidence'
+    with StepGraphs(model, graph, eligible) as sg:
         for step in range(text_steps):
             is_img = step in img_steps
             need_text = int(masked_left.sum()) > 0
             info = {"image_step": is_img, "sampled": None}
-            with torch.cuda.stream(side) if graph else contextlib.nullcontext():
+            with sg.stream():
                 k_cur.copy_(k_dev[step])
                 mlen_cur.copy_(mlen_dev[step:step + 1])
                 if dev_img:
@@ -395,43 +377,7 @@ def _ti2ti_steps(
                     # nothing else draws from torch in such a step (no Gumbel noise or a device-side one, no random re-mask
                     # ranks), so it can be drawn ahead of the step's launches
                     noise_buf.copy_(rng.randn((B, N), torch.bfloat16, device, generator))
-                key = (is_img, need_text)
-                if graph and graphs and model._ws_epoch != ws_epoch:
-                    # the workspace moved after all (a foreign forward in between): captured pointers are stale
-                    for g_old in graphs.values():
-                        lib.mmada_graph_destroy(g_old)
-                    graphs.clear()
-                    seen.clear()
-                ws_epoch = model._ws_epoch
-                if graph and key in graphs:
-                    abi.check(lib.mmada_graph_launch(graphs[key], abi.stream_ptr()), "mmada_graph_launch")
-                    model.graph_replays += 1
-                else:
-                    capture = graph and key in seen  # first step of a kind: eager (first calls set attributes / carve)
-                    if capture:
-                        abi.check(lib.mmada_graph_begin(abi.stream_ptr()), "mmada_graph_begin")
-                    try:
-                        text_part(is_img, need_text)
-                        if is_img:
-                            image_forwards()
-                            if dev_img:
-                                image_commit_sampled()
-                            elif temperature == 0:
-                                if not early_noise:  # the reference's draw order: text Gumbel noise first (:13-16, :30-33)
-                                    noise_buf.copy_(rng.randn((B, N), torch.bfloat16, device, generator))
-                                image_commit(argmax, pmax, 0.0)
-                    except Exception:
-                        if capture:
-                            lib.mmada_graph_abort(abi.stream_ptr())
-                        raise
-                    if capture:
-                        g = C.c_void_p()
-                        abi.check(lib.mmada_graph_end(abi.stream_ptr(), C.byref(g)), "mmada_graph_end")
-                        graphs[key] = g
-                        model.graph_nodes[key] = lib.mmada_graph_num_nodes(g)
-                        abi.check(lib.mmada_graph_launch(g, abi.stream_ptr()), "mmada_graph_launch")
-                        model.graph_replays += 1
-                    seen.add(key)
+                sg.step((is_img, need_text), lambda: launches(is_img, need_text, early_noise))
                 if need_text:
                     masked_left = masked_left - num_transfer[:, step]
                 if is_img:
@@ -447,14 +393,9 @@ def _ti2ti_steps(
                         noise_buf.copy_(rng.randn((B, N), torch.bfloat16, device, generator))  # reference :30-33
                         image_commit(sampled, p_sel, temperature * (1.0 - ratio))
                         info["sampled"] = sampled
-            if graph:
-                torch.cuda.current_stream(device).wait_stream(side)  # whoever consumes `ids` sees the finished step
+            sg.join()   # whoever consumes `ids` sees the finished step
             yield step, ids, info
-            if graph:
-                side.wait_stream(torch.cuda.current_stream(device))
-    finally:
-        for g in graphs.values():
-            lib.mmada_graph_destroy(g)
+            sg.fork()
     yield text_steps, ids, {"image_step": False, "sampled": None, "pos_list": pos_list}
 
 

@@ -17,8 +17,9 @@ import torch
 
 from .. import abi
 from ..model import LLaDAForMultiModalGeneration
-from .interleave_generator import TorchRng, _log, check_m_samplers, cosine_schedule
+from .interleave_generator import TorchRng, _log, cosine_schedule
 from .parallel_generator import check_tp_exchange, mask_len_schedule
+from .sampler_options import IMAGE_COUNTER0, check_samplers, seed_u64
 
 
 def _t2i_steps(
@@ -55,7 +56,7 @@ def _t2i_steps(
         raise TypeError("t2i_generate (MI355X) needs mmada_parallel_amd.LLaDAForMultiModalGeneration")
     if int(model.config.get("mask_token_id", 126336)) != mask_token_id:
         raise ValueError("mask_token_id differs from the model's")
-    dev_img, _ = check_m_samplers(model, image_sampler, sampler_seed=sampler_seed)
+    dev_img, _ = check_samplers(model, image_sampler, sampler_seed=sampler_seed)
     rng = rng or TorchRng()
     lib, h, device = model._lib, model._handle, model.device
     uni_prompting = kwargs.get("uni_prompting", None)
@@ -78,8 +79,8 @@ def _t2i_steps(
     probs = None if dev_img else torch.empty((B * N, CB), dtype=torch.bfloat16, device=device)
     sampled_ids = None
     if dev_img:
-        seed64 = int(sampler_seed) & 0xFFFFFFFFFFFFFFFF
-        img_counter = torch.full((1,), 1 << 62, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_m_sampled
+        seed64 = seed_u64(sampler_seed)
+        img_counter = torch.full((1,), IMAGE_COUNTER0, dtype=torch.int64, device=device)   # advanced by mmada_image_commit_m_sampled
         temps, t_run = [], temperature
         for step in range(timesteps):
             t_run = t_run * (1.0 - 1.0 * (step + 1) / timesteps)                    # :349 (cumulative), host double as below

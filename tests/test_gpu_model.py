@@ -891,3 +891,34 @@ def test_graph_with_a_batch_whose_unconditional_pair_outgrows_the_default_worksp
     captured, model = run(True)
     assert model.graph_replays > 0 and model._ws_epoch == 1, "one allocation, before the first capture"
     assert torch.equal(eager, captured)
+
+
+def test_a_stepwise_generator_closed_early_destroys_the_graphs_it_holds(tiny_model, monkeypatch):
+    """generate_ti2ti_stepwise with MMADA_GRAPH=1, abandoned by its consumer after the first capture: closing the generator destroys
+    every captured graph once (generators/step_graph.StepGraphs leaves its block), and the model is left as an eager run expects it."""
+    from mmada_parallel_amd import abi, generate_ti2ti, generate_ti2ti_stepwise
+
+    job = tiny_job()
+    args = (job["input_ids"].to(DEV), job["text_start"], job["text_end"], job["image_start"], job["seq_len"], job["newline_every"])
+    kw = dict(temperature=0.0, text_temperature=0.0, uncon_text=job["uncon_text"], uncon_image=job["uncon_image"])
+
+    def eager():
+        return generate_ti2ti(tiny_model, *args, return_state=True, graph=False, **kw, **SAMPLER_CASES["img4"])[2]
+
+    want = eager()
+    real, destroyed = abi.lib().mmada_graph_destroy, []
+    monkeypatch.setattr(abi.lib(), "mmada_graph_destroy", lambda g: destroyed.append(g.value) or real(g), raising=False)
+    monkeypatch.setenv("MMADA_GRAPH", "1")
+    tiny_model.graph_nodes = {}
+    steps = generate_ti2ti_stepwise(tiny_model, *args, text_steps=10, cfg_scale=0.0, cfg_img=4.0, **kw)
+    pulled = 0
+    for _ in steps:
+        pulled += 1
+        if tiny_model.graph_nodes:
+            break
+    assert tiny_model.graph_nodes and pulled < 10 and destroyed == [], "a graph is captured and held while the generator is suspended"
+    steps.close()
+    torch.cuda.synchronize()
+    print(f"closed after {pulled} of 10 steps: {len(tiny_model.graph_nodes)} graph(s) captured, {len(destroyed)} destroyed")
+    assert len(destroyed) == len(set(destroyed)) == len(tiny_model.graph_nodes), "each held graph is destroyed exactly once"
+    assert torch.equal(eager(), want), "an eager run after the abandoned one gives what it gave before"

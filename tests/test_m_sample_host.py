@@ -113,3 +113,80 @@ def test_generators_refuse_bad_sampler_arguments_on_a_stub_model():
                       (dict(image_sampler="device"), "image_sampler='device' needs sampler_seed")):
         with pytest.raises(ValueError, match=match):
             t2i_generate(stub, input_ids=ids[None], mask_token_id=int(stub.config.get("mask_token_id", 126336)), **kw)
+
+
+# Every refusal of the five generators' device samplers, word for word as each generator has always raised it (the one shared check,
+# generators/sampler_options.check_samplers, must keep the per-caller wordings): (keywords, tensor-parallel?, MMADA_MICROBATCH, message)
+VALUE = "{}='gpu': 'torch' or 'device'"
+NO_TEXT_DRAW = "text_sampler='device' needs {} > 0 (at 0 the text step is an arg-max: nothing is drawn)"
+NO_IMAGE_DRAW = "image_sampler='device' needs temperature > 0 (at 0 the image step is an arg-max: nothing is drawn)"
+ONE_RANK = "{}='device' needs one rank (tensor parallelism is out of scope)"
+LANES = "text_sampler='device' needs a forward without micro-batched lanes (MMADA_MICROBATCH=1 splits the batch)"
+SEEDLESS = "{}='device' needs sampler_seed"
+DEV_TEXT, DEV_IMG = dict(text_sampler="device", sampler_seed=1), dict(image_sampler="device", sampler_seed=1)
+REFUSALS = {
+    "generate_ti2ti": [
+        (dict(text_sampler="gpu", sampler_seed=1), False, None, VALUE.format("text_sampler")),
+        (dict(image_sampler="gpu", sampler_seed=1), False, None, VALUE.format("image_sampler")),
+        (dict(DEV_TEXT, text_temperature=0.0), False, None, NO_TEXT_DRAW.format("text_temperature")),
+        (dict(DEV_TEXT, remasking="random"), False, None, "text_sampler='device' needs remasking == 'low_confidence'"),
+        (DEV_TEXT, True, None, "text_sampler='device' needs one rank (the vocabulary-parallel draw is a follow-up)"),
+        (DEV_TEXT, False, "1", LANES),
+        (dict(text_sampler="device"), False, None, SEEDLESS.format("text_sampler")),
+        (dict(DEV_IMG, temperature=0.0), False, None, NO_IMAGE_DRAW),
+        (dict(DEV_IMG, temperature=-1.0), False, None, NO_IMAGE_DRAW),
+        (DEV_IMG, True, None, ONE_RANK.format("image_sampler")),
+        (dict(image_sampler="device"), False, None, SEEDLESS.format("image_sampler")),
+    ],
+    "interleave_generate": [
+        (dict(text_sampler="gpu", sampler_seed=1), False, None, VALUE.format("text_sampler")),
+        (dict(image_sampler="gpu", sampler_seed=1), False, None, VALUE.format("image_sampler")),
+        (dict(DEV_TEXT, text_temperature=0.0), False, None, NO_TEXT_DRAW.format("text_temperature")),
+        (dict(DEV_TEXT, text_temperature=0.7), True, None, ONE_RANK.format("text_sampler")),
+        (dict(text_sampler="device", text_temperature=0.7), False, None, SEEDLESS.format("text_sampler")),
+        (DEV_IMG, True, None, ONE_RANK.format("image_sampler")),
+        (dict(image_sampler="device"), False, None, SEEDLESS.format("image_sampler")),
+    ],
+    "t2i_generate": [
+        (dict(image_sampler="gpu", sampler_seed=1), False, None, VALUE.format("image_sampler")),
+        (DEV_IMG, True, None, ONE_RANK.format("image_sampler")),
+        (dict(image_sampler="device"), False, None, SEEDLESS.format("image_sampler")),
+    ],
+    "generate_image": [
+        (dict(image_sampler="gpu", sampler_seed=1), False, None, VALUE.format("image_sampler")),
+        (dict(DEV_IMG, temperature=0.0), False, None, NO_IMAGE_DRAW),
+        (DEV_IMG, True, None, ONE_RANK.format("image_sampler")),
+        (dict(image_sampler="device"), False, None, SEEDLESS.format("image_sampler")),
+    ],
+    "mmu_generate": [
+        (dict(text_sampler="gpu", sampler_seed=1, temperature=0.7), False, None, VALUE.format("text_sampler")),
+        (DEV_TEXT, False, None, NO_TEXT_DRAW.format("temperature")),
+        (dict(DEV_TEXT, temperature=0.7), True, None, ONE_RANK.format("text_sampler")),
+        (dict(text_sampler="device", temperature=0.7), False, None, SEEDLESS.format("text_sampler")),
+        (dict(DEV_TEXT, temperature=0.7), False, "1", LANES),
+    ],
+}
+
+
+@pytest.mark.parametrize("name", REFUSALS)
+def test_each_generator_refuses_in_its_own_words(name, monkeypatch):
+    from mmada_parallel_amd.generators.image_generation_generator import generate_image
+    from mmada_parallel_amd.generators.mmu_generator import mmu_generate
+    from mmada_parallel_amd.generators.parallel_generator import generate_ti2ti
+
+    stub = StubScore()
+    ids = torch.zeros((2, 4), dtype=torch.long)
+    call = {"generate_ti2ti": lambda **kw: generate_ti2ti(stub, ids, 0, 2, 2, 2, 2, **kw),
+            "interleave_generate": lambda **kw: interleave_generate(stub, ids[0], ids[0], **kw),
+            "t2i_generate": lambda **kw: t2i_generate(stub, input_ids=ids, mask_token_id=int(stub.config.get("mask_token_id", 126336)), **kw),
+            "generate_image": lambda **kw: generate_image(stub, ids[:1], **kw),
+            "mmu_generate": lambda **kw: mmu_generate(stub, ids, max_new_tokens=8, steps=4, block_length=4, **kw)}[name]
+    for kw, tensor_parallel, lanes, message in REFUSALS[name]:
+        for tp_size, in_library in ((2, False), (1, True)) if tensor_parallel else ((1, False),):
+            stub.tp_size, stub._comm_in_library = tp_size, in_library
+            with monkeypatch.context() as mp:
+                mp.delenv("MMADA_MICROBATCH", raising=False)
+                if lanes:
+                    mp.setenv("MMADA_MICROBATCH", lanes)
+                with pytest.raises(ValueError, match="^" + re.escape(message) + "$"):
+                    call(**kw)
