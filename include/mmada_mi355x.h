@@ -148,7 +148,12 @@ size_t mmada_score_buffer_bytes(const mmada_handle* h);
  * fold and expression), so logit_out - lse_out in fp32 is mmada_head_logprobs' logprob_out of that column.
  * Record buffer: the handle's (mmada_score_buffer_bytes), ceil(N / 256) * ceil8(R) * 48 + ceil8(R) * 4 bytes — 3/32 of the bf16
  * logits the call stands for; the call synchronises the host only when the buffer must grow, and a call that fits is capturable.
- * One rank only: a handle with a tensor-parallel exchange connected (also a one-rank group) or tp_size != 1 is an error. */
+ * Tensor parallelism: on a group of two or more ranks whose exchange runs in the library over the pull or the copy transport
+ * (mmada_comm_create + mmada_comm_connect_*) every rank makes the call: each multiplies its block of the launch's 256-column tiles,
+ * the tiles' 32-byte key records ride the score exchange of mmada_head_logprobs behind its 16-byte records, and every rank returns the
+ * same bits — those of a one-rank handle on the same normalised rows.  R <= the comm's max_rows; no host synchronisation, no
+ * allocation, capturable.  Anything else tensor-parallel is an error: tp_size != 1 without the library's exchange, a connected
+ * one-rank group, the RCCL transport, the diagnostic modes 3 and 5. */
 #define MMADA_TOPK_MAX 8
 int mmada_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, int k, int32_t* ids_out,
                     float* logit_out, float* lse_out, void* stream);
@@ -174,8 +179,13 @@ unsigned mmada_topk_order_key(unsigned bf16_bits);
  * range and row-window rules).
  * Record buffer: the handle's (mmada_score_buffer_bytes), ceil(N / 256) * ceil8(R) * 32 + ceil8(R) * 4 bytes — 1/16 of the bf16
  * logits the call stands for; the call synchronises the host only when the buffer must grow, and a call that fits is capturable.
- * One rank only: a handle with a tensor-parallel exchange connected (also a one-rank group) or tp_size != 1 is an error; the
- * vocabulary-parallel form is a follow-up. */
+ * Tensor parallelism: on a group of two or more ranks whose exchange runs in the library over the pull or the copy transport
+ * (mmada_comm_create + mmada_comm_connect_*) every rank makes the call: each multiplies its block of the launch's 256-column tiles,
+ * the tiles' 16-byte key triples ride the score exchange of mmada_head_logprobs behind its 16-byte records, and every rank returns the
+ * same bits — those of a one-rank handle on the same normalised rows.  R <= the comm's max_rows; no host synchronisation, no
+ * allocation, capturable.  Anything else tensor-parallel is an error: tp_size != 1 without the library's exchange, a connected
+ * one-rank group, the RCCL transport, the diagnostic modes 3 and 5.  The noise row r stays the row's index in the
+ * call, whatever round of the exchange carries it; every rank passes the same seed and a counter of its own, which advance alike. */
 int mmada_head_sample(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, float temperature, uint64_t seed,
                       uint64_t* counter, int32_t* ids_out, float* logprob_out, float* lse_out, int32_t* argmax_out, float* max_out,
                       void* stream);
@@ -293,7 +303,7 @@ int mmada_text_select_random(mmada_handle* h, const void* logits, const void* no
  *   x0 = mmada_head_sample over the whole vocabulary (row index inside the call: b*T + t); conf = masked ? logprob(x0) : -inf —
  *   ranking by the log-probability is ranking by the probability; the k[b] highest-confidence masked positions of row b get
  *   ids[b, text_start + t] = x0 (confidence descending, then position ascending).
- * The draws differ from torch's RNG stream by construction.  *counter advances by 1 per call.  One rank only, as mmada_head_sample.
+ * The draws differ from torch's RNG stream by construction.  *counter advances by 1 per call.  One rank, or a tensor-parallel group as mmada_head_sample takes it.
  * scratch: device, >= B*T*16 bytes. */
 int mmada_text_select_sampled(mmada_handle* h, const int32_t* rows, int B, int T, float temperature, uint64_t seed, uint64_t* counter,
                               int64_t* ids, int L, int text_start, const int32_t* k, void* scratch, void* stream);

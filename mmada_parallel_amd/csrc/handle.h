@@ -136,6 +136,12 @@ int tp_head_gather(mmada_handle* h, const int32_t* rows, int R, hipStream_t s); 
 // mmada_head_logprobs on a connected handle: the 256-column tiles split over the ranks, records exchanged, every rank joins
 int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
                      float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s);
+// mmada_head_topk / mmada_head_sample on a connected group of two or more ranks (pull or copy transport): the same exchange with
+// the tiles' key records behind the 16-byte records; every rank ends with the bits of a one-rank handle on the same rows
+int tp_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, int k, int32_t* ids, float* logits,
+                 float* lse, hipStream_t s);
+int tp_head_sample(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, float temperature, uint64_t seed,
+                   uint64_t* counter, int32_t* ids, float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s);
 // out[r] = src[b * Lp + l] for rows[r] = b * L + l: the plain row gather behind tp_head_gather, on any [B * Lp, d] buffer
 int tp_gather_rows(const bf16_t* src, const int32_t* rows, int R, int L, int Lp, int d, int nflat, bf16_t* out, hipStream_t s);
 

@@ -61,6 +61,11 @@ static int fused_head_on_one_rank(mmada_handle* h, const char* who, bool one_ran
     return launch(h->xg, h->lm_head + (size_t)col_begin * d, N, d);
 }
 
+// mmada_head_topk / mmada_head_sample take the vocabulary-parallel form (tp_heads.hip) on a group of two or more ranks whose
+// exchange runs in the library; that form refuses what it cannot serve (the RCCL transport, the diagnostic modes).  A handle
+// with tp_size >= 2 but no exchange in the library, and the connected ONE-rank group of the test switch, keep the refusals below.
+static bool vocabulary_parallel_group(const mmada_handle* h) { return h->cfg.tp_size >= 2 && tp_comm_connected(h); }
+
 extern "C" {
 
 int mmada_cache_head_rows(mmada_handle* h, int slot, const int32_t* rows, int R, int col_begin, int col_end,
@@ -127,6 +132,7 @@ int mmada_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, 
         return mm_fail("mmada_head_topk: k=%d exceeds the column range [%d, %d)", k, col_begin, col_end);
     if (fused_head_entry(h, "mmada_head_topk", !rows || !ids_out || !logit_out)) return 1;
     hipStream_t s = (hipStream_t)stream;
+    if (vocabulary_parallel_group(h)) return tp_head_topk(h, rows, R, col_begin, col_end, k, ids_out, logit_out, lse_out, s);
     return fused_head_on_one_rank(
         h, "mmada_head_topk", !runs_tensor_parallel(h) && !h->res.xn_is_final,
         "mmada_head_topk: top-k runs on one rank (a handle without a tensor-parallel exchange): the vocabulary-parallel "
@@ -145,6 +151,8 @@ int mmada_head_sample(mmada_handle* h, const int32_t* rows, int R, int col_begin
     if (!(temperature >= 0.f) || __builtin_isinf(temperature))
         return mm_fail("mmada_head_sample: temperature %g is not a finite value >= 0", (double)temperature);
     hipStream_t s = (hipStream_t)stream;
+    if (vocabulary_parallel_group(h))
+        return tp_head_sample(h, rows, R, col_begin, col_end, temperature, seed, counter, ids_out, logprob_out, lse_out, argmax_out, max_out, s);
     return fused_head_on_one_rank(
         h, "mmada_head_sample", !runs_tensor_parallel(h) && !h->res.xn_is_final,
         "mmada_head_sample: the draw runs on one rank (a handle without a tensor-parallel exchange): the "

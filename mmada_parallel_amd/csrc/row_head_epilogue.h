@@ -139,7 +139,7 @@ MM_DEVICE void rowtopk_merge(int lds, int rt, u32x4* dst) {
     dst[1] = u32x4{best[4], best[5], best[6], best[7]};
 }
 
-// ---- EPI_ROWSAMPLE, step 1: the wave column's best {key, column, logit} of row m: key = x + T * g of the lane's values, the lane's
+// ---- EPI_ROWSAMPLE, step 1: the wave column's best {key, column, logit} of noise row m: key = x + T * g of the lane's values, the lane's
 // best (the first column on equal keys), then the best of the lanes that share the row.  When a lane holds four consecutive columns
 // they cost one Philox evaluation (two when the launch's first column is no multiple of 4), otherwise every value costs one.  The
 // writer lane stores the triple at `at`.  val(ni, r): the lane's logits of this row; c0: the lane's first column inside the launch
@@ -298,7 +298,8 @@ MM_DEVICE void rowstat_epilogue(const GemmArgs& g, int m0, int n0, f32x4 (&acc)[
             rowtopk_rounds<TR>(key, writer, lds + RowTopkLds::at(wn, rt));
         }
         if constexpr (SAMPLE)
-            rowsample_wave_best<TR, FN>([&](int ni, int r) { return val(sl, ni, r); }, a, ctr, m, c0, g.N, writer, lds + RowStatLds::at(wn, rt));
+            // (the noise row: the row's index in the CALL — a.row0 is wave-uniform and zero outside a tensor-parallel round)
+            rowsample_wave_best<TR, FN>([&](int ni, int r) { return val(sl, ni, r); }, a, ctr, m + a.row0, c0, g.N, writer, lds + RowStatLds::at(wn, rt));
     }
     repack();
     __syncthreads();

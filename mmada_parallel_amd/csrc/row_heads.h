@@ -9,7 +9,7 @@
 //                 (N - 256 * nt < 8) hold 0, below every real key.
 //   EPI_ROWSAMPLE (Gumbel-max draw, mmada_head_sample)  the same record with the same bits (no row has a target), plus
 //                 extra[nt * ld + m] = {max key, its column in the whole vocabulary (int bits), the bf16 logit at that column as
-//                 fp32, 0} — key = x + T * g(seed, *counter, row m, column in the whole vocabulary) (sample_noise.h); highest key,
+//                 fp32, 0} — key = x + T * g(seed, *counter, row row0 + m, column in the whole vocabulary) (sample_noise.h); highest key,
 //                 then lowest column.  Columns beyond N carry the key -inf.
 // M may be `rows` rounded up to 8 (pad rows of A hold anything; their results are dropped).
 #pragma once
@@ -24,6 +24,7 @@ constexpr int TOPK_MAX = 8;        // = MMADA_TOPK_MAX (include/mmada_mi355x.h);
 // every GEMM kernel takes keeps its layout and no other kernel's compiled code changes.  THE aliasing, the only statement of it:
 //     part -> C        tx -> resid      target -> pos_map      rows -> rwin      ld -> rlp      col0 -> rbeg
 //     extra -> q       counter -> k     seed -> Hq (low half), Hkv (high half)   temperature -> Lq (its bits)
+//     row0 -> m_base
 // (ldc = ldr = 8: the 8-phase kernel's shape contract looks at them.)  A head that has no use for a field leaves it zero.
 struct RowHeadArgs {
     float4* part;              // [ceil(N / 256)][ld] records
@@ -34,12 +35,14 @@ struct RowHeadArgs {
     const uint64_t* counter;   // EPI_ROWSAMPLE: device [1], one scalar load per wave
     uint64_t seed;             // EPI_ROWSAMPLE
     float temperature;         // EPI_ROWSAMPLE: finite, T >= 0
+    int row0;                  // EPI_ROWSAMPLE: index in the CALL of the GEMM's row 0, for the noise only (a round of the tensor-parallel
+                               // head: tp_heads.hip); zero everywhere else
 };
 static inline __host__ __device__ RowHeadArgs row_head_args(const GemmArgs& g) {
     float t;
     __builtin_memcpy(&t, &g.Lq, 4);
     return RowHeadArgs{(float4*)g.C, (float*)g.resid, (const int64_t*)g.pos_map, g.rwin, g.rlp, g.rbeg, (void*)g.q, (const uint64_t*)g.k,
-                       (uint64_t)(uint32_t)g.Hq | ((uint64_t)(uint32_t)g.Hkv << 32), t};
+                       (uint64_t)(uint32_t)g.Hq | ((uint64_t)(uint32_t)g.Hkv << 32), t, g.m_base};
 }
 static inline void set_row_head_args(GemmArgs& g, const RowHeadArgs& a) {
     g.C = (bf16_t*)a.part; g.resid = (const bf16_t*)a.tx; g.pos_map = (const int32_t*)a.target;
@@ -49,6 +52,7 @@ static inline void set_row_head_args(GemmArgs& g, const RowHeadArgs& a) {
     g.k = (bf16_t*)a.counter;
     g.Hq = (int)(uint32_t)a.seed; g.Hkv = (int)(uint32_t)(a.seed >> 32);
     __builtin_memcpy(&g.Lq, &a.temperature, 4);
+    g.m_base = a.row0;
 }
 // What launch_gemm refuses: the message, or null when the block is complete for `head` (M: rows of the GEMM)
 static inline const char* row_head_args_fault(int head, const RowHeadArgs& a, int M) {
@@ -98,6 +102,24 @@ static inline __host__ __device__ float topk_key_logit(uint32_t key) {   // inve
     float x;
     __builtin_memcpy(&x, &u, 4);
     return x;
+}
+// A candidate of the top-k joins (row_heads.hip, tp_heads.hip): {order value of the logit, ~column inside the launch} as one 64-bit
+// number — logit descending, then tile ascending, then column ascending is ONE unsigned compare, and candidates of a row are
+// distinct.  0: no candidate.
+MM_DEVICE unsigned long long topk_cand(uint32_t key, int tile) {
+    if (key == 0u) return 0ull;
+    const uint32_t col = (uint32_t)tile * (uint32_t)ROW_HEAD_BN + (255u - (key & 255u));
+    return ((unsigned long long)(key >> 16) << 32) | (unsigned long long)(~col);
+}
+// best[] stays sorted in descending order; c replaces the last entry and moves up to its place
+MM_DEVICE void topk_insert(unsigned long long (&best)[TOPK_MAX], unsigned long long c) {
+    best[TOPK_MAX - 1] = c;
+#pragma unroll
+    for (int i = TOPK_MAX - 1; i > 0; --i) {
+        const unsigned long long lo = best[i], hi = best[i - 1];
+        best[i - 1] = lo > hi ? lo : hi;
+        best[i] = lo > hi ? hi : lo;
+    }
 }
 
 // ---- the order of the sampling head's triples {key, column, logit}: highest key, then lowest column

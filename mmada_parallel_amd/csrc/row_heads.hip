@@ -52,24 +52,7 @@ int launch_head_rowstat(const bf16_t* A, const bf16_t* W, int R, int N, int K, i
 }
 
 // ---- the top-k head: the GEMM also leaves every tile's eight best keys --------------------------------------------------------
-// A candidate of the join: {order value of the logit, ~column inside the launch} as one 64-bit number — logit descending, then
-// tile ascending, then column ascending is ONE unsigned compare, and candidates of a row are distinct.  0: no candidate.
-MM_DEVICE unsigned long long topk_cand(uint32_t key, int tile) {
-    if (key == 0u) return 0ull;
-    const uint32_t col = (uint32_t)tile * (uint32_t)ROW_HEAD_BN + (255u - (key & 255u));
-    return ((unsigned long long)(key >> 16) << 32) | (unsigned long long)(~col);
-}
-// best[] stays sorted in descending order; c replaces the last entry and moves up to its place
-MM_DEVICE void topk_insert(unsigned long long (&best)[TOPK_MAX], unsigned long long c) {
-    best[TOPK_MAX - 1] = c;
-#pragma unroll
-    for (int i = TOPK_MAX - 1; i > 0; --i) {
-        const unsigned long long lo = best[i], hi = best[i - 1];
-        best[i - 1] = lo > hi ? lo : hi;
-        best[i] = lo > hi ? hi : lo;
-    }
-}
-
+// (topk_cand / topk_insert, the candidates' order: row_heads.h, shared with the tensor-parallel join)
 // Thread (row, group j) walks the key records of tiles j, j + 16, ... and keeps the best eight candidates sorted in registers (a
 // record is sorted: its entries are taken until one does not beat the thread's eighth — most tiles end at their first); thread
 // (row, 0) merges the 16 lists of the row through LDS the same way and writes the first k.  The candidates are totally ordered, so

@@ -45,19 +45,24 @@ struct RcclApi {
 
 // The published record allocation (stats_pub; one hipIpc handle covers it all): [STAT_ROWS] text records, then at text_bytes
 // the scoring head's two record buffers of buf_bytes each, used alternately.  One buffer = `round` target logits (fp32),
-// then at rec_off [tiles][ld] 16-byte tile records of this rank's tiles (ld = the round's rows, rounded up to 8).
+// then at rec_off [tiles][ld] 16-byte tile records of this rank's tiles (ld = the round's rows, rounded up to 8), and right
+// behind the records of the nt tiles the rank owns in THIS call — at score_extra_off(rec_off, nt, ld) — the head's extra
+// records, [nt][ld] again: 32 bytes (top-k: the tile's eight keys) or 16 bytes (sampling: the tile's best triple), none for
+// scoring.  What a peer needs of a round is therefore one contiguous range from the buffer's start.
+constexpr uint32_t SCORE_EXTRA_MAX = 32;  // the larger extra record (row_heads.h: TOPK_MAX keys of 4 bytes)
 struct ScoreLayout {
     int round;  // rows per round: min(SCORE_ROUND, ceil8(max_rows))
     int tiles;  // 256-column tiles a rank can own: ceil(ceil(vocab / 256) / size)
     size_t text_bytes, buf_bytes, total;
     uint32_t rec_off;
 };
+inline uint32_t score_extra_off(uint32_t rec_off, int nt, int ld) { return rec_off + (uint32_t)nt * (uint32_t)ld * 16u; }
 inline ScoreLayout score_layout(int max_rows, int vocab, int size) {
     ScoreLayout l;
     l.round = min(SCORE_ROUND, (max_rows + 7) / 8 * 8);
     l.tiles = ((vocab + SCORE_BN - 1) / SCORE_BN + size - 1) / size;
     l.rec_off = (uint32_t)l.round * 4u;
-    l.buf_bytes = align_up((size_t)l.rec_off + (size_t)l.tiles * l.round * 16, 256);
+    l.buf_bytes = align_up((size_t)l.rec_off + (size_t)l.tiles * l.round * (16 + SCORE_EXTRA_MAX), 256);
     l.text_bytes = (size_t)STAT_ROWS * sizeof(TextStat);
     l.total = l.text_bytes + 2 * l.buf_bytes;
     return l;

@@ -1,5 +1,6 @@
 // tp_heads.hip — the LM head under tensor parallelism, on the transports of tp_comm.hip: the row gather in front of every head,
-// the vocabulary-parallel text head (mmada_text_select_tp) and the vocabulary-parallel scoring head (tp_head_logprobs).
+// the vocabulary-parallel text head (mmada_text_select_tp) and the vocabulary-parallel row heads: scoring, top-k and the
+// Gumbel-max draw (tp_head_logprobs, tp_head_topk, tp_head_sample — one round loop, three joins).
 #include "row_heads.h"
 #include "tp_comm.h"
 
@@ -61,42 +62,66 @@ __global__ __launch_bounds__(256) void tp_score_reset_kernel(float* tx, int n) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-struct ScoreJoinArgs {
+// Where a join finds the records of a round: what the round loop (tp_head_rounds) hands every head's join
+struct JoinSrc {
     const char* src[TP_MAX];  // rank j's record buffer of this round where THIS rank reads it: its own memory, a peer's mapped
                               // buffer (pull) or the gathered / staged copy (RCCL, copy)
     int sys;                  // pull: src[j != rank] is remote, read with system-scope loads
     int size, rank;
     int q;                    // tiles per rank: tile t is record (t - owner * q) of rank owner = t / q
     uint32_t rec_off;         // byte offset of the records behind the target logits
-    int ld, ntn, R, col_begin, col_end;
+    int ld, ntn, R;
+};
+struct ScoreJoinArgs : JoinSrc {
+    int col_begin, col_end;
     const int64_t* targets;
     float *logprob, *lse;
     int32_t* argmax;
     float* vmax;
 };
+// The top-k and the sampling join: extra record of tile t at x_off(owner) + (t - owner * q) * ld + row, in units of the record
+struct KeyJoinArgs : JoinSrc {
+    int col0, k;              // top-k: first column of the launch, places to write
+    int32_t* ids;             // top-k [R, k], sample [R]
+    float *out, *lse;         // top-k: logits [R, k]; sample: logprob [R]
+    int32_t* argmax;          // sample only (or null), like vmax
+    float* vmax;
+    float* spare;             // top-k: [ld] private floats (the join's unused log-probabilities)
+    uint64_t* counter;        // sample, last round of a call: this rank's counter, + 1; else null
+};
+
+// 16 bytes at byte offset `off` of the buffer of rank `owner` (per lane; src[o] is a kernel argument in SGPRs).  The lanes of a
+// wave hold neighbouring tiles, which may belong to two owners: one pass per rank (unrolled) keeps the base pointer
+// wave-uniform, as load_sys16's descriptor needs it
+MM_DEVICE u32x4 join_load16(const JoinSrc& a, int owner, uint32_t off) {
+    u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int o = 0; o < TP_MAX; ++o) {
+        if (o != owner) continue;
+        if (a.sys && o != a.rank) v = load_sys16(a.src[o], off);
+        else v = *(const u32x4*)(a.src[o] + off);
+    }
+    return v;
+}
+// tile t's 16-byte record of row r, and the byte offset of its extra record of `bytes` bytes (behind the owner's records)
+MM_DEVICE float4 join_record(const JoinSrc& a, int t, int r) {
+    const int owner = t / a.q;
+    const u32x4 v = join_load16(a, owner, a.rec_off + ((uint32_t)(t - owner * a.q) * (uint32_t)a.ld + (uint32_t)r) * 16u);
+    return float4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
+}
+MM_DEVICE uint32_t join_extra_off(const JoinSrc& a, int t, int r, uint32_t bytes) {
+    const int owner = t / a.q, nt = min(a.ntn, (owner + 1) * a.q) - owner * a.q;   // tiles the owner has in this call (t is one)
+    return a.rec_off + (uint32_t)nt * (uint32_t)a.ld * 16u + ((uint32_t)(t - owner * a.q) * (uint32_t)a.ld + (uint32_t)r) * bytes;
+}
 
 // The join of rowstat_combine_kernel (row_heads.hip) with tile t's record taken from the rank that owns t: the same fold
 // (row_heads.h: rowstat_fold), so every rank — and a one-rank handle — ends with the same bits.  Every rank joins every row.
 __global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_score_join_kernel(ScoreJoinArgs a) {
     if (a.sys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // see tp_reduce_norm_kernel
     const int row = blockIdx.x * RS_ROWS + threadIdx.x % RS_ROWS;
-    auto fetch = [&](int t, int r) -> float4 {
-        const int owner = t / a.q;
-        const uint32_t off = a.rec_off + ((uint32_t)(t - owner * a.q) * (uint32_t)a.ld + (uint32_t)r) * 16u;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        // the lanes of a wave hold neighbouring tiles, which may belong to two owners: one pass per rank (unrolled: src[o] is a
-        // kernel argument in SGPRs) keeps the base pointer wave-uniform, as load_sys16's descriptor needs it
-#pragma unroll
-        for (int o = 0; o < TP_MAX; ++o) {
-            if (o != owner) continue;
-            if (a.sys && o != a.rank) v = load_sys16(a.src[o], off);
-            else v = *(const u32x4*)(a.src[o] + off);
-        }
-        return float4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
-    };
     float m, sum;
     int arg;
-    if (!rowstat_fold(fetch, row, a.R, a.ntn, m, sum, arg)) return;
+    if (!rowstat_fold([&](int t, int r) { return join_record(a, t, r); }, row, a.R, a.ntn, m, sum, arg)) return;
     const long long t = a.targets[row];
     float tx = -__builtin_inff();
     if (t >= a.col_begin && t < a.col_end) {  // the target logit lives with the rank that owns the target's tile
@@ -109,6 +134,79 @@ __global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_score_join_kernel(Scor
         }
     }
     rowstat_finish(row, m, sum, arg, t, tx, a.logprob, a.lse, a.argmax, a.vmax);
+}
+
+// The join of rowtopk_combine_kernel (row_heads.hip) with tile t's key record taken from the rank that owns t: the candidates
+// (row_heads.h: topk_cand) are totally ordered, so neither the walk's order nor the owner shows in the result.
+__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_topk_join_kernel(KeyJoinArgs a) {
+    __shared__ unsigned long long sk[RS_GROUPS][TOPK_MAX][RS_ROWS];
+    if (a.sys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // see tp_reduce_norm_kernel
+    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
+    const int row = blockIdx.x * RS_ROWS + rl;
+    unsigned long long best[TOPK_MAX];
+#pragma unroll
+    for (int e = 0; e < TOPK_MAX; ++e) best[e] = 0ull;
+    if (row < a.R)
+        for (int t = j; t < a.ntn; t += RS_GROUPS) {
+            const uint32_t off = join_extra_off(a, t, row, TOPK_MAX * 4u);
+            const u32x4 lo = join_load16(a, t / a.q, off), hi = join_load16(a, t / a.q, off + 16u);
+            const uint32_t key[TOPK_MAX] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+            for (int e = 0; e < TOPK_MAX; ++e) {
+                const unsigned long long c = topk_cand(key[e], t);
+                if (c <= best[TOPK_MAX - 1]) break;
+                topk_insert(best, c);
+            }
+        }
+#pragma unroll
+    for (int e = 0; e < TOPK_MAX; ++e) sk[j][e][rl] = best[e];
+    float m, sum;
+    int arg;
+    // (its barrier also orders the candidate lists above)
+    if (!rowstat_fold([&](int t, int r) { return join_record(a, t, r); }, row, a.R, a.ntn, m, sum, arg)) return;
+    for (int q = 1; q < RS_GROUPS; ++q)
+#pragma unroll
+        for (int e = 0; e < TOPK_MAX; ++e) {
+            const unsigned long long c = sk[q][e][rl];
+            if (c <= best[TOPK_MAX - 1]) break;
+            topk_insert(best, c);
+        }
+#pragma unroll
+    for (int e = 0; e < TOPK_MAX; ++e)
+        if (e < a.k) {
+            a.ids[(size_t)row * a.k + e] = a.col0 + (int)~(uint32_t)best[e];
+            a.out[(size_t)row * a.k + e] = topk_key_logit((uint32_t)(best[e] >> 32) << 16);
+        }
+    rowstat_finish(row, m, sum, arg, -1, 0.f, a.spare, a.lse, nullptr, nullptr);
+}
+
+// The join of rowsample_combine_kernel (row_heads.hip) with tile t's triple taken from the rank that owns t: rowsample_take is a
+// total order (key, then column).  With a.counter (the last round of a call) this is the call's last kernel: every GEMM of this
+// rank has read *counter.
+__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_sample_join_kernel(KeyJoinArgs a) {
+    __shared__ float sk[RS_GROUPS][RS_ROWS], sx[RS_GROUPS][RS_ROWS];
+    __shared__ int sc[RS_GROUPS][RS_ROWS];
+    if (a.sys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // see tp_reduce_norm_kernel
+    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
+    const int row = blockIdx.x * RS_ROWS + rl;
+    float bk = -__builtin_inff(), bx = -__builtin_inff();
+    int bc = 0x7fffffff;
+    if (row < a.R)
+        for (int t = j; t < a.ntn; t += RS_GROUPS) {
+            const u32x4 p = join_load16(a, t / a.q, join_extra_off(a, t, row, 16u));
+            rowsample_take(bk, bc, bx, __uint_as_float(p[0]), (int)p[1], __uint_as_float(p[2]));
+        }
+    sk[j][rl] = bk; sc[j][rl] = bc; sx[j][rl] = bx;
+    float m, sum;
+    int arg;
+    // (its barrier also orders the key triples above)
+    const bool mine = rowstat_fold([&](int t, int r) { return join_record(a, t, r); }, row, a.R, a.ntn, m, sum, arg);
+    if (mine) {
+        for (int q = 1; q < RS_GROUPS; ++q) rowsample_take(bk, bc, bx, sk[q][rl], sc[q][rl], sx[q][rl]);
+        a.ids[row] = bc;
+        rowstat_finish(row, m, sum, arg, bc, bx, a.out, a.lse, a.argmax, a.vmax);
+    }
+    if (a.counter && blockIdx.x == 0 && threadIdx.x == 0) *a.counter += 1;
 }
 
 }  // namespace
@@ -176,10 +274,14 @@ extern "C" int mmada_text_select_tp(mmada_handle* h, const int32_t* rows, int B,
     return launch_text_commit(scratch, B, T, ids, L, text_start, k, s);
 }
 
-// Vocabulary-parallel scoring head (mmada_head_logprobs on a connected handle).  The launch's 256-column tiles are split over
-// the ranks in contiguous blocks (tp.py: score_tile_slice); each rank runs the one-rank EPI_ROWSTAT launch on its own tiles —
-// the same columns, col0-based arg-max indices and partial last tile, hence the same records — into a published buffer, the
-// ranks hand off, and every rank joins every row with the fold of the one-rank head.  Rows go in rounds of c->score.round.
+// Vocabulary-parallel row heads (mmada_head_logprobs on a connected handle; mmada_head_topk and mmada_head_sample on a group of
+// two or more ranks over a mapped transport): ONE round loop, tp_head_rounds, parameterised by the head.  The launch's
+// 256-column tiles are split over the ranks in contiguous blocks (tp.py: score_tile_slice); each rank runs the one-rank launch
+// of the head's epilogue on its own tiles — the same columns, col0-based indices and partial last tile, hence the same records
+// — into a published buffer, the ranks hand off, and every rank joins every row with the fold of the one-rank head (and, for
+// top-k and the draw, the totally ordered candidates of the one-rank join).  Rows go in rounds of c->score.round; the draw's
+// noise row is the row's index in the CALL (RowHeadArgs::row0 = the round's first row).  The three heads share the two
+// published buffers and the flip, so their calls may follow each other in any order.
 //
 // Buffer reuse (write after read).  A rank writes round i's records while a slower peer may still be joining an earlier
 // round, in this call or in the previous one (two calls with no forward between them are legal).  The two published buffers
@@ -192,24 +294,33 @@ extern "C" int mmada_text_select_tp(mmada_handle* h, const int32_t* rows, int B,
 // eager calls and replays interleave freely), so a captured call brackets itself with a hand-off of its own at both ends:
 // behind the first every earlier join has retired, and nothing later writes before the last.  The RCCL transport needs neither
 // argument: an all-gather completes on a rank only when its send buffer may be reused.
-int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
-                     float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s) {
+//
+// head: the epilogue; who: the entry point's name in messages.  fill(ra, r0): the head's own fields of a round's RowHeadArgs
+// (target / counter / seed / temperature / row0) for the round that starts at row r0 — part, tx, extra, rows, ld, col0 are set
+// here.  join(src, r0, rr, last): launches the head's join of the round's rr rows (last: the call's last round).
+template <class Fill, class Join>
+static int tp_head_rounds(mmada_handle* h, const char* who, int head, const int32_t* rows, int R, int col_begin, int col_end,
+                          hipStream_t s, Fill fill, Join join) {
     TpComm* c = h->tp;
-    if (!transport_connected(c)) return mm_fail("mmada_head_logprobs: no tensor-parallel transport connected");
-    if (!h->res.xn_is_final || !resident(h)) return mm_fail("mmada_head_logprobs: no tensor-parallel forward resident");
+    if (!transport_connected(c)) return mm_fail("%s: no tensor-parallel transport connected", who);
+    if (!h->res.xn_is_final || !resident(h)) return mm_fail("%s: no tensor-parallel forward resident", who);
+    const uint32_t xrec = head == EPI_ROWTOPK ? TOPK_MAX * 4u : head == EPI_ROWSAMPLE ? 16u : 0u;   // bytes of the extra record
+    static_assert(TOPK_MAX * 4u <= SCORE_EXTRA_MAX, "the published buffers hold the larger extra record");
+    const bool mapped = peers_mapped(c);
+    if (xrec && !mapped)
+        return mm_fail("%s: over the RCCL transport the vocabulary-parallel head is not built (nothing on one device can exercise "
+                       "it: RCCL refuses two ranks per device); connect the pull or the copy transport", who);
     if (R <= 0) return 0;
     if (R > c->max_rows)
-        return mm_fail("mmada_head_logprobs: %d rows exceed the %d rows this handle's comm was created for (mmada_comm_create max_rows)",
-                       R, c->max_rows);
-    if (check_head_range(h, "mmada_head_logprobs", R, h->res.B * h->res.L, col_begin, col_end)) return 1;
+        return mm_fail("%s: %d rows exceed the %d rows this handle's comm was created for (mmada_comm_create max_rows)", who, R, c->max_rows);
+    if (check_head_range(h, who, R, h->res.B * h->res.L, col_begin, col_end)) return 1;
     const int d = h->cfg.d_model, tp = c->size;
     const ScoreLayout& lay = c->score;
     const int ntn = (col_end - col_begin + SCORE_BN - 1) / SCORE_BN, q = (ntn + tp - 1) / tp;
-    if (q > lay.tiles) return mm_fail("mmada_head_logprobs: %d tiles per rank exceed the record buffers (%d)", q, lay.tiles);
+    if (q > lay.tiles) return mm_fail("%s: %d tiles per rank exceed the record buffers (%d)", who, q, lay.tiles);
     auto tiles_of = [&](int j) { return min(ntn, (j + 1) * q) - min(ntn, j * q); };
     const int t0 = min(ntn, c->rank * q), nt_own = tiles_of(c->rank);
     const int c0 = col_begin + t0 * SCORE_BN, n_own = nt_own > 0 ? min(col_end, c0 + nt_own * SCORE_BN) - c0 : 0;
-    const bool mapped = peers_mapped(c);
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
     const bool bracket = mapped && cs != hipStreamCaptureStatusNone;
@@ -219,32 +330,33 @@ int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin,
         const int rr = min(lay.round, R - r0), rp = (rr + 7) / 8 * 8;
         char* buf = c->score_pub[c->score_flip];
         float* tx = (float*)buf;
-        hipLaunchKernelGGL(tp_score_reset_kernel, dim3((rp + 255) / 256), dim3(256), 0, s, tx, rp);
-        MM_CHECK_HIP(hipGetLastError());
+        if (head == EPI_ROWSTAT) {   // (the other heads have no targets: nothing reads tx)
+            hipLaunchKernelGGL(tp_score_reset_kernel, dim3((rp + 255) / 256), dim3(256), 0, s, tx, rp);
+            MM_CHECK_HIP(hipGetLastError());
+        }
         if (n_own > 0) {
             GemmArgs g = gemm_bt_args(h->xg + (size_t)r0 * d, h->lm_head + (size_t)c0 * d, nullptr, rp, n_own, d, 8);
             RowHeadArgs ra{};
-            ra.part = (float4*)(buf + lay.rec_off); ra.tx = tx; ra.target = targets + r0;
+            fill(ra, r0);
+            ra.part = (float4*)(buf + lay.rec_off); ra.tx = tx;
+            ra.extra = xrec ? buf + score_extra_off(lay.rec_off, nt_own, rp) : nullptr;
             ra.rows = rr; ra.ld = rp; ra.col0 = c0;
             set_row_head_args(g, ra);
             g.publish = mapped;
-            if (launch_gemm(EPI_ROWSTAT, g, s)) return 1;
+            if (launch_gemm(head, g, s)) return 1;
         }
-        ScoreJoinArgs a{};
+        JoinSrc a{};
         a.sys = c->mode == TP_PULL; a.size = tp; a.rank = c->rank; a.q = q; a.rec_off = lay.rec_off; a.ld = rp; a.ntn = ntn; a.R = rr;
-        a.col_begin = col_begin; a.col_end = col_end; a.targets = targets + r0;
-        a.logprob = logprob + r0; a.lse = lse ? lse + r0 : nullptr; a.argmax = argmax ? argmax + r0 : nullptr;
-        a.vmax = vmax ? vmax + r0 : nullptr;
         if (mapped) {
             if (signal_wait(c, s)) return 1;  // every rank's records of this round are complete
             for (int j = 0; j < tp; ++j) {
                 const char* peer = (const char*)c->peers.stats[j] + lay.text_bytes + (size_t)c->score_flip * lay.buf_bytes;
                 if (j == c->rank) a.src[j] = buf;
                 else if (c->mode == TP_PULL) a.src[j] = peer;
-                else {  // copy engines: the peer's target logits and records of ITS tiles -> local staging
+                else {  // copy engines: the peer's target logits, records and extra records of ITS tiles -> local staging
                     char* dst = c->score_all + (size_t)j * lay.buf_bytes;
                     if (tiles_of(j) > 0)
-                        MM_CHECK_HIP(hipMemcpyAsync(dst, peer, (size_t)lay.rec_off + (size_t)tiles_of(j) * rp * 16, hipMemcpyDefault, s));
+                        MM_CHECK_HIP(hipMemcpyAsync(dst, peer, (size_t)lay.rec_off + (size_t)tiles_of(j) * rp * (16 + xrec), hipMemcpyDefault, s));
                     a.src[j] = dst;
                 }
             }
@@ -254,10 +366,55 @@ int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin,
             if (r != ncclSuccess) return nccl_fail(c, "ncclAllGather", r);
             for (int j = 0; j < tp; ++j) a.src[j] = j == c->rank ? buf : c->score_all + (size_t)j * cnt;
         }
-        hipLaunchKernelGGL(tp_score_join_kernel, dim3((rr + RS_ROWS - 1) / RS_ROWS), dim3(RS_ROWS * RS_GROUPS), 0, s, a);
+        join(a, r0, rr, r0 + lay.round >= R);
         MM_CHECK_HIP(hipGetLastError());
         c->score_flip ^= 1;
     }
     if (bracket && signal_wait(c, s)) return 1;
     return 0;
+}
+static dim3 join_grid(int rr) { return dim3((rr + RS_ROWS - 1) / RS_ROWS); }
+
+int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
+                     float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s) {
+    return tp_head_rounds(
+        h, "mmada_head_logprobs", EPI_ROWSTAT, rows, R, col_begin, col_end, s, [&](RowHeadArgs& ra, int r0) { ra.target = targets + r0; },
+        [&](const JoinSrc& src, int r0, int rr, bool) {
+            ScoreJoinArgs a{};
+            (JoinSrc&)a = src;
+            a.col_begin = col_begin; a.col_end = col_end; a.targets = targets + r0;
+            a.logprob = logprob + r0; a.lse = lse ? lse + r0 : nullptr; a.argmax = argmax ? argmax + r0 : nullptr;
+            a.vmax = vmax ? vmax + r0 : nullptr;
+            hipLaunchKernelGGL(tp_score_join_kernel, join_grid(rr), dim3(RS_ROWS * RS_GROUPS), 0, s, a);
+        });
+}
+
+int tp_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, int k, int32_t* ids, float* logits,
+                 float* lse, hipStream_t s) {
+    return tp_head_rounds(
+        h, "mmada_head_topk", EPI_ROWTOPK, rows, R, col_begin, col_end, s, [&](RowHeadArgs&, int) {},
+        [&](const JoinSrc& src, int r0, int rr, bool) {
+            KeyJoinArgs a{};
+            (JoinSrc&)a = src;
+            a.col0 = col_begin; a.k = k;
+            a.ids = ids + (size_t)r0 * k; a.out = logits + (size_t)r0 * k; a.lse = lse ? lse + r0 : nullptr;
+            // the join's unused log-probabilities go to this rank's own slot of the private staging, which no transport uses
+            a.spare = (float*)(h->tp->score_all + (size_t)h->tp->rank * h->tp->score.buf_bytes);
+            hipLaunchKernelGGL(tp_topk_join_kernel, join_grid(rr), dim3(RS_ROWS * RS_GROUPS), 0, s, a);
+        });
+}
+
+int tp_head_sample(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, float temperature, uint64_t seed,
+                   uint64_t* counter, int32_t* ids, float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s) {
+    return tp_head_rounds(
+        h, "mmada_head_sample", EPI_ROWSAMPLE, rows, R, col_begin, col_end, s,
+        [&](RowHeadArgs& ra, int r0) { ra.counter = counter; ra.seed = seed; ra.temperature = temperature; ra.row0 = r0; },
+        [&](const JoinSrc& src, int r0, int rr, bool last) {
+            KeyJoinArgs a{};
+            (JoinSrc&)a = src;
+            a.ids = ids + r0; a.out = logprob + r0; a.lse = lse ? lse + r0 : nullptr;
+            a.argmax = argmax ? argmax + r0 : nullptr; a.vmax = vmax ? vmax + r0 : nullptr;
+            a.counter = last ? counter : nullptr;   // once per call, behind every GEMM of this rank that reads it
+            hipLaunchKernelGGL(tp_sample_join_kernel, join_grid(rr), dim3(RS_ROWS * RS_GROUPS), 0, s, a);
+        });
 }

@@ -154,7 +154,7 @@ def generate_image(
     `debug` only prints one line per step (the reference's per-step dumps are host-side diagnostics).
 
     `image_sampler="device"` (opt-in; the default "torch" is the reference's path, draw for draw; needs temperature > 0, `sampler_seed`
-    and one rank, anything else raises ValueError): a step is mmada_head_rows on ALL image slots, mmada_image_sample_g (col0 =
+    and one rank or a tensor-parallel group on the library's pull / copy transport, anything else raises ValueError): a step is mmada_head_rows on ALL image slots, mmada_image_sample_g (col0 =
     text_vocab_size) and mmada_image_commit_g_sampled.  Neither the [n, codebook] probabilities nor any torch random tensor exists
     and `rng` / `generator` are never called.  The token is a Gumbel-max draw from soft-max(l / temperature) evaluated in fp32 on the
     bf16 CFG-combined logits l — the reference's bf16 l / temperature + gumbel has the same arg-max in exact arithmetic — and the

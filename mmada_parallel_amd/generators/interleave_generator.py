@@ -103,7 +103,7 @@ def interleave_generate(
     multinomial samples the bf16-rounded probabilities — and the re-mask noise is a counter-based Gumbel value per image position,
     both keyed by `sampler_seed` (required) and a counter that starts at 1 << 62 per call and advances by 1 per image step.  The
     re-mask temperature image_temperature * (1 - (i + 1) / text_steps) is host double arithmetic as on the torch path, cast to fp32.
-    One rank only.
+    One rank, or a tensor-parallel group on the library's pull / copy transport (every rank runs the same call with the same seed).
 
     `text_sampler="device"` (opt-in; needs text_temperature > 0): the text draw is mmada_text_draw_cfg on the cond / uncond halves of
     the text logits — a Gumbel-max draw in fp32 from soft-max(combined / text_temperature) instead of the reference's float64

@@ -8,7 +8,7 @@ confidence, and the `k` most confident masked positions of the CURRENT block are
 later blocks are excluded (:677), earlier blocks and the prompt are no longer masked.  The LM head runs only on the
 current block's rows.
 
-Opt-in, `text_sampler="device"` with `sampler_seed` (temperature > 0, one rank): the draw runs inside the kernels — the LM head's
+Opt-in, `text_sampler="device"` with `sampler_seed` (temperature > 0; one rank or a tensor-parallel group on the library's pull / copy transport): the draw runs inside the kernels — the LM head's
 GEMM (mmada_text_select_sampled) without guidance, mmada_text_draw_cfg on the block's logits with it — on the counter-based
 generator of csrc/sample_noise.h; see mmu_generate.
 
@@ -40,7 +40,7 @@ def mmu_generate(model, idx=None, input_embeddings=None, max_new_tokens=128, ste
     mmu_generate; mmu_generate_fast honours it.
 
     `text_sampler="device"` (opt-in; the default "torch" is the reference's path, draw for draw; needs temperature > 0, `sampler_seed`,
-    one rank and a forward without micro-batched lanes, anything else raises ValueError): without guidance a step is ONE
+    one rank (or such a tensor-parallel group) and a forward without micro-batched lanes, anything else raises ValueError): without guidance a step is ONE
     mmada_text_select_sampled call on the current block's rows — a Gumbel-max draw inside the LM head's GEMM, no logits exist — and
     with guidance mmada_head_rows into a fixed [2 * B * block_length, V] buffer, mmada_text_draw_cfg on its halves and the unchanged
     mmada_text_select_cfg.  It draws from soft-max(l / temperature) evaluated in fp32 where the reference takes exp(l) / (-log u)^T

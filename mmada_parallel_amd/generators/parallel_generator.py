@@ -162,7 +162,7 @@ def _ti2ti_steps(
     mmada_text_select_sampled call — a Gumbel-max draw inside the LM head's GEMM with a counter-based generator keyed by
     `sampler_seed` (required) and a counter that starts at 0 per call and advances by 1 per text step.  Neither the [B*T, V] logits
     nor the noise tensor exists.  The draws do not reproduce torch's RNG stream.  Only with text_temperature > 0,
-    remasking == 'low_confidence', on one rank and without micro-batched lanes: anything else raises ValueError.  With
+    remasking == 'low_confidence', on one rank or a tensor-parallel group on the library's pull / copy transport, and without micro-batched lanes: anything else raises ValueError.  With
     temperature == 0 the one randn the reference still draws in an image step (it is multiplied by 0) is drawn ahead of the step's
     launches, outside a capture; torch's stream sees the same values in the same order.
 
@@ -174,7 +174,7 @@ def _ti2ti_steps(
     `sampler_seed` (shared with the text sampler) and a counter of its own that starts at 1 << 62 per call — far from the text
     counter, so a text row and an image row of one step never share (seed, counter, row) — and advances by 1 per image step.  The
     re-mask temperature temperature * (1 - (step + 1) / text_steps) is a device value copied per step outside the captured region,
-    as mask_len is.  Only with temperature > 0 and on one rank: anything else raises ValueError.  The draws do not reproduce torch's
+    as mask_len is.  Only with temperature > 0 and on one rank or a tensor-parallel group on the library's pull / copy transport: anything else raises ValueError.  The draws do not reproduce torch's
     RNG stream."""
     if not isinstance(model, LLaDAForMultiModalGeneration):
         raise TypeError("generate_ti2ti (MI355X) needs mmada_parallel_amd.LLaDAForMultiModalGeneration; "
@@ -439,7 +439,7 @@ def generate_ti2ti(
     `return_state=True` additionally returns the final `combined_input_ids` *before* the random fill of
     still-masked image tokens (reference :360-362) — the quantity parity tests compare.
     `text_sampler="device"` with `sampler_seed`: draw the text tokens inside the LM head's GEMM (see _ti2ti_steps).
-    `image_sampler="device"` with `sampler_seed` (temperature > 0, one rank): draw the image tokens and the re-mask noise in the
+    `image_sampler="device"` with `sampler_seed` (temperature > 0; one rank or a tensor-parallel group on the library's pull / copy transport): draw the image tokens and the re-mask noise in the
     image kernels — no probabilities, no torch.multinomial / randn; with both samplers "device" a temperature > 0 run can replay as
     hipGraphs, bit-identical to the eager run (see _ti2ti_steps)."""
     ids = pos_list = None

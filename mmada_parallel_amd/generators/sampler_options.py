@@ -16,13 +16,17 @@ def check_samplers(model, image_sampler="torch", text_sampler="torch", sampler_s
                    text_temperature=0.0, text_temperature_name="text_temperature",
                    text_rank_note="tensor parallelism is out of scope"):
     """Refuse what a device sampler cannot do; returns (dev_img, dev_text).  First a value that is neither "torch" nor "device",
-    then per sampler that is "device" — text first — a temperature that draws nothing, more than one rank, a missing `sampler_seed`.
+    then per sampler that is "device" — text first — a temperature that draws nothing, a tensor-parallel model other than a group of two or
+    more ranks on the library's pull or copy transport (the "one rank" refusals), a missing `sampler_seed`.
     temperature: the image temperature, for the generators whose image step is an arg-max at 0 (None: not checked).
     text_temperature_name: what the caller's signature calls the text temperature (mmu_generate: `temperature`)."""
     for name, value in (("text_sampler", text_sampler), ("image_sampler", image_sampler)):
         if value not in ("torch", "device"):
             raise ValueError(f"{name}={value!r}: 'torch' or 'device'")
     dev_img, dev_text = image_sampler == "device", text_sampler == "device"
+    # two or more ranks whose exchange runs in the library over a mapped transport: the sampling head is vocabulary-parallel
+    # (model.vocab_parallel_row_heads) and the image-side kernels read logits every rank holds alike
+    vocab_parallel = model.tp_size >= 2 and model._comm_in_library and model.tp_collective in ("pull", "copy")
     needs = []
     if dev_text:
         needs.append(("text_sampler", text_temperature > 0,
@@ -34,7 +38,7 @@ def check_samplers(model, image_sampler="torch", text_sampler="torch", sampler_s
         why = None
         if not draws:
             why = why_draws
-        elif model.tp_size != 1 or model._comm_in_library:
+        elif (model.tp_size != 1 or model._comm_in_library) and not vocab_parallel:
             why = f"one rank ({rank_note})"
         elif sampler_seed is None:
             why = "sampler_seed"

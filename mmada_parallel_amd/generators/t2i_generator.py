@@ -47,7 +47,7 @@ def _t2i_steps(
     """Step generator shared by t2i_generate and t2i_generate_decoding_stepwise: yields (step, sampled_ids) right after
     the draw of every step (where the stepwise variant decodes, :841-848), then commits the step.
 
-    `image_sampler="device"` with `sampler_seed` (opt-in, one rank): a step is mmada_head_rows, mmada_image_sample_m and
+    `image_sampler="device"` with `sampler_seed` (opt-in; one rank or a tensor-parallel group on the library's pull / copy transport): a step is mmada_head_rows, mmada_image_sample_m and
     mmada_image_commit_m_sampled as in interleave_generate — no probabilities, no torch random tensor, `rng` / `generator` never
     called; the counter starts at 1 << 62 and advances by 1 per step.  The cumulative temperature (:349) stays host arithmetic, each
     step's value handed over through a device [1] buffer.  The commit has then run when the step's sampled ids are yielded (they are

@@ -462,6 +462,11 @@ class LLaDAForMultiModalGeneration(TpLinkMixin):
                                                         abi.stream_ptr()), "mmada_head_logprobs")
         return (lp, *stats) if return_stats else lp
 
+    def vocab_parallel_row_heads(self) -> bool:
+        """top_logprobs / sample_tokens (and the generators' device samplers) run their vocabulary-parallel form: a group of two or
+        more ranks whose exchange runs in the library over a mapped transport.  Every rank must then make the same calls."""
+        return self.tp_size >= 2 and self._comm_in_library and self.tp_collective in ("pull", "copy")
+
     _TP_TOPK = ("top_logprobs runs on one rank: the library's top-k head (mmada_head_topk) refuses a tensor-parallel handle; the "
                 "vocabulary-parallel top-k, whose key records would ride the score exchange, is a follow-up")
 
@@ -472,8 +477,12 @@ class LLaDAForMultiModalGeneration(TpLinkMixin):
 
         Order of a row: logit descending, then column ascending (a stable descending sort).  logprobs = logit - lse in fp32, the
         expression of token_logprobs: top_logprobs(rows, k)[1][:, j] equals token_logprobs(rows, ids[:, j]) bit for bit, and lse,
-        ids[:, 0] are its lse / argmax.  rows as in token_logprobs (batch-major on a micro-batched forward).  One rank only."""
-        if self.tp_size != 1 or self._comm_in_library:
+        ids[:, 0] are its lse / argmax.  rows as in token_logprobs (batch-major on a micro-batched forward).
+
+        One rank, or a tensor-parallel group of two or more ranks with the library's exchange connected over the pull or the copy
+        transport: every rank must make the call, the tiles' key records ride the score exchange of token_logprobs and every rank
+        returns the same bits — those of a one-rank handle on the same normalised rows.  The call never synchronises the host."""
+        if (self.tp_size != 1 or self._comm_in_library) and not self.vocab_parallel_row_heads():
             raise NotImplementedError(self._TP_TOPK)
         col_end = self.vocab if col_end is None else col_end
         if not 1 <= k <= TOPK_MAX or k > col_end - col_begin:
@@ -515,8 +524,11 @@ class LLaDAForMultiModalGeneration(TpLinkMixin):
         are its return_stats values.  temperature is finite and >= 0; at 0 the draw is the arg-max.  The noise is a pure function of (seed,
         counter, r, column) — r the row's index in `rows` — so a call is reproducible: `counter` (int64 [1] on the device, default
         the model's own, `sample_counter`) is read by the call and incremented by 1 on the device; reset it to repeat a draw.
-        The draws do not reproduce torch's RNG stream.  One rank only, and not on a micro-batched forward."""
-        if self.tp_size != 1 or self._comm_in_library:
+        The draws do not reproduce torch's RNG stream.  Not on a micro-batched forward.
+
+        One rank, or a tensor-parallel group as in top_logprobs: every rank must make the same calls with the same seed; each
+        rank's counter lives on that rank and advances alike, and every rank draws the same ids."""
+        if (self.tp_size != 1 or self._comm_in_library) and not self.vocab_parallel_row_heads():
             raise NotImplementedError(self._TP_SAMPLE)
         if self._resident.split is not None:
             raise NotImplementedError(self._LANES_SAMPLE)

@@ -370,6 +370,33 @@ def check_tp_score_join(asm=None):
     return report, errors
 
 
+def check_tp_key_joins(asm=None):
+    """The joins of the vocabulary-parallel top-k head and draw (tp_topk_join_kernel, tp_sample_join_kernel): as for the score
+    join, a peer's records — the 16-byte record and the key records behind it — arrive as single 16-byte system-scope loads
+    through descriptors held in SGPRs (no waterfall loop, nothing narrower at system scope) and nothing spills."""
+    asm = asm or device_asm("tp_heads.hip")
+    body, meta = kernels(asm)
+    report, errors = [], []
+    for name, lines in body.items():
+        if "tp_topk_join_kernel" not in name and "tp_sample_join_kernel" not in name:
+            continue
+        x4 = sum(1 for ln in lines if re.search(r"buffer_load_dwordx4 .*sc0 sc1", ln))
+        narrow = sum(1 for ln in lines if re.search(r"(global|buffer|flat)_load_(dword|dwordx2|dwordx3) .*sc0 sc1", ln))
+        priv = int(meta.get(name, {}).get("private_segment_fixed_size", "0"))
+        report.append((name, x4, int(meta.get(name, {}).get("group_segment_fixed_size", "0"))))
+        if x4 < 2:
+            errors.append(f"{name}: {x4} 16-byte system-scope loads (the record and the key record: at least 2)")
+        if narrow:
+            errors.append(f"{name}: {narrow} system-scope loads narrower than 16 bytes")
+        if any("v_readfirstlane" in ln for ln in lines):
+            errors.append(f"{name}: waterfall loop around a buffer load (descriptor not provably wave-uniform)")
+        if priv or any(re.match(r"\s*scratch_", ln) for ln in lines):
+            errors.append(f"{name}: private segment of {priv} bytes / scratch accesses")
+    if len(report) != 2:
+        errors.append(f"{len(report)} key-join kernels found (tp_topk_join_kernel and tp_sample_join_kernel expected)")
+    return report, errors
+
+
 def main():
     bad = []
     rep, err = check_gemm8()
@@ -389,6 +416,10 @@ def main():
         print(f"tp     {name[:90]:90s} sc0 sc1 loads: dwordx4 {x4}  dwordx2 {x2}")
     bad += err
     rep, err = check_tp_score_join()
+    for name, x4, lds in rep:
+        print(f"tp     {name[:90]:90s} sc0 sc1 loads: dwordx4 {x4}  LDS {lds} B")
+    bad += err
+    rep, err = check_tp_key_joins()
     for name, x4, lds in rep:
         print(f"tp     {name[:90]:90s} sc0 sc1 loads: dwordx4 {x4}  LDS {lds} B")
     bad += err

@@ -23,6 +23,12 @@ device (tp_link.connect_local_group, pull transport): they share its compute uni
 
 (t) / (c) is what the split and the k joins cost on top of the one-rank call; on k devices each rank's share runs in parallel.
 
+    python tools/score_bench.py --tp 2 --topk 8 | --sample [--out profiles/heads_tp_bench.txt]
+
+--tp k with --topk K or --sample: the same rig and the same three rows for the vocabulary-parallel top-k head (top_logprobs) or
+draw (sample_tokens at temperature 0.7): (c) the one-rank call, (t) the call on every rank of the group, (h) head_rows on one
+rank + torch.topk / logsumexp, or + the generator's add_gumbel_noise and an arg-max.  The lines are APPENDED to --out.
+
     python tools/score_bench.py --topk 8 [--out profiles/topk_bench.txt]
 
 --topk K: the K likeliest columns of every row and the row's lse, three ways, timed the same way (interleaved, device events):
@@ -90,7 +96,8 @@ def main_tp(args):
     ranks, streams = tp_rig(cfg, sd, k, 2 * ((L + 7) // 8 * 8), dev)
     del sd
     V = plain.vocab
-    lines = [f"score_bench --tp {k}: FUNCTIONAL RIG: {k} ranks as handles of one process on ONE {torch.cuda.get_device_name(0)} (pull transport, "
+    head = f"top-k {args.topk}" if args.topk else "sample (T = 0.7)" if args.sample else "score"
+    lines = [f"score_bench --tp {k} [{head}]: FUNCTIONAL RIG: {k} ranks as handles of one process on ONE {torch.cuda.get_device_name(0)} (pull transport, "
              f"no link involved); d = {cfg['d_model']}, V = {V}, {args.rounds} rounds x {args.reps} calls, device events, ms per call"]
     for B in (1, 2):
         R = B * L
@@ -103,20 +110,43 @@ def main_tp(args):
         torch.cuda.synchronize()
         logits = torch.empty((R, V), dtype=torch.bfloat16, device=dev)
 
+        if args.topk:       # the result compared below: the log-probability of the likeliest column
+            from_call = lambda m: m.top_logprobs(rows, args.topk)[1][:, 0]   # noqa: E731
+
+            def run_h():
+                ranks[0].head_rows(rows, 0, V, out=logits)
+                lf = logits.float()
+                return torch.topk(lf, args.topk, dim=1).values[:, 0] - torch.logsumexp(lf, 1)
+        elif args.sample:   # the drawn ids (the torch draw is another stream of noise: nothing to compare)
+            from mmada_parallel_amd.generators.parallel_generator import add_gumbel_noise
+
+            for m in [plain] + ranks:
+                m.sample_counter.zero_()   # (created here, outside the timed windows)
+            torch.cuda.synchronize()
+            from_call = lambda m: m.sample_tokens(rows, 0.7, seed=1234)[0]   # noqa: E731
+
+            def run_h():
+                ranks[0].head_rows(rows, 0, V, out=logits)
+                return add_gumbel_noise(logits, temperature=0.7).argmax(1)
+        else:
+            from_call = lambda m: m.token_logprobs(rows, targets)   # noqa: E731
+
+            def run_h():
+                ranks[0].head_rows(rows, 0, V, out=logits)
+                return torch.log_softmax(logits.float(), -1).gather(1, targets[:, None])[:, 0]
+
         def run_c():
-            return plain.token_logprobs(rows, targets)
+            return from_call(plain)
 
         def run_t():
-            return on_every_rank(ranks, streams, lambda m: m.token_logprobs(rows, targets))
-
-        def run_h():
-            ranks[0].head_rows(rows, 0, V, out=logits)
-            return torch.log_softmax(logits.float(), -1).gather(1, targets[:, None])[:, 0]
+            return on_every_rank(ranks, streams, from_call)
 
         fns = {"c": run_c, "t": run_t, "h": run_h}
         got, ref = run_t(), run_h()
         torch.cuda.synchronize()
         assert all(torch.equal(x, got[0]) for x in got), "the ranks disagree"
+        if args.sample:
+            ref = got[0]
         for m in ranks:
             assert m.comm_status()["error"] == 0, m.comm_status()
         worst = float((ref - got[0]).abs().max())
@@ -138,7 +168,8 @@ def main_tp(args):
             assert m.comm_status()["error"] == 0, m.comm_status()
         med = {n: statistics.median(v) for n, v in times.items()}
         ratio = [t / c for c, t in zip(times["c"], times["t"])]
-        lines.append(f"R = {R} (B = {B}, L = {L}); ranks bit-identical; max |fused TP - torch on the same rank's logits| log-probability {worst:.2e}")
+        lines.append(f"R = {R} (B = {B}, L = {L}); ranks bit-identical" + ("" if args.sample else
+                     f"; max |fused TP - torch on the same rank's logits| log-probability {worst:.2e}"))
         names = {"c": "(c) fused, one rank (TP = 1 model)", "t": f"(t) fused, {k} ranks, summed device time", "h": "(h) one TP rank: head_rows + torch"}
         for n in order:
             lines.append(f"  {names[n]:42s} median {med[n]:8.3f}  min {min(times[n]):8.3f}  max {max(times[n]):8.3f}")
@@ -148,7 +179,7 @@ def main_tp(args):
     text = "\n".join(lines)
     print(text)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
+    with open(args.out, "a" if args.topk or args.sample else "w") as f:
         f.write(text + "\n")
 
 
@@ -334,20 +365,21 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "score_tp_bench.txt" if args.tp else "topk_bench.txt" if args.topk else
+        args.out = os.path.join(ROOT, "profiles", "heads_tp_bench.txt" if args.tp and (args.topk or args.sample) else
+                                "score_tp_bench.txt" if args.tp else "topk_bench.txt" if args.topk else
                                 "sample_bench.txt" if args.sample else "score_bench.txt")
-    if args.sample:
-        if args.tp or args.topk:
-            ap.error("--sample takes no --tp / --topk")
-        return main_sample(args)
-    if args.topk:
-        if args.tp or not 1 <= args.topk <= 8:
-            ap.error("--topk takes K in 1..8 and no --tp")
-        return main_topk(args)
+    if args.topk and not 1 <= args.topk <= 8:
+        ap.error("--topk takes K in 1..8")
+    if args.sample and args.topk:
+        ap.error("--sample takes no --topk")
     if args.tp:
         if args.tp not in (2, 4, 8):
             ap.error("--tp must be 2, 4 or 8")
         return main_tp(args)
+    if args.sample:
+        return main_sample(args)
+    if args.topk:
+        return main_topk(args)
     dev = "cuda:0"
     cfg = dict(synth.CFG_8B, n_layers=1)
     sd = synth.synthetic_state_dict(cfg, seed=3, device=dev)
