@@ -25,7 +25,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB_NAME = "libmmada_mi355x.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 SOURCES = ["gemm.hip", "gemm8.hip", "row_heads.hip", "attention.hip", "elementwise.hip", "sampler.hip", "vq_kernels.hip", "vq_net.hip", "graph.hip", "tp_comm.hip", "tp_heads.hip", "probe.hip", "api.hip", "forward.hip", "cache.hip", "heads.hip"]
-HEADERS = ["exports.map", "common.h", "kernels.h", "gemm_epilogue.h", "row_heads.h", "row_head_epilogue.h", "sample_noise.h", "handle.h", "tp_comm.h", "attention.h", "vq.h", os.path.join("..", "..", "include", "mmada_mi355x.h")]
+HEADERS = ["exports.map", "common.h", "kernels.h", "gemm_epilogue.h", "row_heads.h", "row_head_join.h", "row_head_epilogue.h", "sample_noise.h", "handle.h", "tp_comm.h", "tp_plan.h", "attention.h", "vq.h", os.path.join("..", "..", "include", "mmada_mi355x.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wno-unused-result"]
 # per-unit flags.  attention: hipcc's SLP vectoriser pairs the fp32 row-sum adds and rescale multiplies into v_pk_*_f32, which
 # cost more issue time beside MFMAs than the two scalar operations they replace (MI355X guide, per-instruction constants);

@@ -1,5 +1,5 @@
 // row_heads.h — the contract of the LM head's row heads (host and device): what the launchers (row_heads.hip, tp_heads.hip), the
-// GEMM epilogue (row_head_epilogue.h) and the joining kernels must agree on.  Nothing of D = A · lm_head[col0 : col0 + N]^T is
+// GEMM epilogue (row_head_epilogue.h) and the joins (row_head_join.h) must agree on.  Nothing of D = A · lm_head[col0 : col0 + N]^T is
 // stored: per row m < rows and 256-column tile nt the GEMM leaves records over the bf16-rounded logits x of that tile.
 //   EPI_ROWSTAT   (scoring, mmada_head_logprobs)  part[nt * ld + m] = {max, sum exp(x - max), first column of the max in the whole
 //                 vocabulary (int bits), 0}, and the logit at column target[m] - col0 (if that is a column of the launch) to tx[m].
@@ -65,9 +65,19 @@ static inline const char* row_head_args_fault(int head, const RowHeadArgs& a, in
                                  : "gemm/rowsample: record buffers or counter missing, or a temperature that is not finite and >= 0";
 }
 
+// The GEMM of head `head`: A [M, K] (M: `a.rows` rounded up to 8) times W = lm_head rows [a.col0, a.col0 + N), with the records
+// going where the caller has carved a.part / a.tx / a.extra.  publish: the records are read by other ranks (GemmArgs::publish).
+// (row_heads.hip; the one launch of both the one-rank heads and a round of the tensor-parallel ones.)
+int launch_row_head_gemm(int head, const bf16_t* A, const bf16_t* W, int M, int N, int K, const RowHeadArgs& a, bool publish, hipStream_t s);
+
+// Bytes of a head's extra record per (row, tile): none (scoring), the tile's keys (top-k), one triple (sample)
+constexpr uint32_t row_head_extra_bytes(int head) {
+    return head == EPI_ROWTOPK ? TOPK_MAX * (uint32_t)sizeof(uint32_t) : head == EPI_ROWSAMPLE ? (uint32_t)sizeof(float4) : 0u;
+}
+
 // ---- the record buffer of a one-rank launch: records | target logits | extra records.  Per row 1/32 (scoring), 3/32 (top-k) or
-// 1/16 (sample) of the bytes of the bf16 logits it stands for, plus 4 bytes.  (The tensor-parallel score exchange publishes its
-// records in a layout of its own: tp_comm.h, ScoreLayout.)
+// 1/16 (sample) of the bytes of the bf16 logits it stands for, plus 4 bytes.  (The tensor-parallel heads publish their records in
+// a layout of their own: tp_comm.h, ScoreLayout.)
 struct RowHeadLayout {
     int rp, ntn;                   // rows rounded up to 8 (the records' leading dimension), 256-column tiles
     size_t part, tx, extra, bytes; // byte offsets of the three sub-buffers, total size
@@ -77,11 +87,10 @@ static inline RowHeadLayout row_head_layout(int R, int N, int head) {
     l.rp = (R + 7) / 8 * 8;
     l.ntn = (N + ROW_HEAD_BN - 1) / ROW_HEAD_BN;
     const size_t recs = (size_t)l.rp * l.ntn;
-    const size_t extra_rec = head == EPI_ROWTOPK ? TOPK_MAX * sizeof(uint32_t) : head == EPI_ROWSAMPLE ? sizeof(float4) : 0;
     l.part = 0;
     l.tx = recs * sizeof(float4);
     l.extra = l.tx + (size_t)l.rp * sizeof(float);
-    l.bytes = l.extra + recs * extra_rec;
+    l.bytes = l.extra + recs * row_head_extra_bytes(head);
     return l;
 }
 
@@ -103,83 +112,8 @@ static inline __host__ __device__ float topk_key_logit(uint32_t key) {   // inve
     __builtin_memcpy(&x, &u, 4);
     return x;
 }
-// A candidate of the top-k joins (row_heads.hip, tp_heads.hip): {order value of the logit, ~column inside the launch} as one 64-bit
-// number — logit descending, then tile ascending, then column ascending is ONE unsigned compare, and candidates of a row are
-// distinct.  0: no candidate.
-MM_DEVICE unsigned long long topk_cand(uint32_t key, int tile) {
-    if (key == 0u) return 0ull;
-    const uint32_t col = (uint32_t)tile * (uint32_t)ROW_HEAD_BN + (255u - (key & 255u));
-    return ((unsigned long long)(key >> 16) << 32) | (unsigned long long)(~col);
-}
-// best[] stays sorted in descending order; c replaces the last entry and moves up to its place
-MM_DEVICE void topk_insert(unsigned long long (&best)[TOPK_MAX], unsigned long long c) {
-    best[TOPK_MAX - 1] = c;
-#pragma unroll
-    for (int i = TOPK_MAX - 1; i > 0; --i) {
-        const unsigned long long lo = best[i], hi = best[i - 1];
-        best[i - 1] = lo > hi ? lo : hi;
-        best[i] = lo > hi ? hi : lo;
-    }
-}
 
-// ---- the order of the sampling head's triples {key, column, logit}: highest key, then lowest column
+// ---- the order of the sampling head's triples {key, column, logit}: highest key, then lowest column (the epilogue's and the join's)
 MM_DEVICE void rowsample_take(float& k, int& c, float& x, float ok, int oc, float ox) {
     if (ok > k || (ok == k && oc < c)) { k = ok; c = oc; x = ox; }
-}
-
-// ---- the one fold of a row's column-tile records into {max, sum exp(x - max), first arg-max}, shared by the one-rank joins
-// (row_heads.hip) and the tensor-parallel join (tp_heads.hip: tp_score_join_kernel), so that they cannot drift apart: the order
-// below IS the result's definition.
-// Joins the column-tile records of a row in a FIXED order (so that neither the tile order of the GEMM nor its configuration
-// nor the rank that produced a tile shows in the result): 16 rows x 16 tile groups per workgroup; group j folds tiles j, j + 16,
-// ... in ascending order (online soft-max: rescale by exp(m_tile - m_row)), then thread (row, 0) folds the 16 groups in ascending
-// order.
-constexpr int RS_ROWS = 16, RS_GROUPS = 16;
-
-// Called by every thread of a workgroup of RS_ROWS * RS_GROUPS threads (thread = (row rl, group j), row = blockIdx.x * RS_ROWS + rl).
-// fetch(t, row) -> float4 record of tile t.  Returns true on the one thread per row (< R) that holds the row's result.
-template <class Fetch>
-MM_DEVICE bool rowstat_fold(Fetch fetch, int row, int R, int ntn, float& m, float& sum, int& arg) {
-    __shared__ float sm[RS_GROUPS][RS_ROWS], ss[RS_GROUPS][RS_ROWS];
-    __shared__ int sa[RS_GROUPS][RS_ROWS];
-    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
-    m = -__builtin_inff(); sum = 0.f;
-    arg = 0x7fffffff;
-    if (row < R)
-        for (int t = j; t < ntn; t += RS_GROUPS) {
-            const float4 p = fetch(t, row);
-            const int a = __float_as_int(p.z);
-            if (p.x > m) {   // tiles ascend inside a group: an equal maximum further right does not replace
-                sum = sum * expf(m - p.x) + p.y;
-                m = p.x;
-                arg = a;
-            } else
-                sum += p.y * expf(p.x - m);
-        }
-    sm[j][rl] = m; ss[j][rl] = sum; sa[j][rl] = arg;
-    __syncthreads();
-    if (j != 0 || row >= R) return false;
-    for (int q = 1; q < RS_GROUPS; ++q) {
-        const float mq = sm[q][rl], sq = ss[q][rl];
-        const int aq = sa[q][rl];
-        if (mq > m) {
-            sum = sum * expf(m - mq) + sq;
-            m = mq;
-            arg = aq;
-        } else if (mq > -__builtin_inff()) {
-            sum += sq * expf(mq - m);
-            if (mq == m && aq < arg) arg = aq;   // groups interleave the tiles: the leftmost column wins
-        }
-    }
-    return true;
-}
-
-// The row's outputs from its fold and its target logit tx (-inf: the target is no column of the range)
-MM_DEVICE void rowstat_finish(int row, float m, float sum, int arg, long long target, float tx, float* logprob, float* lse_out,
-                              int32_t* argmax_out, float* max_out) {
-    const float lse = m + logf(sum);
-    logprob[row] = target < 0 ? 0.f : tx - lse;
-    if (lse_out) lse_out[row] = lse;
-    if (argmax_out) argmax_out[row] = arg;
-    if (max_out) max_out[row] = m;
 }

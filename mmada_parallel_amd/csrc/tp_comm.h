@@ -1,5 +1,5 @@
 // tp_comm.h — state and small helpers shared by the two tensor-parallel units: tp_comm.hip (transports, the exchange, the
-// forward) and tp_heads.hip (the vocabulary-parallel text and scoring heads).  Private to them: every other unit sees the
+// forward) and tp_heads.hip (the vocabulary-parallel text head and row heads: scoring, top-k, the draw).  Private to them: every other unit sees the
 // opaque `struct TpComm;` and the function declarations of handle.h only.
 #pragma once
 #include <rccl/rccl.h>

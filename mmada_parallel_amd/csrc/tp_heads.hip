@@ -1,7 +1,7 @@
 // tp_heads.hip — the LM head under tensor parallelism, on the transports of tp_comm.hip: the row gather in front of every head,
 // the vocabulary-parallel text head (mmada_text_select_tp) and the vocabulary-parallel row heads: scoring, top-k and the
 // Gumbel-max draw (tp_head_logprobs, tp_head_topk, tp_head_sample — one round loop, three joins).
-#include "row_heads.h"
+#include "row_head_join.h"
 #include "tp_comm.h"
 
 static_assert(SCORE_BN == ROW_HEAD_BN, "the published score records are the one-rank launch's, tile for tile");
@@ -62,7 +62,8 @@ __global__ __launch_bounds__(256) void tp_score_reset_kernel(float* tx, int n) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// Where a join finds the records of a round: what the round loop (tp_head_rounds) hands every head's join
+// Where a join finds the records of a round — the record source (row_head_join.h) of the three joins below: tile t's records
+// come from the rank that owns t.  What the round loop (tp_head_rounds) hands every head's join.
 struct JoinSrc {
     const char* src[TP_MAX];  // rank j's record buffer of this round where THIS rank reads it: its own memory, a peer's mapped
                               // buffer (pull) or the gathered / staged copy (RCCL, copy)
@@ -71,142 +72,74 @@ struct JoinSrc {
     int q;                    // tiles per rank: tile t is record (t - owner * q) of rank owner = t / q
     uint32_t rec_off;         // byte offset of the records behind the target logits
     int ld, ntn, R;
-};
-struct ScoreJoinArgs : JoinSrc {
-    int col_begin, col_end;
-    const int64_t* targets;
-    float *logprob, *lse;
-    int32_t* argmax;
-    float* vmax;
-};
-// The top-k and the sampling join: extra record of tile t at x_off(owner) + (t - owner * q) * ld + row, in units of the record
-struct KeyJoinArgs : JoinSrc {
-    int col0, k;              // top-k: first column of the launch, places to write
-    int32_t* ids;             // top-k [R, k], sample [R]
-    float *out, *lse;         // top-k: logits [R, k]; sample: logprob [R]
-    int32_t* argmax;          // sample only (or null), like vmax
-    float* vmax;
-    float* spare;             // top-k: [ld] private floats (the join's unused log-probabilities)
-    uint64_t* counter;        // sample, last round of a call: this rank's counter, + 1; else null
-};
+    int col_begin, col_end;   // the call's column range (the owner of a target's tile)
 
-// 16 bytes at byte offset `off` of the buffer of rank `owner` (per lane; src[o] is a kernel argument in SGPRs).  The lanes of a
-// wave hold neighbouring tiles, which may belong to two owners: one pass per rank (unrolled) keeps the base pointer
-// wave-uniform, as load_sys16's descriptor needs it
-MM_DEVICE u32x4 join_load16(const JoinSrc& a, int owner, uint32_t off) {
-    u32x4 v = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int o = 0; o < TP_MAX; ++o) {
-        if (o != owner) continue;
-        if (a.sys && o != a.rank) v = load_sys16(a.src[o], off);
-        else v = *(const u32x4*)(a.src[o] + off);
-    }
-    return v;
-}
-// tile t's 16-byte record of row r, and the byte offset of its extra record of `bytes` bytes (behind the owner's records)
-MM_DEVICE float4 join_record(const JoinSrc& a, int t, int r) {
-    const int owner = t / a.q;
-    const u32x4 v = join_load16(a, owner, a.rec_off + ((uint32_t)(t - owner * a.q) * (uint32_t)a.ld + (uint32_t)r) * 16u);
-    return float4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
-}
-MM_DEVICE uint32_t join_extra_off(const JoinSrc& a, int t, int r, uint32_t bytes) {
-    const int owner = t / a.q, nt = min(a.ntn, (owner + 1) * a.q) - owner * a.q;   // tiles the owner has in this call (t is one)
-    return a.rec_off + (uint32_t)nt * (uint32_t)a.ld * 16u + ((uint32_t)(t - owner * a.q) * (uint32_t)a.ld + (uint32_t)r) * bytes;
-}
-
-// The join of rowstat_combine_kernel (row_heads.hip) with tile t's record taken from the rank that owns t: the same fold
-// (row_heads.h: rowstat_fold), so every rank — and a one-rank handle — ends with the same bits.  Every rank joins every row.
-__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_score_join_kernel(ScoreJoinArgs a) {
-    if (a.sys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // see tp_reduce_norm_kernel
-    const int row = blockIdx.x * RS_ROWS + threadIdx.x % RS_ROWS;
-    float m, sum;
-    int arg;
-    if (!rowstat_fold([&](int t, int r) { return join_record(a, t, r); }, row, a.R, a.ntn, m, sum, arg)) return;
-    const long long t = a.targets[row];
-    float tx = -__builtin_inff();
-    if (t >= a.col_begin && t < a.col_end) {  // the target logit lives with the rank that owns the target's tile
-        const int owner = (int)((t - a.col_begin) / SCORE_BN) / a.q;
+    // 16 bytes at byte offset `off` of the buffer of rank `owner` (per lane; src[o] is a kernel argument in SGPRs).  The lanes of
+    // a wave hold neighbouring tiles, which may belong to two owners: one pass per rank (unrolled) keeps the base pointer
+    // wave-uniform, as load_sys16's descriptor needs it
+    MM_DEVICE u32x4 load16(int owner, uint32_t off) const {
+        u32x4 v = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int o = 0; o < TP_MAX; ++o) {
             if (o != owner) continue;
-            const float* p = (const float*)a.src[o] + row;
-            tx = (a.sys && o != a.rank) ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : *p;
+            if (sys && o != rank) v = load_sys16(src[o], off);
+            else v = *(const u32x4*)(src[o] + off);
         }
+        return v;
     }
-    rowstat_finish(row, m, sum, arg, t, tx, a.logprob, a.lse, a.argmax, a.vmax);
-}
+    // byte offset of tile t's extra record of `bytes` bytes for row r (behind the owner's records)
+    MM_DEVICE uint32_t extra_off(int t, int r, uint32_t bytes) const {
+        const int owner = t / q, nt = min(ntn, (owner + 1) * q) - owner * q;   // tiles the owner has in this call (t is one)
+        return rec_off + (uint32_t)nt * (uint32_t)ld * 16u + ((uint32_t)(t - owner * q) * (uint32_t)ld + (uint32_t)r) * bytes;
+    }
+    static MM_DEVICE float4 as_float4(u32x4 v) {
+        return float4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
+    }
 
-// The join of rowtopk_combine_kernel (row_heads.hip) with tile t's key record taken from the rank that owns t: the candidates
-// (row_heads.h: topk_cand) are totally ordered, so neither the walk's order nor the owner shows in the result.
-__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_topk_join_kernel(KeyJoinArgs a) {
-    __shared__ unsigned long long sk[RS_GROUPS][TOPK_MAX][RS_ROWS];
-    if (a.sys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // see tp_reduce_norm_kernel
-    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
-    const int row = blockIdx.x * RS_ROWS + rl;
-    unsigned long long best[TOPK_MAX];
+    MM_DEVICE float4 record(int t, int r) const {
+        const int owner = t / q;
+        return as_float4(load16(owner, rec_off + ((uint32_t)(t - owner * q) * (uint32_t)ld + (uint32_t)r) * 16u));
+    }
+    MM_DEVICE void topk_keys(int t, int r, uint32_t (&key)[TOPK_MAX]) const {
+        const uint32_t off = extra_off(t, r, row_head_extra_bytes(EPI_ROWTOPK));
+        const u32x4 lo = load16(t / q, off), hi = load16(t / q, off + 16u);
+        key[0] = lo[0]; key[1] = lo[1]; key[2] = lo[2]; key[3] = lo[3];
+        key[4] = hi[0]; key[5] = hi[1]; key[6] = hi[2]; key[7] = hi[3];
+    }
+    MM_DEVICE float4 sample_triple(int t, int r) const {
+        return as_float4(load16(t / q, extra_off(t, r, row_head_extra_bytes(EPI_ROWSAMPLE))));
+    }
+    MM_DEVICE float target_logit(int row, long long t) const {
+        float tx = -__builtin_inff();
+        if (t >= col_begin && t < col_end) {  // the target logit lives with the rank that owns the target's tile
+            const int owner = (int)((t - col_begin) / SCORE_BN) / q;
 #pragma unroll
-    for (int e = 0; e < TOPK_MAX; ++e) best[e] = 0ull;
-    if (row < a.R)
-        for (int t = j; t < a.ntn; t += RS_GROUPS) {
-            const uint32_t off = join_extra_off(a, t, row, TOPK_MAX * 4u);
-            const u32x4 lo = join_load16(a, t / a.q, off), hi = join_load16(a, t / a.q, off + 16u);
-            const uint32_t key[TOPK_MAX] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-            for (int e = 0; e < TOPK_MAX; ++e) {
-                const unsigned long long c = topk_cand(key[e], t);
-                if (c <= best[TOPK_MAX - 1]) break;
-                topk_insert(best, c);
+            for (int o = 0; o < TP_MAX; ++o) {
+                if (o != owner) continue;
+                const float* p = (const float*)src[o] + row;
+                tx = (sys && o != rank) ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : *p;
             }
         }
-#pragma unroll
-    for (int e = 0; e < TOPK_MAX; ++e) sk[j][e][rl] = best[e];
-    float m, sum;
-    int arg;
-    // (its barrier also orders the candidate lists above)
-    if (!rowstat_fold([&](int t, int r) { return join_record(a, t, r); }, row, a.R, a.ntn, m, sum, arg)) return;
-    for (int q = 1; q < RS_GROUPS; ++q)
-#pragma unroll
-        for (int e = 0; e < TOPK_MAX; ++e) {
-            const unsigned long long c = sk[q][e][rl];
-            if (c <= best[TOPK_MAX - 1]) break;
-            topk_insert(best, c);
-        }
-#pragma unroll
-    for (int e = 0; e < TOPK_MAX; ++e)
-        if (e < a.k) {
-            a.ids[(size_t)row * a.k + e] = a.col0 + (int)~(uint32_t)best[e];
-            a.out[(size_t)row * a.k + e] = topk_key_logit((uint32_t)(best[e] >> 32) << 16);
-        }
-    rowstat_finish(row, m, sum, arg, -1, 0.f, a.spare, a.lse, nullptr, nullptr);
-}
-
-// The join of rowsample_combine_kernel (row_heads.hip) with tile t's triple taken from the rank that owns t: rowsample_take is a
-// total order (key, then column).  With a.counter (the last round of a call) this is the call's last kernel: every GEMM of this
-// rank has read *counter.
-__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_sample_join_kernel(KeyJoinArgs a) {
-    __shared__ float sk[RS_GROUPS][RS_ROWS], sx[RS_GROUPS][RS_ROWS];
-    __shared__ int sc[RS_GROUPS][RS_ROWS];
-    if (a.sys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // see tp_reduce_norm_kernel
-    const int rl = threadIdx.x % RS_ROWS, j = threadIdx.x / RS_ROWS;
-    const int row = blockIdx.x * RS_ROWS + rl;
-    float bk = -__builtin_inff(), bx = -__builtin_inff();
-    int bc = 0x7fffffff;
-    if (row < a.R)
-        for (int t = j; t < a.ntn; t += RS_GROUPS) {
-            const u32x4 p = join_load16(a, t / a.q, join_extra_off(a, t, row, 16u));
-            rowsample_take(bk, bc, bx, __uint_as_float(p[0]), (int)p[1], __uint_as_float(p[2]));
-        }
-    sk[j][rl] = bk; sc[j][rl] = bc; sx[j][rl] = bx;
-    float m, sum;
-    int arg;
-    // (its barrier also orders the key triples above)
-    const bool mine = rowstat_fold([&](int t, int r) { return join_record(a, t, r); }, row, a.R, a.ntn, m, sum, arg);
-    if (mine) {
-        for (int q = 1; q < RS_GROUPS; ++q) rowsample_take(bk, bc, bx, sk[q][rl], sc[q][rl], sx[q][rl]);
-        a.ids[row] = bc;
-        rowstat_finish(row, m, sum, arg, bc, bx, a.out, a.lse, a.argmax, a.vmax);
+        return tx;
     }
-    if (a.counter && blockIdx.x == 0 && threadIdx.x == 0) *a.counter += 1;
+    MM_DEVICE void acquire() const {
+        if (sys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // see tp_reduce_norm_kernel
+    }
+};
+
+// The joins of row_heads.hip's kernels (the bodies: row_head_join.h) over the ranks' records.  Every rank joins every row.
+__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_score_join_kernel(JoinSrc src, ScoreOut out) {
+    src.acquire();
+    rowstat_join(src, src.R, src.ntn, out);
+}
+__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_topk_join_kernel(JoinSrc src, TopkOut out) {
+    src.acquire();
+    rowtopk_join(src, src.R, src.ntn, out);
+}
+// (with out.counter — the last round of a call — the call's last kernel: every GEMM of this rank has read *counter)
+__global__ __launch_bounds__(RS_ROWS * RS_GROUPS) void tp_sample_join_kernel(JoinSrc src, SampleOut out) {
+    src.acquire();
+    rowsample_join(src, src.R, src.ntn, out);
 }
 
 }  // namespace
@@ -304,8 +237,9 @@ static int tp_head_rounds(mmada_handle* h, const char* who, int head, const int3
     TpComm* c = h->tp;
     if (!transport_connected(c)) return mm_fail("%s: no tensor-parallel transport connected", who);
     if (!h->res.xn_is_final || !resident(h)) return mm_fail("%s: no tensor-parallel forward resident", who);
-    const uint32_t xrec = head == EPI_ROWTOPK ? TOPK_MAX * 4u : head == EPI_ROWSAMPLE ? 16u : 0u;   // bytes of the extra record
-    static_assert(TOPK_MAX * 4u <= SCORE_EXTRA_MAX, "the published buffers hold the larger extra record");
+    const uint32_t xrec = row_head_extra_bytes(head);
+    static_assert(row_head_extra_bytes(EPI_ROWTOPK) <= SCORE_EXTRA_MAX && row_head_extra_bytes(EPI_ROWSAMPLE) <= SCORE_EXTRA_MAX,
+                  "the published buffers hold the larger extra record");
     const bool mapped = peers_mapped(c);
     if (xrec && !mapped)
         return mm_fail("%s: over the RCCL transport the vocabulary-parallel head is not built (nothing on one device can exercise "
@@ -335,18 +269,16 @@ static int tp_head_rounds(mmada_handle* h, const char* who, int head, const int3
             MM_CHECK_HIP(hipGetLastError());
         }
         if (n_own > 0) {
-            GemmArgs g = gemm_bt_args(h->xg + (size_t)r0 * d, h->lm_head + (size_t)c0 * d, nullptr, rp, n_own, d, 8);
             RowHeadArgs ra{};
             fill(ra, r0);
             ra.part = (float4*)(buf + lay.rec_off); ra.tx = tx;
             ra.extra = xrec ? buf + score_extra_off(lay.rec_off, nt_own, rp) : nullptr;
             ra.rows = rr; ra.ld = rp; ra.col0 = c0;
-            set_row_head_args(g, ra);
-            g.publish = mapped;
-            if (launch_gemm(head, g, s)) return 1;
+            if (launch_row_head_gemm(head, h->xg + (size_t)r0 * d, h->lm_head + (size_t)c0 * d, rp, n_own, d, ra, mapped, s)) return 1;
         }
         JoinSrc a{};
         a.sys = c->mode == TP_PULL; a.size = tp; a.rank = c->rank; a.q = q; a.rec_off = lay.rec_off; a.ld = rp; a.ntn = ntn; a.R = rr;
+        a.col_begin = col_begin; a.col_end = col_end;
         if (mapped) {
             if (signal_wait(c, s)) return 1;  // every rank's records of this round are complete
             for (int j = 0; j < tp; ++j) {
@@ -373,19 +305,14 @@ static int tp_head_rounds(mmada_handle* h, const char* who, int head, const int3
     if (bracket && signal_wait(c, s)) return 1;
     return 0;
 }
-static dim3 join_grid(int rr) { return dim3((rr + RS_ROWS - 1) / RS_ROWS); }
 
 int tp_head_logprobs(mmada_handle* h, const int32_t* rows, int R, int col_begin, int col_end, const int64_t* targets,
                      float* logprob, float* lse, int32_t* argmax, float* vmax, hipStream_t s) {
     return tp_head_rounds(
         h, "mmada_head_logprobs", EPI_ROWSTAT, rows, R, col_begin, col_end, s, [&](RowHeadArgs& ra, int r0) { ra.target = targets + r0; },
         [&](const JoinSrc& src, int r0, int rr, bool) {
-            ScoreJoinArgs a{};
-            (JoinSrc&)a = src;
-            a.col_begin = col_begin; a.col_end = col_end; a.targets = targets + r0;
-            a.logprob = logprob + r0; a.lse = lse ? lse + r0 : nullptr; a.argmax = argmax ? argmax + r0 : nullptr;
-            a.vmax = vmax ? vmax + r0 : nullptr;
-            hipLaunchKernelGGL(tp_score_join_kernel, join_grid(rr), dim3(RS_ROWS * RS_GROUPS), 0, s, a);
+            const ScoreOut out{targets + r0, logprob + r0, lse ? lse + r0 : nullptr, argmax ? argmax + r0 : nullptr, vmax ? vmax + r0 : nullptr};
+            hipLaunchKernelGGL(tp_score_join_kernel, join_grid(rr), dim3(RS_ROWS * RS_GROUPS), 0, s, src, out);
         });
 }
 
@@ -394,13 +321,10 @@ int tp_head_topk(mmada_handle* h, const int32_t* rows, int R, int col_begin, int
     return tp_head_rounds(
         h, "mmada_head_topk", EPI_ROWTOPK, rows, R, col_begin, col_end, s, [&](RowHeadArgs&, int) {},
         [&](const JoinSrc& src, int r0, int rr, bool) {
-            KeyJoinArgs a{};
-            (JoinSrc&)a = src;
-            a.col0 = col_begin; a.k = k;
-            a.ids = ids + (size_t)r0 * k; a.out = logits + (size_t)r0 * k; a.lse = lse ? lse + r0 : nullptr;
             // the join's unused log-probabilities go to this rank's own slot of the private staging, which no transport uses
-            a.spare = (float*)(h->tp->score_all + (size_t)h->tp->rank * h->tp->score.buf_bytes);
-            hipLaunchKernelGGL(tp_topk_join_kernel, join_grid(rr), dim3(RS_ROWS * RS_GROUPS), 0, s, a);
+            float* spare = (float*)(h->tp->score_all + (size_t)h->tp->rank * h->tp->score.buf_bytes);
+            const TopkOut out{col_begin, k, ids + (size_t)r0 * k, logits + (size_t)r0 * k, lse ? lse + r0 : nullptr, spare};
+            hipLaunchKernelGGL(tp_topk_join_kernel, join_grid(rr), dim3(RS_ROWS * RS_GROUPS), 0, s, src, out);
         });
 }
 
@@ -410,11 +334,8 @@ int tp_head_sample(mmada_handle* h, const int32_t* rows, int R, int col_begin, i
         h, "mmada_head_sample", EPI_ROWSAMPLE, rows, R, col_begin, col_end, s,
         [&](RowHeadArgs& ra, int r0) { ra.counter = counter; ra.seed = seed; ra.temperature = temperature; ra.row0 = r0; },
         [&](const JoinSrc& src, int r0, int rr, bool last) {
-            KeyJoinArgs a{};
-            (JoinSrc&)a = src;
-            a.ids = ids + r0; a.out = logprob + r0; a.lse = lse ? lse + r0 : nullptr;
-            a.argmax = argmax ? argmax + r0 : nullptr; a.vmax = vmax ? vmax + r0 : nullptr;
-            a.counter = last ? counter : nullptr;   // once per call, behind every GEMM of this rank that reads it
-            hipLaunchKernelGGL(tp_sample_join_kernel, join_grid(rr), dim3(RS_ROWS * RS_GROUPS), 0, s, a);
+            const SampleOut out{ids + r0, logprob + r0, lse ? lse + r0 : nullptr, argmax ? argmax + r0 : nullptr, vmax ? vmax + r0 : nullptr,
+                                last ? counter : nullptr};   // once per call, behind every GEMM of this rank that reads it
+            hipLaunchKernelGGL(tp_sample_join_kernel, join_grid(rr), dim3(RS_ROWS * RS_GROUPS), 0, s, src, out);
         });
 }
